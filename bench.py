@@ -7,10 +7,15 @@
 
 A step = zero_grad + twin forward + JSD loss + backward + [RCCL all-reduce] + fused Adam on one
 synthetic K-distributed clutter batch already resident in HBM (TS:209-219 order).  Prints ONE JSON
-line on rank 0 with `roofline` (dominant MFMA kernel, HIP-event timed inside the timed region)
-and, at N=1, `cpu_baseline` (the CPU oracle timed on the host cores on the SAME batch) and `secondary`
-(BASELINE configs[2]: the bf16 MFMA conv path at B=256, run after the headline's timed region in a child
-process of its own so that it starts from a fresh allocator).
+line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline (`value`,
+`ms_per_step`); --dump-outputs DIR also writes what the last timed step computed (dump_outputs).
+
+--full adds everything else, each part measured after the headline's timed region: `roofline` (dominant
+MFMA kernel, HIP-event timed inside the timed region, plus a fully bracketed breakdown loop),
+`f32_mfma_only`, `reference_loop`, for N > 1 the with / without-overlap `comm` curve, and, at N=1,
+`cpu_baseline` (the CPU oracle timed on the host cores on the SAME batch) and `secondary` (BASELINE
+configs[2]: the bf16 MFMA conv path at B=256, run in a child process of its own so that it starts from a
+fresh allocator).
 
 Nothing in this file touches the GPU (no torch / onet_amd import) before `_self_launch` has had its chance:
 a process that has initialised HIP must not be replaced or forked into ranks."""
@@ -254,8 +259,28 @@ def _self_launch(args, argv):
     return rc
 
 
-SECONDARY_ARGS = ["--gpus", "1", "--conv", "bf16", "--batch", "256", "--warmup", "8", "--steps", "5",
+SECONDARY_ARGS = ["--gpus", "1", "--conv", "bf16", "--batch", "256", "--warmup", "8", "--steps", "5", "--full",
                   "--no-cpu-baseline", "--no-secondary", "--no-reference-loop"]
+DUMP_SAMPLE = 1 << 22      # values of the flat parameter / gradient vectors written by --dump-outputs (16 MiB each in fp32)
+
+
+def dump_outputs(path, model, loss):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, the updated parameters, their gradients and the
+    BatchNorm running statistics -- as float32 .npy files under `path`.  Parameters and gradients (31 M values each) are a
+    fixed sample: the same DUMP_SAMPLE positions of the flat vectors (model.parameters() order) in every run."""
+    import numpy as np
+    params = list(model.parameters())
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    n = flat_p.numel()
+    idx = np.sort(np.random.default_rng(1981).choice(n, min(n, DUMP_SAMPLE), replace=False))
+    idx = torch.from_numpy(idx).to(flat_p.device)
+    arrays = {"loss": loss.detach().reshape(1), "params_sample": flat_p[idx], "grads_sample": flat_g[idx],
+              "bn_running_stats": torch.cat([b.detach().reshape(-1) for k, b in model.named_buffers()
+                                             if k.endswith(("running_mean", "running_var"))])}
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def secondary_config2():
@@ -319,7 +344,16 @@ def parse_args(argv=None):
     ap.add_argument("--host-data", action="store_true", help="synthesise the batch with the NumPy generator on the host")
     ap.add_argument("--no-comm-curve", action="store_true",
                     help="N > 1: skip the two extra loops (single all-reduce after backward; no all-reduce) behind the timed region")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline and per-kernel tables, f32_mfma_only, reference_loop, "
+                         "the N > 1 comm curve, cpu_baseline and secondary (the --no-* options above leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (loss, sampled parameters and gradients, BatchNorm running "
+                         "statistics) as float32 DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if (args.bracket_all or args.mfma_events_only) and not args.full:
+        ap.error("--bracket-all / --mfma-events-only choose the roofline's HIP-event brackets: they need --full")
+    return args
 
 
 def main(args):
@@ -375,20 +409,20 @@ def main(args):
     loss = X_cpu = None
     # the warm-up steps also say which MFMA kernel dominates the step: the timed region then brackets THAT kernel's launches only
     # (HIP events on the launch stream) -- bracketing all ~300 launches of a step costs ~1 ms of it
-    if args.warmup > 0:
+    if args.full and args.warmup > 0:
         ops.profile_start(everything=False)
     for _ in range(args.warmup):
         loss = train_step(onet, opt, X)      # (held like in the timed loop: the caching allocator sees the same liveness pattern)
     barrier()
     dom_kind = None
-    if args.warmup > 0:
+    if args.full and args.warmup > 0:
         wprof, _ = ops.profile_stop()
         if wprof:
             dom_kind = max(wprof, key=lambda k: sum(r[1].elapsed_time(r[2]) for r in wprof[k]))
         del wprof
-    if args.bracket_all:
+    if args.full and args.bracket_all:
         ops.profile_start(everything=True)
-    else:
+    elif args.full:
         ops.profile_start(everything=False, only=None if (dom_kind is None or args.mfma_events_only) else {dom_kind})
     dev_allocs0 = int(torch.cuda.memory_stats(dev).get("num_device_alloc", 0))
     t0 = time.perf_counter()
@@ -399,9 +433,11 @@ def main(args):
     barrier()
     elapsed = time.perf_counter() - t0
     prof, prof_all = ops.profile_stop()
+    if args.dump_outputs and rank == 0:      # before any loop below trains the model further
+        dump_outputs(args.dump_outputs, onet, loss)
     # whole-step breakdown (every launch bracketed): its own short loop AFTER the timed region, same model, same batch
     prof_b, n_break, wall_b = prof, args.steps, elapsed / args.steps * 1e3
-    if not args.bracket_all:
+    if args.full and not args.bracket_all:
         n_break = 3
         ops.profile_start(everything=True)
         barrier()
@@ -414,7 +450,7 @@ def main(args):
     # the same loop with the fp32-MFMA kernels only (Winograd F(4x4) / direct), for the record next to
     # the headline, whose 3x3 convolutions run on the bf16 matrix pipe by operand splitting (same fp32 tensors and results)
     f32_mfma_only = None
-    if world == 1 and not bf16 and conv in ("auto", "split") and ops.SPLIT_AUTO and not args.torch_adam and not args.no_f32_mfma_only:
+    if args.full and world == 1 and not bf16 and conv in ("auto", "split") and ops.SPLIT_AUTO and not args.torch_adam and not args.no_f32_mfma_only:
         keep = onet.settings
         onet.settings = keep.replace(conv="auto", split=False)
         for _ in range(3):
@@ -453,7 +489,7 @@ def main(args):
         if "ONET_FORCE_LOCAL_RANK" not in os.environ and (dist.get_backend() != "nccl" or dist.get_world_size() != args.gpus):
             raise SystemExit("[bench] --gpus %d but the process group is %s with %d rank(s): not an RCCL run of the requested size"
                              % (args.gpus, dist.get_backend(), dist.get_world_size()))
-        if not args.torch_adam and not args.no_comm_curve:
+        if args.full and not args.torch_adam and not args.no_comm_curve:
             comm = comm_curve(onet, opt, X, train_step, barrier, dev, max(3, args.steps // 2), overlap, args.bucket_mb)
             comm["overlap_ms" if overlap else "no_overlap_ms"] = round(elapsed / args.steps * 1e3, 3)
             if "no_allreduce_ms" in comm:
@@ -461,7 +497,7 @@ def main(args):
     # the reference's own loop shape (TS:209-219), for the record next to the headline: the same steps with the batch copied from
     # pinned host memory every step (TS:211 X.to(device)) and loss.item() every step (TS:219)
     reference_loop = None
-    if world == 1 and not args.no_reference_loop:
+    if args.full and world == 1 and not args.no_reference_loop:
         Xh = X.cpu().pin_memory()
         for _ in range(2):
             float(train_step(onet, opt, Xh.to(dev, non_blocking=False)).item())
@@ -478,7 +514,8 @@ def main(args):
                                   % (Xh.numel() * 4 / 2 ** 20)}
         del Xh
 
-    if rank == 0:
+    roofline = None
+    if rank == 0 and args.full:
         # multiplies the algorithm issues relative to direct convolution: F(4x4,3x3) 36 per 16 outputs x 9 taps -> 1/4 (the
         # weight-gradient kernel F(3x3,4x4) likewise); the split kernels issue THREE 16-bit MFMAs per product term of the direct
         # algorithm: 1/3
@@ -598,6 +635,7 @@ def main(args):
                                          "the timed region (which brackets the dominant kernel only: bracketing everything costs the "
                                          "difference between wall_ms and timed_region_ms_per_step); " % n_break) +
                                         "unattributed = torch glue kernels, event overhead and launch gaps"}
+    if rank == 0:
         imgs = args.batch * world * args.steps
         if args.size == 256 and args.chans == 1:
             cfg_name = "configs[2]" if bf16 else ("configs[3]" if world > 1 and args.batch * world == 256 else "configs[1]")
@@ -623,7 +661,7 @@ def main(args):
                              "registers); every gradient element within 2e-4 of the "
                              "fp64 oracle under the run's own decisions incl. this B=32 dispatch (tests/test_gpu_gradients.py: 9.5e-5; the "
                              "fp32-MFMA-only dispatch: 4.6e-5 on the comparable case); Settings(split=False) keeps the fp32-MFMA Winograd kernels "
-                             "(timed in f32_mfma_only)") if (conv in ("auto", "split") and ops.split_enabled()) else "f32 throughout (fp32 MFMA)",
+                             "(timed in f32_mfma_only under --full)") if (conv in ("auto", "split") and ops.split_enabled()) else "f32 throughout (fp32 MFMA)",
                "data": "synthetic",
                "data_source": data_src,
                "config": {"workload": "%s: batch=%d/GPU %dx%dx%d synthetic K-clutter, %s, twin U-Net "
@@ -643,8 +681,9 @@ def main(args):
                "hbm_reserved_gb": round(torch.cuda.max_memory_reserved(dev) / 2 ** 30, 2),
                "alloc_retries": int(torch.cuda.memory_stats(dev).get("num_alloc_retries", 0)),
                "device_allocs_in_timed_steps": int(torch.cuda.memory_stats(dev).get("num_device_alloc", 0)) - dev_allocs0,
-               "device_allocs_per_timed_step": [b - a for a, b in zip([dev_allocs0] + allocs_per_step, allocs_per_step)],
-               "roofline": roofline}
+               "device_allocs_per_timed_step": [b - a for a, b in zip([dev_allocs0] + allocs_per_step, allocs_per_step)]}
+        if roofline is not None:
+            out["roofline"] = roofline
         if distributed:
             out["rccl_world"] = world if dist.get_backend() == "nccl" else 0
             out["dist_backend"] = dist.get_backend()
@@ -662,7 +701,7 @@ def main(args):
         if reference_loop is not None:
             out["reference_loop"] = reference_loop
         headline = world == 1 and not bf16 and args.size == 256 and args.chans == 1 and args.batch == 32 and not args.torch_adam
-        if headline and not args.no_secondary:
+        if args.full and headline and not args.no_secondary:
             # BASELINE configs[2] in the same driver-run line: release this process's HBM first (the child peaks at ~150 GB)
             X_cpu = X.cpu()
             del loss, opt, onet, X, prof, prof_all, prof_b
@@ -672,7 +711,7 @@ def main(args):
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
             out["secondary"] = {"configs[2]": secondary_config2()}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if X_cpu is None:
                 X_cpu = X.cpu()
             out["cpu_baseline"] = cpu_baseline(X_cpu, args.cpu_seconds)

@@ -38,7 +38,7 @@ def test_bench_two_ranks_sharing_one_gpu_over_gloo(shape):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     extra = ["--batch", "4", "--size", "64"] if shape == "c2_small" else ["--batch", "4", "--size", "512", "--chans", "3"]
-    out = _torchrun(os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    out = _torchrun(os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                     "--bucket-mb", "8", *extra)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -59,7 +59,7 @@ def test_bench_two_ranks_at_the_configs3_per_gpu_workload():
     loops ran and `allreduce_exposed_ms` is in the line."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    out = _torchrun(os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline")
+    out = _torchrun(os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline")
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -102,7 +102,7 @@ def test_bench_one_rank_over_rccl():
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "4", "--size", "64",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--bucket-mb", "8"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--bucket-mb", "8"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=540)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -155,7 +155,7 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(ONET_DIST_BACKEND="gloo", ONET_FORCE_LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--bucket-mb", "8", "--batch", "4", "--size", "64"], cwd=ROOT, env=env,
+                          "--full", "--no-cpu-baseline", "--bucket-mb", "8", "--batch", "4", "--size", "64"], cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=540)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -163,3 +163,28 @@ def test_bench_launches_its_own_ranks():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 8 and d["value"] > 0
     assert "secondary" not in d and "cpu_baseline" not in d          # N = 1 only
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_prints_the_headline_and_dumps_its_last_step(tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full): the headline fields and none of the --full measurements; --dump-outputs
+    writes float32 arrays of the last timed step, within 64 MB, whose loss is the one the line reports."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "4", "--size", "64",
+                          "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], cwd=ROOT,
+                         capture_output=True, text=True, timeout=540)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "images/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 3
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) <= 1e-2 * d["value"]
+    assert not {"roofline", "f32_mfma_only", "reference_loop", "secondary", "cpu_baseline", "comm"} & set(d)
+    arrays = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert {"loss", "params_sample", "grads_sample", "bn_running_stats"} <= set(arrays)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+    assert float(arrays["loss"][0]) == d["loss"]
+    assert np.abs(arrays["grads_sample"]).max() > 0

@@ -276,6 +276,38 @@ def test_bench_parent_is_gpu_free_before_the_launch_decision():
     assert not ({"torch", "onet_amd", "oracle"} & names), names
 
 
+def test_bench_bracket_options_need_full():
+    """--bracket-all / --mfma-events-only only shape the roofline, which a plain run does not measure: refused without --full."""
+    import subprocess
+    for opt in ("--bracket-all", "--mfma-events-only"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), opt], cwd=ROOT, capture_output=True, text=True,
+                             timeout=120)
+        assert out.returncode == 2 and "need --full" in out.stderr, (opt, out.stderr[-1000:])
+
+
+def test_bench_dump_outputs_format(tmp_path, monkeypatch):
+    """bench.dump_outputs on a CPU model: float32 arrays within 64 MB, and the parameter / gradient sample takes the same
+    positions in every run (two builds are compared output for output)."""
+    import bench
+    from onet_amd import Onet
+    monkeypatch.setattr(bench, "torch", torch)         # bench.main() imports torch into the module
+    m = Onet(in_chns=1, binit=True, bshare=True)
+    for i, p in enumerate(m.parameters()):
+        p.grad = torch.full_like(p, float(i))
+    bench.dump_outputs(str(tmp_path / "a"), m, torch.tensor(0.5))
+    bench.dump_outputs(str(tmp_path / "b"), m, torch.tensor(0.5))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["bn_running_stats.npy", "grads_sample.npy", "loss.npy", "params_sample.npy"]
+    arrays = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype == np.float32 for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+    assert arrays["params_sample.npy"].size == bench.DUMP_SAMPLE and float(arrays["loss.npy"][0]) == 0.5
+    for n in names:
+        assert np.array_equal(arrays[n], np.load(tmp_path / "b" / n)), n
+    flat_g = torch.cat([p.grad.reshape(-1) for p in m.parameters()]).numpy()
+    assert set(np.unique(arrays["grads_sample.npy"])) <= set(np.unique(flat_g))
+
+
 def test_zy3_dict_reader(tmp_path):
     """`io.load_zy3_dict` on a file with the schema the reference's ZY-3 loaders read (dataloader/zy3_cloud_thumbnailv5_20240304.py:
     92-122 `torch.load` of `{image_id: {'true_color': tensor [3,H,W], 'mask': tensor [H,W]}}`; the Dataset indexes

@@ -38,7 +38,7 @@ try:
 except Exception:
     pass
 with open(f"profiles/{tag}_kernel_stats_{sfx}.md", "w") as f:
-    f.write(f"# rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 3 --no-cpu-baseline {extra} ({desc})\n\n")
+    f.write(f"# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 3 --warmup 3 --no-cpu-baseline {extra} ({desc})\n\n")
     _w = re.findall(r"--warmup\s+(\d+)", "--warmup 3 " + extra)
     nwarm = int(_w[-1])
     nbk = 0 if "--bracket-all" in extra else 3
@@ -80,7 +80,7 @@ for fcsv in glob.glob(f"{src}/sq/**/*kernel_trace.csv", recursive=True):
     for r in csv.DictReader(open(fcsv)):
         dur[r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")[:60]].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
 with open(f"profiles/{tag}_sq_counters_{sfx}.md", "w") as f:
-    f.write(f"# rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA --kernel-trace -- python bench.py --steps 3 --warmup 3 {extra} ({desc})\n\n")
+    f.write(f"# rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA --kernel-trace -- python bench.py --full --steps 3 --warmup 3 {extra} ({desc})\n\n")
     f.write("effective clock = GRBM_GUI_ACTIVE / 8 / duration (MI355X_MICROARCH.md, DVFS give-back); MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE/8 x 1024 SIMDs).\n"
             "Profiled passes run slower than un-profiled ones (same guide), so durations here are longer than in the kernel-stats table.\n\n")
     f.write("Wave time split (fractions of SQ_WAVE_CYCLES): issuing = SQ_ACTIVE_INST_ANY, waiting to issue = SQ_WAIT_INST_ANY (matrix pipe busy, dependencies), "

@@ -1,9 +1,11 @@
 #!/bin/bash
-mkdir -p gpurun_out
-timeout -k 10 1100 python bench.py > gpurun_out/bench_c.json 2> gpurun_out/bench_c.err
-python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/bench_c.json").read().strip().splitlines()[-1])
+# the full benchmark line (bench.py --full) and a summary of its parts: tools/run_bench_summary.sh OUTDIR
+OUT=${1:?usage: tools/run_bench_summary.sh OUTDIR}
+mkdir -p "$OUT"
+timeout -k 10 1100 python bench.py --full > "$OUT/bench_c.json" 2> "$OUT/bench_c.err"
+python - "$OUT/bench_c.json" <<'PY'
+import json, sys
+d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print("headline", d["value"], d["ms_per_step"], "frac", d["roofline"]["frac"], "avg", d["roofline"]["avg_launch_ms"], "traffic", d["roofline"].get("traffic"))
 print("step", {k: v for k, v in d["roofline"]["step"].items() if k != "note"})
 print("f32", d.get("f32_mfma_only", {}).get("value")); print("ref", d.get("reference_loop", {}).get("ms_per_step"))
