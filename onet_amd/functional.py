@@ -21,12 +21,33 @@ def _carries_settings(cls):
         return fwd(ctx, *args, **kw)
 
     def backward(ctx, *grads):
+        if torch.is_grad_enabled():
+            # (autograd runs backward with grad mode on only under create_graph=True: the kernels' outputs carry no graph, a second
+            # derivative taken through them would silently be zero)
+            raise RuntimeError("onet_amd: double differentiation (create_graph=True) is not supported: the HIP backward kernels "
+                               "build no graph of their own")
         with ops.using(getattr(ctx, "_onet_settings", None)):
             return bwd(ctx, *grads)
 
     forward.__doc__, backward.__doc__ = fwd.__doc__, bwd.__doc__
     cls.forward, cls.backward = staticmethod(forward), staticmethod(backward)
     return cls
+
+
+def _record_versions(ctx, *params):
+    """Forward: the parameters backward reads (as ctx.params, outside autograd's saved tensors) and their version counters."""
+    ctx.params = params
+    ctx.param_versions = tuple(None if p is None else p._version for p in params)
+
+
+def _check_versions(ctx, checked):
+    """Backward: raise as autograd does for a saved tensor if a parameter that `checked` marks was modified in place since forward
+    (an optimizer step, `p.mul_()` under no_grad ...): the packs and coefficients made in forward no longer belong to it."""
+    for p, v0, c in zip(ctx.params, ctx.param_versions, checked):
+        if c and p is not None and p._version != v0:
+            raise RuntimeError("onet_amd: one of the variables needed for gradient computation has been modified by an inplace "
+                               f"operation: a parameter of shape {list(p.shape)} is at version {p._version}; expected version {v0} "
+                               "instead")
 
 
 @_carries_settings
@@ -118,11 +139,15 @@ class ConvBNReLUFn(torch.autograd.Function):
         if aux is not None:
             aux["a_amax"] = a_amax
         ctx.twin = ops.twin_src_of(x)       # a virtual twin batch (placeholder + (X, bias)): backward re-attaches the tag
-        ctx.save_for_backward(x, z, save_all, None if norm is None else norm[0], None if norm is None else norm[1])
+        # the unit below's (z, save) leave the dict here and become saved tensors of this node: every backward through the graph
+        # (retain_graph) finds them, and they are freed with the graph's other saved tensors -- the dict lives as long as the caller
+        # holds the loss tensor, i.e. into the next step, and must not keep a whole set of pre-activations alive
+        below = (link_in.pop("z"), link_in.pop("save")) if (training and link_in is not None and "z" in link_in) else (None, None)
+        ctx.save_for_backward(x, z, save_all, None if norm is None else norm[0], None if norm is None else norm[1], *below)
         ctx.training = training
         ctx.packed = packed
         ctx.wshape = tuple(weight.shape)
-        ctx.params = (weight, gamma, beta)          # for ops.grad_slot_if_free in backward
+        _record_versions(ctx, weight, gamma, beta)  # (also for ops.grad_slot_if_free in backward)
         ctx.link_out = ctx.link_in = None
         if training and link_out is not None:
             link_out.clear()
@@ -130,7 +155,7 @@ class ConvBNReLUFn(torch.autograd.Function):
             if defer:
                 link_out["deferred"] = True
             ctx.link_out = link_out
-        if training and link_in is not None and "z" in link_in:
+        if below[0] is not None:
             ctx.link_in = link_in
         if pooled is not None and link_out is not None:
             link_out["pooled"] = pooled
@@ -207,20 +232,25 @@ class ConvBNReLUFn(torch.autograd.Function):
             ops.bn_relu_apply(z, save_all, out=a, amax=a_amax, group_images=gi)
         p16["a"], p16["a_slots"], p16["a_amax"] = aP, act_slots, a_amax
         ctx.x_slots = x_slots
-        ctx.up_link = p16.get("up_link")    # (first convolution of a decoder block: see UpConvTCatFn -- the up-sampled half of dx leaves pre-split)
+        # (first convolution of a decoder block: see UpConvTCatFn -- the up-sampled half of dx leaves pre-split.  The request is kept on
+        # this node, not taken from the dict in backward: every backward through a retained graph makes the same hand-off)
+        ctx.up_link = p16.get("up_link")
+        ctx.up_want = None if ctx.up_link is None else ctx.up_link.get("want")
         ctx.twin = ops.twin_src_of(x)       # a virtual twin batch (placeholder + (X, bias)): backward re-attaches the tag
-        ctx.save_for_backward(x, z, save_all, xP)
+        # the unit below's (z, save): saved tensors of this node (see ConvBNReLUFn.forward)
+        below = (link_in.pop("z"), link_in.pop("save")) if (training and link_in is not None and "z" in link_in) else (None, None)
+        ctx.save_for_backward(x, z, save_all, xP, *below)
         ctx.pre = True
         ctx.training = training
         ctx.packed = packed
         ctx.wshape = tuple(weight.shape)
-        ctx.params = (weight, gamma, beta)
+        _record_versions(ctx, weight, gamma, beta)
         ctx.link_out = ctx.link_in = None
         if training and link_out is not None:
             link_out.clear()
             link_out.update(z=z, save=save_all)
             ctx.link_out = link_out
-        if training and link_in is not None and "z" in link_in:
+        if below[0] is not None:
             ctx.link_in = link_in
         if pooled is not None and link_out is not None:
             link_out["pooled"] = pooled
@@ -236,9 +266,10 @@ class ConvBNReLUFn(torch.autograd.Function):
 
     @staticmethod
     def _backward_pre(ctx, da):
-        x, z, save_all, xP = ctx.saved_tensors
+        x, z, save_all, xP, z_below, save_below = ctx.saved_tensors
         x = ConvBNReLUFn._retag_twin(ctx, x)
         need_x, need_w, need_g, need_b = ctx.needs_input_grad[:4]
+        _check_versions(ctx, (True, True, False))    # (as torch: conv2d saves the weight, batch_norm gamma, neither beta)
         pw, pg, pb = ctx.params
         aff = (ops.grad_slot_if_free(pg) if need_g else None, ops.grad_slot_if_free(pb) if need_b else None)
         rec4, da_amax = None, None
@@ -248,9 +279,6 @@ class ConvBNReLUFn(torch.autograd.Function):
             lk.pop("rec", None)
             if rda.data_ptr() != da.data_ptr() or rda.shape != da.shape or rda.stride() != da.stride():
                 rec4 = da_amax = None
-        z_below = save_below = None
-        if ctx.link_in is not None:                 # the unit below's (z, save) must not outlive this backward
-            z_below, save_below = ctx.link_in.pop("z", None), ctx.link_in.pop("save", None)
         nones = (None,) * 12
         if xP is None:
             # fp32 input (the stem): dz in fp32 for the fp32-input kernels; no input gradient path on pre-split operands
@@ -281,11 +309,11 @@ class ConvBNReLUFn(torch.autograd.Function):
                 if am_below is not None:
                     ctx.link_in["da_amax"] = am_below
         up = getattr(ctx, "up_link", None)
-        if need_x and dx is None and up is not None and up.get("want") and (dz_slots is not None or dzP.shape[3] == 1):
+        if need_x and dx is None and up is not None and ctx.up_want and (dz_slots is not None or dzP.shape[3] == 1):
             # the input of this convolution is a concat buffer whose up-sampled half came out of a ConvTranspose2d: that half of dx is
             # read only by the ConvTranspose2d backward GEMMs, and leaves this launch in THEIR operand form (fp16 hi | mid slots scaled by
             # a bound from dz's bound and the weights); the fp32 tensor keeps its shape, its upper channels are never written
-            C2, Ct = up["want"]
+            C2, Ct = ctx.up_want
             bound = ops.conv3x3_dgrad_bound(pw, dz_slots, C2) if dzP.shape[3] == 2 else None      # (plain bf16 parts are not scaled)
             dx, dyP = ops.conv3x3_split_dgrad_pre_slots(dzP, dpack, ctx.wshape[1], C2, bound, slots=dz_slots, always=dz_slots is not None)
             up["dyP"], up["dy_slots"], up["da"] = dyP, bound, dx
@@ -297,9 +325,10 @@ class ConvBNReLUFn(torch.autograd.Function):
     def backward(ctx, da):
         if ctx.pre:
             return ConvBNReLUFn._backward_pre(ctx, da)
-        x, z, save_all, nz, nsave = ctx.saved_tensors
+        x, z, save_all, nz, nsave, z_below, save_below = ctx.saved_tensors
         x = ConvBNReLUFn._retag_twin(ctx, x)
         need_x, need_w, need_g, need_b = ctx.needs_input_grad[:4]
+        _check_versions(ctx, (True, True, False))
         pw, pg, pb = ctx.params
         aff = (ops.grad_slot_if_free(pg) if need_g else None, ops.grad_slot_if_free(pb) if need_b else None)
         G = save_all.shape[0]
@@ -340,18 +369,13 @@ class ConvBNReLUFn(torch.autograd.Function):
         if need_x:
             lk = ctx.link_in
             fused = None
-            if lk is not None and "z" in lk:
-                # (z, save) leave the dict here: the graph -- and with it this ctx and the dict -- lives as long as the
-                # caller holds the loss tensor, i.e. into the next step; a whole set of pre-activations must not
-                fused = ops.conv3x3_dgrad_bnreduce(dz, ctx.packed, lk.pop("z"), lk.pop("save"))
+            if lk is not None and z_below is not None:
+                fused = ops.conv3x3_dgrad_bnreduce(dz, ctx.packed, z_below, save_below)
             if fused is not None:
                 dx, r = fused
                 lk["da"], lk["rec"] = dx, r
             else:
                 dx = ops.conv3x3_auto(dz, ctx.packed, 1, amax=dz_amax)
-        if ctx.link_in is not None:                 # whatever path ran: the unit below's (z, save) must not outlive this backward
-            ctx.link_in.pop("z", None)
-            ctx.link_in.pop("save", None)
         return (dx, dw, (dgamma if need_g else None), (dbeta if need_b else None)) + (None,) * 12
 
 
@@ -366,11 +390,13 @@ class Conv3x3Fn(torch.autograd.Function):
         ctx.save_for_backward(x)
         ctx.packed = packed
         ctx.wshape = tuple(weight.shape)
+        _record_versions(ctx, weight)
         return z
 
     @staticmethod
     def backward(ctx, dz):
         (x,) = ctx.saved_tensors
+        _check_versions(ctx, (True,))
         dw = ops.conv3x3_wgrad_auto(x, dz, ctx.wshape) if ctx.needs_input_grad[1] else None
         dx = ops.conv3x3_auto(dz, ctx.packed, 1) if ctx.needs_input_grad[0] else None
         return dx, dw, None
@@ -441,20 +467,22 @@ class SkipPoolFn(torch.autograd.Function):
             y = pooled[0]                   # the producing BatchNorm + ReLU pass already wrote the pooled tensor (onet_bn_relu_apply_pool)
         else:
             y = ops.maxpool2_fwd(x)
-        ctx.save_for_backward(x)
-        ctx.link = link if (link is not None and "z" in link) else None
+        # the producing unit's (z, save): saved tensors of this node (see ConvBNReLUFn.forward)
+        below = (link.pop("z"), link.pop("save")) if (link is not None and "z" in link) else (None, None)
+        ctx.save_for_backward(x, *below)
+        ctx.link = link if below[0] is not None else None
         return (x.view_as(x), y, x.view_as(x)) if returned else (x.view_as(x), y)
 
     @staticmethod
     def backward(ctx, g_skip, g_pool, g_ret=None):
-        (x,) = ctx.saved_tensors
+        x, z, save = ctx.saved_tensors
         if g_pool is None:
             gs = [g for g in (g_skip, g_ret) if g is not None]
             return (sum(gs[1:], gs[0]) if gs else None), None, None, None
         lk = ctx.link
-        if lk is not None and "z" in lk:
+        if lk is not None:
             am = ops.new_amax(g_pool.device) if (getattr(ctx, "pre", False) and ops.p16_parts() == 2) else None
-            dx, part2 = ops.maxpool2_bwd(x, g_pool, add=g_skip, add2=g_ret, bn=(lk.pop("z"), lk.pop("save")), dx_amax=am)
+            dx, part2 = ops.maxpool2_bwd(x, g_pool, add=g_skip, add2=g_ret, bn=(z, save), dx_amax=am)
             if part2 is not None:
                 lk["da"], lk["rec4"] = dx, part2
                 if am is not None:
@@ -510,7 +538,7 @@ class UpConvTCatFn(torch.autograd.Function):
             ctx.save_for_backward(x1)
             ctx.wp_dgrad = wp_dgrad
             ctx.meta = (C2, Ct, h, w, pt, pl, tuple(weight.shape), bias is not None)
-            ctx.params = (weight, bias)
+            _record_versions(ctx, weight, bias)
             # round 5: the backward GEMMs on slot operands too -- the consumer of the concat buffer (the decoder block's first convolution)
             # is told, through the shared dict, to hand the up-sampled half of its input gradient over pre-split
             lk = p16.get("up_link")
@@ -535,7 +563,7 @@ class UpConvTCatFn(torch.autograd.Function):
         ctx.save_for_backward(x1)
         ctx.wp_dgrad = wp_dgrad
         ctx.meta = (C2, Ct, h, w, pt, pl, tuple(weight.shape), bias is not None)
-        ctx.params = (weight, bias)
+        _record_versions(ctx, weight, bias)
         return cat
 
     @staticmethod
@@ -543,12 +571,14 @@ class UpConvTCatFn(torch.autograd.Function):
         (x1,) = ctx.saved_tensors
         C2, Ct, h, w, pt, pl, wshape, has_bias = ctx.meta
         need_x1, need_x2, need_w, need_b = ctx.needs_input_grad[:4]
+        # (as torch: conv_transpose2d saves the weight, not the bias.  The input-gradient packs are made here from the live weight)
+        _check_versions(ctx, (True, False))
         dx2 = dcat[:, :C2] if need_x2 else None
         dx1 = dw = db = None
         lk = getattr(ctx, "up_link", None)
         if lk is not None:
+            # (the per-backward payload only: the request itself, lk["want"], stays for a further backward through a retained graph)
             dyP, dy_slots, rda = lk.pop("dyP", None), lk.pop("dy_slots", None), lk.pop("da", None)
-            lk.pop("want", None)
             if dyP is not None and rda is not None and rda.data_ptr() == dcat.data_ptr() and rda.shape == dcat.shape:
                 # the up-sampled half of dcat exists only pre-split (written by the 3x3 input gradient that produced dcat)
                 x1P, x1_slots, packed = ctx.slot_ops
@@ -563,7 +593,7 @@ class UpConvTCatFn(torch.autograd.Function):
                 return dx1, dx2, (got[0] if need_w else None), (got[1] if want_db else None), None, None, None
             if ops.is_placeholder(x1):
                 raise RuntimeError("onet_amd: ConvTranspose2d backward: the input exists only pre-split and the pre-split gradient did not arrive")
-        wp_dgrad = ops.pack_of(ctx.wp_dgrad) if need_x1 else None     # (the weight is what it was in forward: no optimizer step in between)
+        wp_dgrad = ops.pack_of(ctx.wp_dgrad) if need_x1 else None     # (the weight is what it was in forward: checked above)
         if (need_x1 or need_w or need_b) and ops.convT2x2_bwd_fusable(Ct):
             # the GEMM kernels gather dy from the concat gradient themselves: no space-to-depth tensor
             dup = dcat[:, C2:]
@@ -633,12 +663,12 @@ class TwinInputFn(torch.autograd.Function):
     """[X ; clip(1 - X + bias, 0, 1)] as one batch of 2B (OV:180 for the second half)."""
 
     @staticmethod
-    def forward(ctx, x, bias):
+    def forward(ctx, x, bias, virtual=True):
         ops.require_gpu(x)
         x = x.contiguous()
         ctx.save_for_backward(x)
         ctx.bias = bias
-        if ops.TWIN_VIRTUAL:
+        if ops.TWIN_VIRTUAL and virtual:
             # K7 as SURVEY 2 states it: the complement half is formed by the stem kernels while they load X; the 2B-image tensor
             # exists only if some other reader asks for it (ops.plane materialises it once)
             return ops.twin_virtual(x, bias)
@@ -650,7 +680,7 @@ class TwinInputFn(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         B = x.shape[0]
         y = ops.complement_clip(x, ctx.bias)
-        return g[:B] - g[B:] * ((y > 0) & (y < 1)).to(g.dtype), None
+        return g[:B] - g[B:] * ((y > 0) & (y < 1)).to(g.dtype), None, None
 
 
 @_carries_settings

@@ -50,6 +50,17 @@ def invalidate_packed(model: nn.Module):
             m.invalidate_packed()
 
 
+def _hooked(module: nn.Module) -> bool:
+    """Can a forward hook or forward pre-hook -- registered on `module`, on any module inside it, or globally -- see or replace a
+    tensor that one block hands to the next?  Such a network takes the plain fp32 hand-offs (UNet._forward, Onet._forward): no
+    placeholder reaches a hook, and no pre-split form, pooled tensor or pre-activation travels beside a block's return value, so
+    what a hook returns is what the next block reads.  (A walk over the module tree: no launch, nothing changes without hooks.)"""
+    g = torch.nn.modules.module
+    if g._global_forward_hooks or g._global_forward_pre_hooks:
+        return True
+    return any(m._forward_hooks or m._forward_pre_hooks for m in module.modules())
+
+
 class Conv3x3(nn.Conv2d, _Packable):
     """nn.Conv2d(cin, cout, kernel_size=3, padding=1, bias=False) parameter holder (OV:47,51)."""
 
@@ -303,10 +314,12 @@ class UNet(nn.Module):
         """head_link (Onet.forward, twin batch): a dict through which the LAST unit hands its pre-activation and coefficients to the head
         instead of writing its activation (the second returned tensor is then a placeholder: Onet's head is its only reader)."""
         # the 18 num_batches_tracked counters of a pass take their increments in one multi-tensor launch when the pass is through
+        plain = _hooked(self)
         with ops.counting_batches():
-            return self._forward(x, groups, head_link)
+            return self._forward(x, groups, None if plain else head_link, plain)
 
-    def _forward(self, x, groups=1, head_link=None):
+    def _forward(self, x, groups=1, head_link=None, plain=False):
+        """plain: a hook watches a block (_hooked): every block returns a real fp32 tensor and its consumers read only that."""
         # ConvTranspose path: the four skip tensors are produced directly inside the first half of their concat
         # buffers (allocated here, before the encoder runs), the decoder fills the second half
         cats = [None] * 4
@@ -323,7 +336,7 @@ class UNet(nn.Module):
         # exists ONLY pre-split: the encoder's BatchNorm pass writes the skip groups, the Up block the up-sampled ones
         catsP = [None] * 4
         pool_p = [False] * 4                                # the pooled tensor of encoder level k feeds a pre-split convolution
-        if not self.bilinear and x.dim() == 4 and x.is_cuda and ops.presplit() and self.training:
+        if not self.bilinear and x.dim() == 4 and x.is_cuda and ops.presplit() and self.training and not plain:
             B, h, w = x.shape[0], x.shape[2], x.shape[3]
             for k, enc in enumerate((self.inc, self.down1.maxpool_conv[1], self.down2.maxpool_conv[1], self.down3.maxpool_conv[1])):
                 C = enc.double_conv[3].out_channels
@@ -379,12 +392,12 @@ class UNet(nn.Module):
             return (t, None, t) if returned else (t, None)
 
         # pl[i]: the producing block's second unit -> the SkipPoolFn of its output (BatchNorm-backward reduce records)
-        pl = [{} for _ in range(4)]
+        pl = [None] * 4 if plain else [{} for _ in range(4)]
         c0 = self.inc.double_conv[3].out_channels
         c1 = self.down1.maxpool_conv[1].double_conv[3].out_channels
         c2 = self.down2.maxpool_conv[1].double_conv[3].out_channels
         c3 = self.down3.maxpool_conv[1].double_conv[3].out_channels
-        if x.dim() == 4 and x.is_cuda and _SKIPPOOL and ops.FUSE_POOL:
+        if x.dim() == 4 and x.is_cuda and _SKIPPOOL and ops.FUSE_POOL and not plain:
             # the four encoder outputs are max-pooled next: their BatchNorm + ReLU pass writes the pooled tensor too
             for i in range(4):
                 pl[i]["want_pool"] = {"p16": pool_p[i]}
@@ -447,7 +460,8 @@ class Onet(nn.Module):
             # weights packed / weight gradients reduced once); BatchNorm treats the halves as two batches, in the
             # reference's order (X first).  Results: identical activations, weight gradients summed in one
             # split-K reduction instead of two plus autograd's add.
-            XX = Fn.TwinInputFn.apply(X, float(self.bias))
+            # (a hooked U-Net gets the twin batch as a real tensor: a pre-hook of its first block would otherwise see a placeholder)
+            XX = Fn.TwinInputFn.apply(X, float(self.bias), not _hooked(self.topu))
             hl = {} if (ops.HEAD_NORM and self.training) else None     # (the last activation is formed by the head from z: no tensor)
             L, H = self.topu(XX, groups=2, head_link=hl)
             Vt, Vd, S, sLt, sLd = Fn.HeadSoftmaxTwinFn.apply(L, H, hl)

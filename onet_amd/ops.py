@@ -536,12 +536,21 @@ class PackedT:
     packs of the slot-operand forward, built on first use per number of parts."""
 
     def __init__(self, w):
-        self.w = w.detach()
+        self.w = w.detach()             # (aliases the live parameter, version counter included)
+        self._v = self.w._version
         self._t = [None, None]          # built on first use: a step on the slot-operand forward never asks for the fused fp32 pack
         self._s = {}
 
+    def _same_weight(self):
+        """A pack made lazily -- at backward time, for the input gradient -- must be of the weight the forward used."""
+        if self.w._version != self._v:
+            raise RuntimeError("onet_amd: one of the variables needed for gradient computation has been modified by an inplace operation: "
+                               f"a ConvTranspose2d weight of shape {list(self.w.shape)} is at version {self.w._version}; expected version "
+                               f"{self._v} instead")
+
     def __getitem__(self, i):
         if self._t[i] is None:
+            self._same_weight()
             self._t[i] = packT2x2_fused(self.w) if i == 0 else packT2x2(self.w)[1]
         return self._t[i]
 
@@ -553,6 +562,7 @@ class PackedT:
 
     def slots(self, parts):
         if parts not in self._s:       # (the backward GEMMs' pack comes out of the same launch -- a training step wants both)
+            self._same_weight()
             self._s[parts] = packT2x2_slots(self.w, parts, dgrad=bool(CONVT_BWD_SLOTS))
         v = self._s[parts]
         return v[0] if isinstance(v, tuple) else v
@@ -560,6 +570,7 @@ class PackedT:
     def dgrad_slots(self, parts):
         v = self._s.get(parts)
         if not isinstance(v, tuple):
+            self._same_weight()
             self._s[parts] = v = packT2x2_slots(self.w, parts, dgrad=True)
         return v[1]
 
@@ -1453,13 +1464,24 @@ def conv3x3_split_wgrad(x, dz, dw_shape, out=None, norm=None, dz_amax=None, x_am
     return dw
 
 
+def _engine_accumulates(param):
+    """Will the running backward accumulate into param.grad?  Not under torch.autograd.grad (the gradient is returned to the caller,
+    who must not get a view of the flat buffer that the next zero_grad clears) nor under backward(inputs=...) without param."""
+    # (its AccumulateGrad node, looked up per call -- a few microseconds, once per parameter and zero_grad: kept on the parameter it
+    # would form a reference cycle through the node's own reference to the parameter)
+    try:
+        return bool(torch._C._will_engine_execute_node(torch.autograd.graph.get_gradient_edge(param).node))
+    except RuntimeError:            # "... a leaf node was passed ... while running autograd.grad()"
+        return False
+
+
 def grad_slot_if_free(param):
     """FlatAdam registers, per parameter, its slice of the flat gradient buffer.  When the parameter has no .grad yet
     (FlatAdam.zero_grad sets it to None) a backward kernel may write its result straight into that slice and hand the
     view to autograd, which then adopts it as .grad without an accumulation kernel (62 + 72 tiny adds per step
     otherwise).  -> a fresh contiguous view, or None (no slot, or a gradient is already there: regular path)."""
     slot = getattr(param, "_onet_gslot", None)
-    if slot is None or param.grad is not None or getattr(param, "_onet_gslot_taken", False):
+    if slot is None or param.grad is not None or getattr(param, "_onet_gslot_taken", False) or not _engine_accumulates(param):
         return None
     # one taker per zero_grad: with shared weights used twice in a graph (two-pass mode) autograd sums the two
     # contributions in its input buffer BEFORE .grad is set, so ".grad is None" alone would hand the slice out twice

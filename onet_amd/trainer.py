@@ -260,6 +260,9 @@ class FlatAdam:
         for a, b, n in segs:
             ops.adam_step(self.flat[a:b], self.gflat[a:b], self.m[a:b], self.v[a:b], g["lr"], g["betas"][0], g["betas"][1],
                           g["eps"], g["weight_decay"], n, grad_scale=1.0 / self.world_size)
+        # the kernel rewrote the parameters through a pointer: bump their version counters as an in-place torch op would, so that a
+        # graph recorded before the step refuses its backward (functional._check_versions) instead of mixing old and new weights
+        torch.autograd.graph.increment_version([p for p in self.params if p.grad is not None])
         invalidate_packed(self.model)
 
     def broadcast_params(self, src=0):
@@ -267,6 +270,7 @@ class FlatAdam:
             dist.broadcast(self.flat, src=src, group=self.pg)
             for b in self.model.buffers():
                 dist.broadcast(b, src=src, group=self.pg)
+            torch.autograd.graph.increment_version(self.params)      # (written through the flat buffer: see step)
             invalidate_packed(self.model)
 
 
