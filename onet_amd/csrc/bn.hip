@@ -7,10 +7,6 @@
 
 using namespace onet;
 
-#ifndef ONET_BN_BATCH
-#define ONET_BN_BATCH 1
-#endif
-
 // Partial over one image plane chunk: part[p][c][3] = (n_k, mean_k, M2_k), M2_k = sum (z - mean_k)^2.
 // ONE pass in fp64 over sums shifted by a pivot (the chunk's first element, within a few standard deviations of
 // its mean): s1 = sum (z - pivot), s2 = sum (z - pivot)^2, mean = pivot + s1/n, M2 = s2 - s1^2/n.  With the shift
@@ -33,7 +29,6 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __re
     double v[2] = {0.0, 0.0};
     if (vec) {
         int i = beg + threadIdx.x * 4;
-#if ONET_BN_BATCH
         for (; i + 3072 < end; i += 4096) {       // four 16-byte loads in flight per thread; same summation order as below
             float4 q[4];
 #pragma unroll
@@ -45,7 +40,6 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __re
                 v[1] += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
             }
         }
-#endif
         for (; i < end; i += 1024) {
             const float4 q = *reinterpret_cast<const float4*>(src + i);
             const double d0 = q.x - pivot, d1 = q.y - pivot, d2 = q.z - pivot, d3 = q.w - pivot;
@@ -245,7 +239,6 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const ZT* __restrict
     float* dst = a + (int64_t)b * a_bs + (int64_t)c * HW;
     const int beg = ch * 4096, end = min(beg + 4096, HW);
     if (((HW & 3) == 0) && ((z_bs & 3) == 0) && ((a_bs & 3) == 0)) {
-#if ONET_BN_BATCH
         if (end - beg == 4096) {          // full chunk: all four 16-byte loads of the thread in flight before the first use
             const int i0 = beg + threadIdx.x * 4;
             float4 q[4];
@@ -263,7 +256,6 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const ZT* __restrict
             amax_commit(vmax, amax);
             return;
         }
-#endif
         for (int i = beg + threadIdx.x * 4; i < end; i += 1024) {
             float4 q = bn_ldz4<ZT>(src + i);
             q.x = fmaxf(fmaf(q.x - mean, sc, sh), 0.f);
@@ -371,9 +363,6 @@ __device__ __forceinline__ bn_u32x4* bn_tr_lds() {
     return reinterpret_cast<bn_u32x4*>(bn_dyn_lds);
 }
 static inline unsigned bn_tr_bytes(int nparts) { return (unsigned)(nparts == 1 ? BN_TR_SLOTS / 2 : BN_TR_SLOTS) * 16u; }
-#ifndef BN_APPLY_SPLIT_TR
-#define BN_APPLY_SPLIT_TR 1
-#endif
 // addr(px) -> global slot index of the hi part of the block's pixel px (0 .. 1023; < 0: outside), mid_off = slots from hi to mid
 template <typename AddrFn>
 __device__ __forceinline__ void bn_store_slots_block_fn(bn_u32x4* lds, unsigned* __restrict__ xs, int mid_off, const float (&v)[4][8], float s,
@@ -448,11 +437,10 @@ __device__ __forceinline__ void bn_store_slots_block(bn_u32x4* lds, unsigned* __
     }
 }
 
-// a = relu(bn(z)) -> xs (pre-split) and, where `a` is given, the fp32 tensor too.  A thread owns 8 channels of four pixels 64 apart
-// (a wave covers 256 consecutive pixels, four times 64): every load is a coalesced 256-byte row piece of one channel plane and
-// every 16-byte slot store lands next to its neighbour lanes' (1 KB contiguous per store instruction).  Measured against the
-// variant with four CONSECUTIVE pixels per thread (float4 loads, slot stores 64 bytes apart between lanes): 0.085 vs 0.108 ms per
-// launch -- the strided 16-byte stores cost more than the narrower loads.
+// a = relu(bn(z)) -> xs (pre-split) and, where `a` is given, the fp32 tensor too.  A thread owns 8 channels of four CONSECUTIVE
+// pixels (float4 loads); the block's slots are traded through LDS (bn_store_slots_block) so that every 16-byte slot store lands
+// next to its neighbour lanes'.  Without the trade the slot stores of consecutive pixels go out 64 bytes apart between lanes and
+// cost more than the narrower loads of four pixels 64 apart per thread do (0.108 vs 0.085 ms per launch).
 template <typename ZT = float>
 __global__ __launch_bounds__(256) void bn_relu_apply_split_kernel(const ZT* __restrict__ z, int64_t z_bs, unsigned* __restrict__ xs,
                                                                   int64_t xs_bs, float* __restrict__ a, int64_t a_bs,
@@ -465,62 +453,27 @@ __global__ __launch_bounds__(256) void bn_relu_apply_split_kernel(const ZT* __re
     const int plane = blockIdx.x / bpp, blk = blockIdx.x % bpp;
     const int C8 = C >> 3, b = plane / C8, c8 = plane % C8;
     if (gimg) save += (int64_t)(b / gimg) * 4 * C;        // statistics groups = consecutive batch slices of gimg images, save [G][4][C]
-#if BN_APPLY_SPLIT_TR
-    {   // variant: four CONSECUTIVE pixels per thread (float4 loads) and the block's slots traded through LDS for coalesced stores
-        bn_u32x4* const tr = bn_tr_lds();            // 40 KB (np = 2) / 20 KB (np = 1: one part) of dynamic LDS
-        const int HW = H * W, p = (blk * 256 + threadIdx.x) * 4;
-        const bool live = p < HW;
-        const ZT* src = z + (int64_t)b * z_bs + (int64_t)c8 * 8 * HW + p;
-        float v[4][8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int c = c8 * 8 + k;
-            const float mean = save[c], sc = save[2 * C + c], sh = save[3 * C + c];
-            const float4 q = live ? bn_ldz4<ZT>(src + (int64_t)k * HW) : make_float4(0.f, 0.f, 0.f, 0.f);
-            v[0][k] = fmaxf(fmaf(q.x - mean, sc, sh), 0.f);
-            v[1][k] = fmaxf(fmaf(q.y - mean, sc, sh), 0.f);
-            v[2][k] = fmaxf(fmaf(q.z - mean, sc, sh), 0.f);
-            v[3][k] = fmaxf(fmaf(q.w - mean, sc, sh), 0.f);
-        }
-        if (a && live) {
-            float* d = a + (int64_t)b * a_bs + (int64_t)c8 * 8 * HW + p;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) *reinterpret_cast<float4*>(d + (int64_t)k * HW) = make_float4(v[0][k], v[1][k], v[2][k], v[3][k]);
-        }
-        bn_store_slots_block(tr, xs + (int64_t)b * xs_bs, c8, H, W, blk * 1024, HW, v, s_act, np);
-        return;
-    }
-#endif
-    const int HW = H * W, lane = threadIdx.x & 63, p0 = blk * 1024 + (threadIdx.x >> 6) * 256 + lane;
-    const ZT* src = z + (int64_t)b * z_bs + (int64_t)c8 * 8 * HW;
+    bn_u32x4* const tr = bn_tr_lds();            // 40 KB (np = 2) / 20 KB (np = 1: one part) of dynamic LDS
+    const int HW = H * W, p = (blk * 256 + threadIdx.x) * 4;
+    const bool live = p < HW;
+    const ZT* src = z + (int64_t)b * z_bs + (int64_t)c8 * 8 * HW + p;
     float v[4][8];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int p = p0 + 64 * j;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[j][k] = p < HW ? bn_ldz<ZT>(src + (int64_t)k * HW + p) : 0.f;
-    }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const int c = c8 * 8 + k;
         const float mean = save[c], sc = save[2 * C + c], sh = save[3 * C + c];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j][k] = fmaxf(fmaf(v[j][k] - mean, sc, sh), 0.f);
+        const float4 q = live ? bn_ldz4<ZT>(src + (int64_t)k * HW) : make_float4(0.f, 0.f, 0.f, 0.f);
+        v[0][k] = fmaxf(fmaf(q.x - mean, sc, sh), 0.f);
+        v[1][k] = fmaxf(fmaf(q.y - mean, sc, sh), 0.f);
+        v[2][k] = fmaxf(fmaf(q.z - mean, sc, sh), 0.f);
+        v[3][k] = fmaxf(fmaf(q.w - mean, sc, sh), 0.f);
     }
-    unsigned* o = xs + (int64_t)b * xs_bs;
-    float* d = a ? a + (int64_t)b * a_bs + (int64_t)c8 * 8 * HW : nullptr;
+    if (a && live) {
+        float* d = a + (int64_t)b * a_bs + (int64_t)c8 * 8 * HW + p;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int p = p0 + 64 * j;
-        if (p >= HW) continue;
-        int y, x;
-        bn_pixel_of(p, W, y, x);
-        if (d) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) d[(int64_t)k * HW + p] = v[j][k];
-        }
-        bn_store_slots(o, ((int64_t)(c8 * H + y) * np) * W + x, W, v[j], s_act, np);
+        for (int k = 0; k < 8; ++k) *reinterpret_cast<float4*>(d + (int64_t)k * HW) = make_float4(v[0][k], v[1][k], v[2][k], v[3][k]);
     }
+    bn_store_slots_block(tr, xs + (int64_t)b * xs_bs, c8, H, W, blk * 1024, HW, v, s_act, np);
 }
 
 // ... of an encoder output that is max-pooled next: a thread owns 8 channels of a 2 x 4 pixel patch (W % 4 == 0), writes the activation
@@ -606,9 +559,8 @@ __global__ __launch_bounds__(256) void bn_relu_apply_pool_split_kernel(const ZT*
 // dz of the BatchNorm + ReLU backward (bn_relu_bwd_apply_kernel's arithmetic: fp64 per element, rounded once) pre-split: fp16 parts
 // of 2^k dz with k = amax_scale(bound) from the magnitude slots (`slots`: an upper bound of |dz| written by bn_bwd_bound_kernel
 // BEFORE this pass; the consumers read the same slots and undo 2^k on their accumulators).  8 channels x 4 pixels per thread.
-#ifndef BN_BWD_OCC16
-#define BN_BWD_OCC16 4
-#endif
+// blocks per CU with a bf16 `z`: kept packed in registers until use, it fits a fourth block (126 VGPRs); the fp32 form spills at four
+constexpr int BN_BWD_OCC16 = 4;
 template <typename ZT = float>
 __global__ __launch_bounds__(256, sizeof(ZT) == 2 ? BN_BWD_OCC16 : 3) void bn_relu_bwd_apply_split_kernel(const float* __restrict__ da, int64_t da_bs, const ZT* __restrict__ z,
                                                                       int64_t z_bs, const float* __restrict__ save, const float* __restrict__ coef,
@@ -703,7 +655,6 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(const float* __
     double v[2] = {0.0, 0.0};
     if (((HW & 3) == 0) && ((z_bs & 3) == 0) && ((da_bs & 3) == 0) && ((chunk_len & 3) == 0)) {
         int i = beg + threadIdx.x * 4;
-#if ONET_BN_BATCH
         for (; i + 3072 < end; i += 4096) {       // eight 16-byte loads in flight per thread; same summation order as below
             float4 q[4], g[4];
 #pragma unroll
@@ -723,7 +674,6 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(const float* __
                 }
             }
         }
-#endif
         for (; i < end; i += 1024) {
             const float4 q = bn_ldz4<ZT>(zs + i);
             const float4 g = *reinterpret_cast<const float4*>(ds + i);
@@ -878,7 +828,6 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const float* __r
     float* out = dz + (int64_t)b * dz_bs + (int64_t)c * HW;
     const int beg = ch * 4096, end = min(beg + 4096, HW);
     if (((HW & 3) == 0) && ((z_bs & 3) == 0) && ((da_bs & 3) == 0) && ((dz_bs & 3) == 0)) {
-#if ONET_BN_BATCH
         if (end - beg == 4096) {          // full chunk: the thread's eight 16-byte loads in flight before the first use
             const int i0 = beg + threadIdx.x * 4;
             float4 q[4], g[4];
@@ -902,7 +851,6 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const float* __r
             amax_commit(vmax, amax);
             return;
         }
-#endif
         for (int i = beg + threadIdx.x * 4; i < end; i += 1024) {
             const float4 q = *reinterpret_cast<const float4*>(zs + i);
             const float4 g = *reinterpret_cast<const float4*>(ds + i);

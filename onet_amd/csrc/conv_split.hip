@@ -660,19 +660,13 @@ struct SpPreArgs {
     const unsigned* zP_slots = nullptr;
 };
 
-#ifndef SP_PRE_LAST_TAP
-#define SP_PRE_LAST_TAP 4   // the next chunk's DMA pieces go out during taps 0 .. SP_PRE_LAST_TAP
-#endif
 // PM: 0 = bf16 (hi | mid) parts, 1 = fp16 (hi | mid) parts -- three MFMAs per term on 16-channel chunks; 2 = PLAIN bf16 operands
 // (BASELINE configs[2]'s bf16 MFMA conv path: xs [B][C/8][H][W][8] bf16, one part): the same LDS image and DMA schedule with the
 // "part" index standing for the second 16 channels of a 32-channel chunk, two MFMAs per term (one per 16 channels).
 // W16: maps 16 pixels wide (the U-Net's 16-pixel level): a tile's 32 pixel columns are TWO IMAGES side by side, each with its own halo
 // columns in the LDS image (18 + 18 columns), so a horizontal tap never reads the neighbour image; a.B counts image PAIRS.
-#ifndef SP_PRE_NW
-#define SP_PRE_NW 8      // waves per block (8: two rows per wave; 4 (timing experiment): four rows per wave, one wave per SIMD)
-#endif
 template <bool W16> struct SpPreCfg {
-    static constexpr int NW = SP_PRE_NW, NT = 16 / NW, TW = 32, CO_T = 64, ROWS = NW * NT;
+    static constexpr int NW = 8, NT = 16 / NW, TW = 32, CO_T = 64, ROWS = NW * NT;     // NW waves per block: two rows per wave
     static constexpr int IN_ROWS = ROWS + 2, IN_COLS = W16 ? 36 : 34;
     static constexpr int NPIX = IN_ROWS * IN_COLS;                      // 612 / 648 halo pixels
     static constexpr int NPIXP = W16 ? 656 : 640;                       // pixel slots per half (4 NPIXP = whole 64-slot DMA pieces)
@@ -681,9 +675,10 @@ template <bool W16> struct SpPreCfg {
     static constexpr int BUF_SLOTS = W_SLOTS + 2 * IN_PART;             // 76 / 77 KB
     static constexpr int LDS_BYTES = 2 * BUF_SLOTS * 16;
     static constexpr int NB = (NT - 1) + 3;
+    static constexpr int LAST_TAP = 4;                                  // the next chunk's DMA pieces go out during taps 0 .. LAST_TAP
 };
 template <bool ST, int PM, bool W16>
-__global__ __launch_bounds__(SP_PRE_NW * 64, SP_PRE_NW / 4) void conv3x3_split_pre_kernel(SpPreArgs a) {
+__global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void conv3x3_split_pre_kernel(SpPreArgs a) {
     constexpr bool F16 = PM == 1;
     using C = SpPreCfg<W16>;
     constexpr int NT = C::NT, IN_COLS = C::IN_COLS, NWI = C::NWI, CO_T = C::CO_T, NPIXP = C::NPIXP, NB = C::NB;
@@ -852,11 +847,11 @@ __global__ __launch_bounds__(SP_PRE_NW * 64, SP_PRE_NW / 4) void conv3x3_split_p
                 // or two per tap during the first taps, so that they have the rest of the chunk's MFMAs to land
                 if (idx == 0) advance();
                 {
-                    constexpr int NPIECE = NII + NWI, PER = (NPIECE + SP_PRE_LAST_TAP) / (SP_PRE_LAST_TAP + 1);
+                    constexpr int NPIECE = NII + NWI, PER = (NPIECE + C::LAST_TAP) / (C::LAST_TAP + 1);
 #pragma unroll
                     for (int q = 0; q < PER; ++q) {
                         const int pc = idx * PER + q;
-                        if (idx <= SP_PRE_LAST_TAP && pc < NPIECE) {
+                        if (idx <= C::LAST_TAP && pc < NPIECE) {
                             if (pc & 1) { if (pc / 2 < NWI) dma_w(buf ^ 1, pc / 2); else dma_in(buf ^ 1, pc - NWI); }
                             else { if (pc / 2 < NII) dma_in(buf ^ 1, pc / 2); else dma_w(buf ^ 1, pc - NII); }
                         }
@@ -875,37 +870,6 @@ __global__ __launch_bounds__(SP_PRE_NW * 64, SP_PRE_NW / 4) void conv3x3_split_p
                         } else if constexpr (F16) {
                             const f16x8 ah = __builtin_bit_cast(f16x8, Aq[idx & 1][m][0]), am = __builtin_bit_cast(f16x8, Aq[idx & 1][m][1]);
                             const f16x8 bh = __builtin_bit_cast(f16x8, Bq[kx & 1][n + ky][0]), bm = __builtin_bit_cast(f16x8, Bq[kx & 1][n + ky][1]);
-#ifdef SP_PRE_TIMING_MFMA16      // TIMING ONLY (wrong results): the same matrix work as six v_mfma_f32_16x16x32_f16 on accumulator quarters
-                            {
-                                f32x4s q0 = __builtin_shufflevector(acc[m][n], acc[m][n], 0, 1, 2, 3), q1 = __builtin_shufflevector(acc[m][n], acc[m][n], 4, 5, 6, 7);
-                                f32x4s q2 = __builtin_shufflevector(acc[m][n], acc[m][n], 8, 9, 10, 11), q3 = __builtin_shufflevector(acc[m][n], acc[m][n], 12, 13, 14, 15);
-                                q0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh, q0, 0, 0, 0);
-                                q1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm, q1, 0, 0, 0);
-                                q2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, q2, 0, 0, 0);
-                                q3 = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh, q3, 0, 0, 0);
-                                q0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm, q0, 0, 0, 0);
-                                q1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, q1, 0, 0, 0);
-                                const auto lo = __builtin_shufflevector(q0, q1, 0, 1, 2, 3, 4, 5, 6, 7), hi = __builtin_shufflevector(q2, q3, 0, 1, 2, 3, 4, 5, 6, 7);
-                                acc[m][n] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-                            }
-#ifdef SP_PRE_TIMING_EXTRA        // ... plus what the real K-packed kernel adds: one wasted half MFMA per tile and chunk, 36 more fragment reads
-                            if (idx == 8 && n == 0) {
-                                f32x4s q0 = __builtin_shufflevector(acc[m][1], acc[m][1], 0, 1, 2, 3), q1 = __builtin_shufflevector(acc[m][1], acc[m][1], 4, 5, 6, 7);
-                                f32x4s q2 = __builtin_shufflevector(acc[m][1], acc[m][1], 8, 9, 10, 11), q3 = __builtin_shufflevector(acc[m][1], acc[m][1], 12, 13, 14, 15);
-                                q0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bm, q0, 0, 0, 0);
-                                q1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bm, q1, 0, 0, 0);
-                                q2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bm, q2, 0, 0, 0);
-                                q3 = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bm, q3, 0, 0, 0);
-                                const auto lo = __builtin_shufflevector(q0, q1, 0, 1, 2, 3, 4, 5, 6, 7), hi = __builtin_shufflevector(q2, q3, 0, 1, 2, 3, 4, 5, 6, 7);
-                                acc[m][1] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-                            }
-                            if (n == 0) {
-                                const u32x4s e0 = ab[(idx * 2 + m) * 64 + 16], e1 = bb[(idx + m) * IN_COLS + 2 + IN_PART];
-                                asm volatile("" :: "v"(e0), "v"(e1));
-                            }
-#endif
-                            continue;
-#endif
                             acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(am, bh, acc[m][n], 0, 0, 0);
                             acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bm, acc[m][n], 0, 0, 0);
                             acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[m][n], 0, 0, 0);
@@ -1073,7 +1037,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     using C = SpPreCfg<W16>;
     static_assert(C::NW == 8 && C::NT == 2, "conv3x3_pre16_kernel: 8 waves of 2 rows");
     constexpr int NT = 2, IN_COLS = C::IN_COLS, NWI = C::NWI, CO_T = C::CO_T, NPIXP = C::NPIXP;
-    constexpr int BUF = C::BUF_SLOTS, W_PART = C::W_PART, IN_PART = C::IN_PART, ROWS = C::ROWS, TW = C::TW;
+    constexpr int BUF = C::BUF_SLOTS, IN_PART = C::IN_PART, ROWS = C::ROWS, TW = C::TW;
     constexpr int NII = (2 * IN_PART + 511) / 512;
     constexpr int CH_OFF = W16 ? 18 : 16;                              // column of the second 16-pixel tile in the halo image
     constexpr int NSTEP = PM == 2 ? 9 : 14;
@@ -1236,11 +1200,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
                 }
                 if (s == 0) advance();
                 {
-                    constexpr int NPIECE = NII + NWI, PER = (NPIECE + SP_PRE_LAST_TAP) / (SP_PRE_LAST_TAP + 1);
+                    constexpr int NPIECE = NII + NWI, PER = (NPIECE + C::LAST_TAP) / (C::LAST_TAP + 1);
 #pragma unroll
                     for (int q = 0; q < PER; ++q) {
                         const int pc = s * PER + q;
-                        if (s <= SP_PRE_LAST_TAP && pc < NPIECE) {
+                        if (s <= C::LAST_TAP && pc < NPIECE) {
                             if (pc & 1) { if (pc / 2 < NWI) dma_w(buf ^ 1, pc / 2); else dma_in(buf ^ 1, pc - NWI); }
                             else { if (pc / 2 < NII) dma_in(buf ^ 1, pc / 2); else dma_w(buf ^ 1, pc - NII); }
                         }
@@ -1498,9 +1462,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     }
 }
 
-#ifndef SP_PRE16
-#define SP_PRE16 1      // 1: conv3x3_pre16_kernel (v_mfma_f32_16x16x32); 0: conv3x3_split_pre_kernel (32x32x16) -- same-box A/B builds
-#endif
 template <bool ST, int PM, bool W16, bool RD = false>
 int launch_split_pre(SpPreArgs a, hipStream_t st) {
     using C = SpPreCfg<W16>;
@@ -1514,8 +1475,8 @@ int launch_split_pre(SpPreArgs a, hipStream_t st) {
     // which launches take the 16x16x32 kernel (profiles/r05_mfma_shape_ab.md): plain bf16 operands (K = 32 channels: no packing) always; the
     // (hi | mid) forward WITH the statistics epilogue and the input gradients that carry the fused reduce (the lane layout's cheap
     // epilogues: -5 %); the plain (hi | mid) input gradient keeps the 32x32x16 kernel (equal speed), and so does the (hi | mid) 16-pixel
-    // level (that instance of the new kernel exceeds the register budget).  SP_PRE16 = 2 / 0: everything / nothing (A-B builds).
-    constexpr bool P16 = RD || (SP_PRE16 > 1) || (SP_PRE16 == 1 && (PM == 2 || (ST && !W16)));
+    // level (that instance of the new kernel exceeds the register budget).
+    constexpr bool P16 = RD || PM == 2 || (ST && !W16);
     void (*kern)(SpPreArgs);
     if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD>;      // (constexpr: the instances not dispatched are not built)
     else kern = conv3x3_split_pre_kernel<ST, PM, W16>;
@@ -1605,13 +1566,6 @@ struct SwArgs {
     const unsigned* dz_amax;   //      lands in [2^13, 2^14)); the slab store undoes both scales
 };
 
-// MFMA groups of a unit (6 with 64-channel tiles, 12 with 128) before the next unit's rows are committed
-#ifndef SW_CAT64
-#define SW_CAT64 2
-#endif
-#ifndef SW_CAT128
-#define SW_CAT128 5
-#endif
 // Maps narrower than a strip (G = 64 / W = 2 or 4: the 32- and 16-pixel levels): a unit is row y of G IMAGES side by side -- the dz
 // row is their 64 pixels back to back, the x row keeps each image's own halo (sub-row pitch SR_P dwords: W / 2 data dwords + the
 // right-halo dword, rounded to 16 bytes), so a horizontal shift never reads a neighbouring image's pixel.  Everything else -- the
@@ -1816,7 +1770,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_split_wgrad_kernel(SwArgs a) {
             const bool more = y + 1 < ye, more2 = y + 2 < ye;
             const unsigned* ab = a_ptr + buf * 2 * SR_DZ_PART;
             u32x4s ah, am;
-            constexpr int CAT = COT == 64 ? SW_CAT64 : SW_CAT128;
+            // MFMA groups of the unit (of 6 with 64-channel tiles, 12 with 128) before the next unit's rows are committed
+            constexpr int CAT = COT == 64 ? 2 : 5;
             // Segments run LAST TO FIRST: a lane's 8-pixel fragment is one aligned ds_read_b128 (4 dwords); the fifth dword its
             // shifted copies need is the first dword of the NEXT 8-pixel group -- for the kh = 0 half that of its kh = 1 partner in
             // the same read, for the kh = 1 half that of the kh = 0 lane of the segment read one group earlier: both arrive by
@@ -1917,9 +1872,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_split_wgrad_kernel(SwArgs a) {
 // A channel group's plane of 68 slots = 272 dwords = 16 banks (mod 64): the 4 pixel rows x (2 groups x 2 half-slots) a 32-lane
 // half reads fall on 64 different banks -- conflict-free without a swizzle.
 typedef short s16x4w __attribute__((ext_vector_type(4)));
-#ifndef SWP_SHARE_B
-#define SWP_SHARE_B 1
-#endif
 struct SwPreArgs {
     const void* xs;
     int64_t xs_bs;        // batch strides in 4-byte units
@@ -1941,212 +1893,12 @@ __device__ __forceinline__ u32x4s swp_frag(unsigned addr) {      // 8 consecutiv
     return u32x4s{(unsigned)a, (unsigned)(a >> 32), (unsigned)b, (unsigned)(b >> 32)};
 }
 
+// The MFMA shape is v_mfma_f32_16x16x32 (profiles/r05_mfma_shape_ab.md: the shape the chip clocks higher on).  K = pixels here, so
+// K = 32 is natural -- one instruction takes 32 consecutive pixels of a unit's row, no K-packing.  A wave's 32 x 32 channel tile per
+// tap is four 16 x 16 accumulators; M = input channels (A = x fragment), N = output channels (B = dz fragment), so a lane owns four
+// CONSECUTIVE input channels of one output channel and the slab leaves as float4 stores.  Lane group lg = lane / 16 takes pixels
+// 8 lg .. 8 lg + 7 of the step (G = 4, four 16-pixel images per unit: lane groups 0-1 / 2-3 sit in two different images' sub-rows).
 // PM: 0 bf16 (hi | mid), 1 fp16 (hi | mid) -- three MFMAs per term; 2: PLAIN bf16 operands, one part (BASELINE configs[2]), one MFMA
-template <int G, int COT, int PM>
-__global__ __launch_bounds__(512, 2) void conv3x3_split_wgrad_pre_kernel(SwPreArgs a) {
-    constexpr bool F16 = PM == 1;
-    constexpr int NP = PM == 2 ? 1 : 2;                        // parts per operand
-    constexpr int PXP = G == 4 ? 76 : SWP_PXP;
-    constexpr int XS = 8, DS = COT / 8;                        // channel groups per image
-    // (row images padded to whole 64-slot DMA pieces: the lanes of a piece beyond the image write zeros, which must not land in the
-    // next ring slot / buffer)
-    constexpr int X_PART = XS * PXP, X_ROW = (NP * X_PART + 63) / 64 * 64;      // slots
-    constexpr int DZ_PART = DS * PXP, DZ_BUF = (NP * DZ_PART + 63) / 64 * 64;
-    constexpr int NXI = (X_ROW + 511) / 512, NDI = (DZ_BUF + 511) / 512;      // DMA rounds per wave (64 slots each, 8 waves)
-    constexpr int NKS = COT == 64 ? 2 : 4;                     // k-steps (16 pixels) per wave and unit
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_w[];
-    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem_w;
-    const unsigned x_base = lds0, dz_base = lds0 + 4 * X_ROW * 16;
-
-    int bid;
-    {
-        const int n = gridDim.x, q = n >> 3, r = n & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
-    const int tiles = a.ciTiles * a.coTiles;
-    const int ks = bid / tiles, tile = bid % tiles;
-    const int ci0 = (tile % a.ciTiles) * 64, co0 = (tile / a.ciTiles) * COT;
-    const int nunits = (a.B / G) * a.tilesX * a.H;
-    const int per = (nunits + a.splitK - 1) / a.splitK;
-    const int u0 = ks * per, u1 = min(u0 + per, nunits);
-
-    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = COT == 64 ? wid >> 2 : 0, wm = COT == 64 ? (wid >> 1) & 1 : wid >> 1, wn = wid & 1;
-    const int l31 = lane & 31, kh = lane >> 5;
-    const int HW = a.H * a.W;
-
-    f32x16 acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-    // transposed-read lane bases (bytes): lane = 16 g + 4 q + p supplies pixel row q, channels 4 p .. 4 p + 3 of the channel half g & 1
-    const int tq = (lane >> 2) & 3, tp = lane & 3, tg = (lane >> 4) & 1;
-    const unsigned a_lane = (unsigned)((((wm * 4 + 2 * tg + (tp >> 1)) * PXP + 8 * kh + tq) * 16) + (tp & 1) * 8);
-    const unsigned b_lane = (unsigned)((((wn * 4 + 2 * tg + (tp >> 1)) * PXP + 8 * kh + tq) * 16) + (tp & 1) * 8);
-
-    // ---- staging: slot position i = (wid + 8 k) * 64 + lane of a row image [part][group][PXP]
-    i32x4s xr, dr;
-    unsigned x_off[NXI], d_off[NDI];
-    auto setup_strip = [&](int b, int x0) __attribute__((always_inline)) {
-        if (G == 1) {
-            xr = sp_rsrc4(reinterpret_cast<const unsigned*>(a.xs) + (int64_t)b * a.xs_bs, (int64_t)a.Cin * HW * 2 * NP);
-            dr = sp_rsrc4(reinterpret_cast<const unsigned*>(a.dzs) + (int64_t)b * a.dzs_bs, (int64_t)a.Cout * HW * 2 * NP);
-        } else {
-            xr = sp_rsrc4(a.xs, (int64_t)(a.B - 1) * a.xs_bs * 4 + (int64_t)a.Cin * HW * 2 * NP);
-            dr = sp_rsrc4(a.dzs, (int64_t)(a.B - 1) * a.dzs_bs * 4 + (int64_t)a.Cout * HW * 2 * NP);
-        }
-#pragma unroll
-        for (int k = 0; k < NXI; ++k) {
-            const int i = (wid + 8 * k) * 64 + lane;
-            const int part = i / X_PART, s = (i % X_PART) / PXP, pi = i % PXP;
-            const int img = G == 1 ? 0 : pi / (a.W + 2), xx = G == 1 ? x0 - 1 + pi : pi % (a.W + 2) - 1;
-            const bool ok = i < NP * X_PART && pi < (G == 1 ? 66 : G * (a.W + 2)) && xx >= 0 && xx < a.W && ci0 + 8 * s < a.Cin;
-            const int64_t img_off = G == 1 ? 0 : (int64_t)(b * G + img) * a.xs_bs * 4;
-            x_off[k] = ok ? (unsigned)(img_off + ((int64_t)((ci0 / 8 + s) * a.H) * NP + part) * a.W * 16 + xx * 16) : OOB_S;
-        }
-#pragma unroll
-        for (int k = 0; k < NDI; ++k) {
-            const int i = (wid + 8 * k) * 64 + lane;
-            const int part = i / DZ_PART, s = (i % DZ_PART) / PXP, pi = i % PXP;
-            const int img = G == 1 ? 0 : pi / a.W, xx = G == 1 ? x0 + pi : pi % a.W;
-            const bool ok = i < NP * DZ_PART && pi < 64 && xx < a.W && co0 + 8 * s < a.Cout;
-            const int64_t img_off = G == 1 ? 0 : (int64_t)(b * G + img) * a.dzs_bs * 4;
-            d_off[k] = ok ? (unsigned)(img_off + ((int64_t)((co0 / 8 + s) * a.H) * NP + part) * a.W * 16 + xx * 16) : OOB_S;
-        }
-    };
-    // row y of the strip into ring slot / dz buffer; rows outside the image are zeros (every lane out of range)
-    auto dma_x = [&](int y, int k) __attribute__((always_inline)) {
-        if ((wid + 8 * k) * 64 < X_ROW) {
-            const bool ok = y >= 0 && y < a.H;
-            sp_dma16(xr, x_base + (unsigned)(((y & 3) * X_ROW + (wid + 8 * k) * 64) * 16), ok ? x_off[k] : OOB_S, ok ? (unsigned)(y * NP * a.W * 16) : 0u);
-        }
-    };
-    auto dma_dz = [&](int y, int k) __attribute__((always_inline)) {
-        if ((wid + 8 * k) * 64 < DZ_BUF) {
-            const bool ok = y >= 0 && y < a.H;
-            sp_dma16(dr, dz_base + (unsigned)(((y & 1) * DZ_BUF + (wid + 8 * k) * 64) * 16), ok ? d_off[k] : OOB_S, ok ? (unsigned)(y * NP * a.W * 16) : 0u);
-        }
-    };
-
-    int u = u0;
-    while (u < u1) {
-        const int yb = u % a.H, sb = u / a.H;
-        const int tx = sb % a.tilesX, b = sb / a.tilesX;
-        const int x0 = G == 1 ? tx * 64 : 0;
-        const int ye = min(a.H, yb + (u1 - u));
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();                              // every wave is done with the previous run's ring and dz buffers
-        setup_strip(b, x0);
-#pragma unroll
-        for (int k = 0; k < NXI; ++k) {
-            dma_x(yb - 1, k);
-            dma_x(yb, k);
-            dma_x(yb + 1, k);
-        }
-#pragma unroll
-        for (int k = 0; k < NDI; ++k) dma_dz(yb, k);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        for (int y = yb; y < ye; ++y) {
-            // unit y: MFMAs on dz buffer y & 1 and ring rows y - 1 .. y + 1; the rows of unit y + 1 (dz row y + 1, x row y + 2) go
-            // by DMA into the other dz buffer and the ring slot of row y - 2 (both last read in unit y - 1), spread over the k-steps
-            const bool more = y + 1 < ye;
-            const unsigned ab = dz_base + (unsigned)((y & 1) * DZ_BUF * 16) + a_lane;
-            unsigned bb[3];
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) bb[ky] = x_base + (unsigned)((((y - 1 + ky) & 3) * X_ROW) * 16) + b_lane;
-#pragma unroll
-            for (int kk = 0; kk < NKS; ++kk) {
-                const int kst = grp * 2 + kk;                                  // 16-pixel k-step of the unit
-                const int dpx = 16 * kst;                                      // dz pixel slot
-                const int xpx = G == 1 ? 16 * kst : (G == 2 ? (kst >> 1) * 34 + (kst & 1) * 16 : kst * 18);      // x pixel slot of tap kx = 0
-                if (more) {
-                    constexpr int NP = NXI + NDI, PER = (NP + NKS - 1) / NKS;
-#pragma unroll
-                    for (int q = 0; q < PER; ++q) {
-                        const int pc = kk * PER + q;
-                        if (pc < NDI) dma_dz(y + 1, pc);
-                        else if (pc < NP) dma_x(y + 2, pc - NDI);
-                    }
-                }
-                const u32x4s Ah = swp_frag(ab + dpx * 16), Am = NP == 2 ? swp_frag(ab + (DZ_PART + dpx) * 16) : Ah;
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky) {
-#if SWP_SHARE_B
-                    // the three horizontal taps of a row read pixels 8 kh + kx .. + 7: ONE set of three transposed reads (12 pixels, six
-                    // dwords of two pixels each) serves all three -- kx = 0: dwords 0-3, kx = 2: dwords 1-4, kx = 1: the 16-bit-shifted
-                    // pairs (v_alignbit) -- instead of two reads per tap and part (40 -> 22 LDS reads per 27 MFMAs)
-                    u32x4s Bs[2][3];
-#pragma unroll
-                    for (int pt = 0; pt < NP; ++pt) {
-                        const unsigned ba = bb[ky] + (pt * X_PART + xpx) * 16;
-                        const u32x4s lo = swp_frag(ba);                                       // pixels 0 .. 7 of the lane's window
-                        const s16x4w r2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4w*)(uintptr_t)(ba + 128));
-                        const unsigned d4 = (unsigned)__builtin_bit_cast(unsigned long long, r2);   // pixels 8, 9
-                        Bs[pt][0] = lo;
-                        Bs[pt][1] = u32x4s{__builtin_amdgcn_alignbit(lo[1], lo[0], 16), __builtin_amdgcn_alignbit(lo[2], lo[1], 16),
-                                           __builtin_amdgcn_alignbit(lo[3], lo[2], 16), __builtin_amdgcn_alignbit(d4, lo[3], 16)};
-                        Bs[pt][2] = u32x4s{lo[1], lo[2], lo[3], d4};
-                    }
-#endif
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-#if SWP_SHARE_B
-                        const u32x4s Bh = Bs[0][kx], Bm = NP == 2 ? Bs[1][kx] : Bs[0][kx];
-#else
-                        const u32x4s Bh = swp_frag(bb[ky] + (xpx + kx) * 16), Bm = NP == 2 ? swp_frag(bb[ky] + (X_PART + xpx + kx) * 16) : Bh;
-#endif
-                        const int t = ky * 3 + kx;
-                        if constexpr (PM == 2) {
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Ah), __builtin_bit_cast(bf16x8, Bh), acc[t], 0, 0, 0);
-                        } else if constexpr (F16) {
-                            const f16x8 ah = __builtin_bit_cast(f16x8, Ah), am = __builtin_bit_cast(f16x8, Am);
-                            const f16x8 bh = __builtin_bit_cast(f16x8, Bh), bm = __builtin_bit_cast(f16x8, Bm);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(am, bh, acc[t], 0, 0, 0);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bm, acc[t], 0, 0, 0);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[t], 0, 0, 0);
-                        } else {
-                            const bf16x8 ah = __builtin_bit_cast(bf16x8, Ah), am = __builtin_bit_cast(bf16x8, Am);
-                            const bf16x8 bh = __builtin_bit_cast(bf16x8, Bh), bm = __builtin_bit_cast(bf16x8, Bm);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[t], 0, 0, 0);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[t], 0, 0, 0);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[t], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-        }
-        u += ye - yb;
-    }
-
-    float x_inv = 1.f, dz_inv = 1.f;
-    const unsigned* xsl = (a.split_ch && ci0 >= a.split_ch) ? a.x_slots2 : a.x_slots;      // this block's 64 input channels
-    (void)amax_scale(amax_read(xsl), false, x_inv);
-    (void)amax_scale(amax_read(a.dz_slots), true, dz_inv);
-    const float out_scale = (xsl ? x_inv : 1.f) * (a.dz_slots ? dz_inv : 1.f);
-    const int64_t n = (int64_t)a.Cout * a.Cin;
-    const int ci = ci0 + wn * 32 + l31;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        float* o = a.slab + ((int64_t)(COT == 64 ? ks * 2 + grp : ks) * 9 + t) * n;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int co = co0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-            if (co < a.Cout && ci < a.Cin) o[(int64_t)co * a.Cin + ci] = acc[t][r] * out_scale;
-        }
-    }
-}
-
-// Round 5: the same kernel on v_mfma_f32_16x16x32 (profiles/r05_mfma_shape_ab.md: the shape the chip clocks higher on).  K = pixels here,
-// so K = 32 is natural -- one instruction takes 32 consecutive pixels of a unit's row (two of the 32x32x16 form's 16-pixel k-steps),
-// no K-packing, the same LDS image, DMA schedule and fragment bytes.  A wave's 32 x 32 channel tile per tap is four 16 x 16
-// accumulators; M = input channels (A = x fragment), N = output channels (B = dz fragment), so a lane owns four CONSECUTIVE input
-// channels of one output channel and the slab leaves as float4 stores.  Lane group lg = lane / 16 takes pixels 8 lg .. 8 lg + 7 of the
-// step (G = 4, four 16-pixel images per unit: lane groups 0-1 / 2-3 sit in two different images' sub-rows).
 template <int G, int COT, int PM>
 __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_pre16_kernel(SwPreArgs a) {
     constexpr bool F16 = PM == 1;
@@ -2356,16 +2108,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_pre16_kernel(SwPreArgs a
     }
 }
 
-#ifndef SP_WGRAD16
-#define SP_WGRAD16 1     // 1: conv3x3_wgrad_pre16_kernel (v_mfma_f32_16x16x32); 0: conv3x3_split_wgrad_pre_kernel -- same-box A/B builds
-#endif
-
 int split_wgrad_group(int W) { return W >= 64 ? 1 : 64 / W; }      // images per unit: 1, 2 (W = 32), 4 (W = 16)
 
-#ifndef SW_COT128
-#define SW_COT128 1
-#endif
-int split_wgrad_cot(int Cout, int W) { return (SW_COT128 && Cout % 128 == 0 && W >= 32) ? 128 : 64; }    // output channels per block
+int split_wgrad_cot(int Cout, int W) { return (Cout % 128 == 0 && W >= 32) ? 128 : 64; }    // output channels per block
 
 void split_wgrad_plan(int B, int Cin, int Cout, int H, int W, int& splitK, int& tilesX) {
     tilesX = W >= 64 ? cdiv(W, 64) : 1;
@@ -2484,7 +2229,7 @@ int onet_conv3x3_split_wgrad_pre(const void* xs, int64_t xs_bs, const void* x_am
     const int lds = (4 * ((np * 8 * pxp + 63) / 64 * 64) + 2 * ((np * (COT / 8) * pxp + 63) / 64 * 64)) * 16;
 #define ONET_SWP_LAUNCH(G_, COT_, F_)                                                                              \
     do {                                                                                                           \
-        auto kern = SP_WGRAD16 ? conv3x3_wgrad_pre16_kernel<G_, COT_, F_> : conv3x3_split_wgrad_pre_kernel<G_, COT_, F_>; \
+        auto kern = conv3x3_wgrad_pre16_kernel<G_, COT_, F_>;                                                      \
         static PerDeviceOnce once;                                                                                 \
         if (once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
         hipLaunchKernelGGL(kern, grid, blk, lds, st, a);                                                           \
@@ -2582,7 +2327,7 @@ int onet_conv3x3_split_pre_nparts(int B, int H, int W) {
 int onet_conv3x3_split_fwd_pre(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
                                const void* wq, int wq_f16, void* z, int z_bf16, int64_t z_bs, float* part, int B, int Cin, int Cout, int H, int W,
                                void* stream) {
-    ONET_REQUIRE(!z_bf16 || (wq_f16 == 2 && SP_PRE16 && (z_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(z) & 7) == 0),
+    ONET_REQUIRE(!z_bf16 || (wq_f16 == 2 && (z_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(z) & 7) == 0),
                  "conv3x3_split_fwd_pre: a bf16 output goes with plain bf16 operands (wq_f16 == 2), 8-byte aligned rows");
     ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "conv3x3_split_fwd_pre: split_ch must be a multiple of 32 inside Cin");
     ONET_REQUIRE(xs && wq && z, "conv3x3_split_fwd_pre: null pointer");

@@ -15,10 +15,6 @@
 
 using namespace onet;
 
-#ifndef ONET_W4W_ASYM
-#define ONET_W4W_ASYM 1
-#endif
-
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4w __attribute__((ext_vector_type(4)));
 typedef float f32x2w __attribute__((ext_vector_type(2)));
@@ -224,8 +220,8 @@ static __device__ __forceinline__ void wino4w_body(const W4wArgs a, float* lds) 
         }
     };
 
-    // unit u lives in buffer (u - u0) & 1; the registers hold unit u+1 during the first half of unit u's K-steps and are
-    // committed to the other buffer between K-steps 1 and 2 (every wave left that buffer at the barrier that ended unit
+    // unit u lives in buffer (u - u0) & 1; the registers hold unit u+1 during the first K-steps of unit u and are
+    // committed to the other buffer after K-step 0 or 1 (every wave left that buffer at the barrier that ended unit
     // u-1), then take unit u+2: ONE barrier per unit
     issue(u0);
     commit(lds);
@@ -234,7 +230,6 @@ static __device__ __forceinline__ void wino4w_body(const W4wArgs a, float* lds) 
     for (int u = u0; u < u1; ++u) {
         float* cur = lds + ((u - u0) & 1) * W4_BUF_FLOATS;
         float* nxt = lds + (((u - u0) & 1) ^ 1) * W4_BUF_FLOATS;
-#if ONET_W4W_ASYM
         // the x rows are staged by waves 0..2, the dz rows by waves 4..7: SIMD partners (w, w + 4), i.e. position groups with
         // RH = 0 / 1.  In lockstep both partners sit in their staging burst (8 b128 loads + 9 b128 LDS stores) at once
         // and the matrix pipe idles: the RH = 1 waves stage one K-step earlier
@@ -243,12 +238,6 @@ static __device__ __forceinline__ void wino4w_body(const W4wArgs a, float* lds) 
         ksteps(cur, 1, 2);
         if constexpr (RH == 0) { commit(nxt); issue(u + 2); }
         ksteps(cur, 2, 4);
-#else
-        ksteps(cur, 0, 2);
-        commit(nxt);
-        issue(u + 2);
-        ksteps(cur, 2, 4);
-#endif
         __syncthreads();
     }
 

@@ -26,10 +26,6 @@
 
 using namespace onet;
 
-#ifndef ONET_GEMM_SPREAD
-#define ONET_GEMM_SPREAD 0
-#endif
-
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4g __attribute__((ext_vector_type(4)));
 typedef float f32x2g __attribute__((ext_vector_type(2)));
@@ -204,16 +200,13 @@ __global__ __launch_bounds__(256, 2) void convt_gemm_kernel(GArgs g) {
     }
     const unsigned a_step = MODE == 0 ? (unsigned)((int64_t)KC * M * 4) : (unsigned)(4 * M * 4);       // dgrad: 4 channels on
     const unsigned b_step = MODE == 0 ? (unsigned)((int64_t)KC * hw * 4) : (unsigned)((int64_t)4 * g.HoWo * 4);
-    // piece q of the wave's four per chunk: 0, 1 = its two A pieces, 2, 3 = its two B pieces
-    auto issue1 = [&](int chunk, int buf, int q) __attribute__((always_inline)) {
-        const unsigned la = g_lds(lds) + (unsigned)(buf * 2 * TILE_F * 4), lb = la + TILE_F * 4;
-        const int j = q & 1;
-        if (q < 2) g_dma16(ra, la + (2 * wid + j) * 1024, a_off[j] + chunk * a_step);
-        else g_dma16(rb, lb + (2 * wid + j) * 1024, b_off[j] + chunk * b_step);
-    };
+    // the wave's four pieces of a chunk: its two A pieces, then its two B pieces
     auto issue = [&](int chunk, int buf) __attribute__((always_inline)) {
+        const unsigned la = g_lds(lds) + (unsigned)(buf * 2 * TILE_F * 4), lb = la + TILE_F * 4;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) issue1(chunk, buf, q);
+        for (int j = 0; j < 2; ++j) g_dma16(ra, la + (2 * wid + j) * 1024, a_off[j] + chunk * a_step);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) g_dma16(rb, lb + (2 * wid + j) * 1024, b_off[j] + chunk * b_step);
     };
 
     f32x16 acc[2][2];
@@ -270,13 +263,9 @@ __global__ __launch_bounds__(256, 2) void convt_gemm_kernel(GArgs g) {
         } else {
 #pragma unroll
         for (int s = 0; s < KC / 2; ++s) {
-            // the next chunk's four DMA pieces go out one per two K-steps, not as a burst in front of the MFMAs (a piece
-            // holds the issuing wave for 60-180 cycles)
-#if ONET_GEMM_SPREAD
-            if ((s & 1) == 0 && more) issue1(c + 1, buf ^ 1, s >> 1);
-#else
+            // the next chunk's four DMA pieces go out as one burst in front of the MFMAs: spread one per two K-steps they
+            // measured slower (0.520 -> 0.531 ms; with 2-5 blocks per CU the bursts of different blocks already interleave)
             if (s == 0 && more) issue(c + 1, buf ^ 1);
-#endif
             float av[2], bv[2];
 #pragma unroll
             for (int t = 0; t < 2; ++t) av[t] = A[(2 * s + kh) * 128 + t * 32];
@@ -400,7 +389,7 @@ __global__ __launch_bounds__(256, 2) void convt_wgrad_gemm_kernel(GArgs g) {
     // DMA roles per chunk: 16 A pieces (8 rows x 128 B each) + 16 B pieces (4 rows x 256 B each), 8 per wave
     // A: lane -> row = 8 p + (l >> 3), physical 16-B chunk l & 7 holds source chunk (l & 7) ^ ((row >> 1) & 7)
     // B: lane -> row = 4 p + (l >> 4), physical chunk l & 15 holds source chunk (l & 15) ^ (row & 7)
-    auto issue = [&](int chunk, int buf, int j0, int j1) __attribute__((always_inline)) {
+    auto issue = [&](int chunk, int buf) __attribute__((always_inline)) {
         const int64_t pix = (int64_t)chunk * KP;
         const int b = (int)(pix / hw), p0 = (int)(pix % hw);
         const i32x4g rx = g_rsrc(g.a + (int64_t)b * g.a_bs, (int64_t)g.Cin * hw * 4);
@@ -408,7 +397,6 @@ __global__ __launch_bounds__(256, 2) void convt_wgrad_gemm_kernel(GArgs g) {
         const unsigned la = g_lds(lds) + (unsigned)(buf * (WA_F + WB_F) * 4), lb = la + WA_F * 4;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if (j < j0 || j >= j1) continue;
             const int p = 4 * wid + j;
             {
                 const int row = 8 * p + (lane >> 3), src = (lane & 7) ^ ((row >> 1) & 7);
@@ -441,7 +429,7 @@ __global__ __launch_bounds__(256, 2) void convt_wgrad_gemm_kernel(GArgs g) {
     const bool dj = (l31 & 1) != 0;
 
     if (ch0 < ch1) {
-        issue(ch0, 0, 0, 4);
+        issue(ch0, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
@@ -451,7 +439,7 @@ __global__ __launch_bounds__(256, 2) void convt_wgrad_gemm_kernel(GArgs g) {
         const float* A = lds + buf * (WA_F + WB_F);
         const float* Bt = A + WA_F;
         if constexpr (PREC != 0) {
-            if (more) issue(c + 1, buf ^ 1, 0, 4);
+            if (more) issue(c + 1, buf ^ 1);
             // K = 16 pixels per MFMA: lane (i, kh) holds pixels 8 gg + 4 kh + 0..3 of two consecutive 8-pixel groups
 #pragma unroll
             for (int g2 = 0; g2 < KP / 16; ++g2) {
@@ -479,11 +467,7 @@ __global__ __launch_bounds__(256, 2) void convt_wgrad_gemm_kernel(GArgs g) {
         } else {
 #pragma unroll
         for (int gg = 0; gg < KP / 8; ++gg) {
-#if ONET_GEMM_SPREAD
-            if (more) issue(c + 1, buf ^ 1, gg, gg + 1);        // one A and one B piece of the next chunk per 16 MFMAs
-#else
-            if (gg == 0 && more) issue(c + 1, buf ^ 1, 0, 4);
-#endif
+            if (gg == 0 && more) issue(c + 1, buf ^ 1);     // one burst (spread over the groups: 0.561 -> 0.610 ms)
             f32x4g a4[2], b4[2][2];
 #pragma unroll
             for (int t = 0; t < 2; ++t)
@@ -585,12 +569,9 @@ __device__ __forceinline__ f32x16 s_mfma(u32x4g a, u32x4g b, f32x16 c) {
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8g, a), __builtin_bit_cast(bf16x8g, b), c, 0, 0, 0);
 }
 
-#ifndef SLOT_NST
-#define SLOT_NST 2       // measured (B = 64, the four decoder levels, forward): 2 stages / 4 blocks per CU 1.17 ms, 3 / 3 1.20, 4 / 2 1.24
-#endif
-#ifndef SLOT_OCC
-#define SLOT_OCC 4
-#endif
+// stages of the forward / input-gradient ring and blocks per CU, measured (B = 64, the four decoder levels, forward): 2 stages / 4
+// blocks per CU 1.17 ms, 3 / 3 1.20, 4 / 2 1.24
+constexpr int SLOT_NST = 2, SLOT_OCC = 4;
 template <int N>
 __device__ __forceinline__ void slot_wait() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -884,7 +865,7 @@ __global__ __launch_bounds__(256, SLOT_OCC) void convt_slot_dgrad_kernel(SDArgs 
 
 // ---- weight gradient on slot operands:  dW[ci][c][di][dj] = sum_{b,i,j} x[b][ci][i][j] dy[b][c][2i+di][2j+dj]   (M = Cin, N = 4 Ct, K = pixels)
 // Both operands are pre-split tensors, channels contiguous inside a slot and the reduction index (pixels) running ACROSS slots: the
-// fragments are read with the transposing LDS read ds_read_b64_tr_b16, exactly as conv3x3_split_wgrad_pre_kernel does (conv_split.hip:
+// fragments are read with the transposing LDS read ds_read_b64_tr_b16, exactly as conv3x3_wgrad_pre16_kernel does (conv_split.hip:
 // a 16-lane group fetches 4 pixel slots x 16 channels and every lane receives ITS channel's four pixels).  Block tile: 128 input
 // channels (16 slot groups) x 32 output channels (4 groups) x 4 sub-pixels; a K-chunk = 32 input pixels; LDS image of a chunk =
 // planes of PXP = 36 slots (32 + 4 pad: 144 dwords = 16 banks mod 64, the conflict-free plane pitch of the 3x3 kernel):
@@ -909,21 +890,18 @@ struct SWArgs {
 // Ct % 64 == 0): 256 input channels x (64 output channels x 4 sub-pixels), EIGHT waves of 128 x 64, one block per CU: twice the MFMAs
 // per staged byte and per barrier (MFMA busy 0.35 -> 0.40 on the 1024-channel level; a per-chunk 64-bit division in the staging code
 // had cost 6 scalar instructions per MFMA).
-#ifndef SLOT_WGRAD_BIG
-#define SLOT_WGRAD_BIG 1
-#endif
-#ifndef SLOT_WGRAD_BIG_CP
-#define SLOT_WGRAD_BIG_CP 32     // (measured, B = 64, four levels: 32-pixel chunks / 2 stages 1.28 ms, 16-pixel chunks / ring of 3 1.35; the 128 x 128 tile 1.47)
-#endif
+// pixels per chunk, both tiles (measured, B = 64, four levels: 32-pixel chunks / 2 stages 1.28 ms, 16-pixel chunks / ring of 3 1.35;
+// the 128 x 128 tile 1.47)
+constexpr int SW_CP = 32;
 template <int BIG> struct SwCfg {
     static constexpr int NWAVE = BIG ? 8 : 4;
     static constexpr int TM = BIG ? 4 : 2;                    // 32-row accumulator tiles per wave along M (waves: 2 along M)
     static constexpr int GB = BIG ? 8 : 4;                    // output-channel groups per block (GB * 8 channels)
     static constexpr int APL = 2 * TM * 4;                    // A planes per part (input-channel groups)
     static constexpr int BPL = 4 * GB;                        // B planes per part: [sub-pixel q][group]
-    static constexpr int CP = BIG ? SLOT_WGRAD_BIG_CP : 32;   // pixels per chunk
-    static constexpr int PXP = CP + 4;                        // plane pitch in slots: 36 / 20 -> 144 / 80 dwords = 16 banks mod 64
-    static constexpr int NST = BIG ? (SLOT_WGRAD_BIG_CP == 16 ? 3 : 2) : 2;
+    static constexpr int CP = SW_CP;                          // pixels per chunk
+    static constexpr int PXP = CP + 4;                        // plane pitch in slots: 36 -> 144 dwords = 16 banks mod 64
+    static constexpr int NST = 2;
     static constexpr int MT = 64 * TM;                        // block tile rows (input channels)
 };
 
@@ -944,7 +922,7 @@ __global__ __launch_bounds__(SwCfg<BIG>::NWAVE * 64, BIG ? 1 : 2) void convt_slo
     constexpr int STAGE = NP * (A_SLOTS + B_SLOTS);
     constexpr int NPIECE = STAGE / 64;
     constexpr int NPW = (NPIECE + NWAVE - 1) / NWAVE;                       // pieces per wave and chunk
-    constexpr int LOG_CP = CP == 16 ? 4 : 5;
+    constexpr int LOG_CP = __builtin_ctz(CP);
     extern __shared__ __attribute__((aligned(16))) unsigned char sw_smem[];
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)sw_smem;
     const int bid = xcd_order(gridDim.x);
@@ -1327,13 +1305,13 @@ int convt_gemm_wgrad(const float* x, int64_t x_bs, const float* dy, int64_t dy_b
 
 }  // namespace onet
 
-// split-K plan of the slot-operand weight gradient: -> big (256 x 256 tiles, 16-pixel chunks) or not (128 x 128, 32-pixel chunks)
+// split-K plan of the slot-operand weight gradient: -> big (256 x 256 tiles) or not (128 x 128)
 static bool wgrad_slots_plan(int B, int Cin, int Ct, int h, int w, int& splitK, int& per) {
     const bool big = (Cin % 256) == 0 && (Ct % 64) == 0;
-    const int64_t chunks = (int64_t)B * h * w / (big ? SLOT_WGRAD_BIG_CP : 32);
+    const int64_t chunks = (int64_t)B * h * w / SW_CP;
     const int64_t tiles = big ? (int64_t)(Cin / 256) * (Ct / 64) : (int64_t)(Cin / 128) * (Ct / 32);
     int64_t k = std::max<int64_t>(1, ((big ? 256 : 512) + tiles - 1) / tiles);   // one (two) blocks per CU
-    k = std::min<int64_t>(k, std::max<int64_t>(1, chunks / (big ? 512 / SLOT_WGRAD_BIG_CP : 16)));     // at least 512 pixels per block
+    k = std::min<int64_t>(k, std::max<int64_t>(1, chunks / (512 / SW_CP)));     // at least 512 pixels per block
     k = std::min<int64_t>(k, std::max<int64_t>(1, (256ll << 20) / ((int64_t)Cin * 4 * Ct * 4)));
     per = (int)((chunks + k - 1) / k);
     splitK = (int)((chunks + per - 1) / per);
@@ -1407,18 +1385,7 @@ int onet_convT2x2_wgrad_slots(const void* xP, int64_t xP_bs, const void* x_amax,
     int lw = 0;
     while ((1 << lw) < w) ++lw;
     SWArgs g{xP, xP_bs, dyP, dyP_bs, (float*)ws, nullptr, (const unsigned*)x_amax, (const unsigned*)dy_amax, B, Cin, Ct, h, w, lw, 0, 0, 1, 0};
-    const bool big = wgrad_slots_plan(B, Cin, Ct, h, w, g.splitK, g.chunksPerSplit) && SLOT_WGRAD_BIG;
-    if (!big) {          // (SLOT_WGRAD_BIG = 0, A/B builds: the small tile's plan)
-        int k, per;
-        const int64_t chunks = (int64_t)B * hw / 32, tiles = (int64_t)(Cin / 128) * (Ct / 32);
-        int64_t kk = std::max<int64_t>(1, (512 + tiles - 1) / tiles);
-        kk = std::min<int64_t>(kk, std::max<int64_t>(1, chunks / 16));
-        kk = std::min<int64_t>(kk, std::max<int64_t>(1, (256ll << 20) / ((int64_t)Cin * 4 * Ct * 4)));
-        per = (int)((chunks + kk - 1) / kk);
-        k = (int)((chunks + per - 1) / per);
-        g.splitK = k;
-        g.chunksPerSplit = per;
-    }
+    const bool big = wgrad_slots_plan(B, Cin, Ct, h, w, g.splitK, g.chunksPerSplit);
     g.mTiles = big ? Cin / 256 : Cin / 128;
     g.nTiles = big ? Ct / 64 : Ct / 32;
     const int64_t n = (int64_t)Cin * 4 * Ct;

@@ -668,7 +668,7 @@ class TwinInputFn(torch.autograd.Function):
         x = x.contiguous()
         ctx.save_for_backward(x)
         ctx.bias = bias
-        if ops.TWIN_VIRTUAL and virtual:
+        if virtual:
             # K7 as SURVEY 2 states it: the complement half is formed by the stem kernels while they load X; the 2B-image tensor
             # exists only if some other reader asks for it (ops.plane materialises it once)
             return ops.twin_virtual(x, bias)

@@ -177,9 +177,6 @@ class DoubleConv(nn.Module):
         return self._unit(a1, s[3], s[4], None if out is None else (out,), groups, link_out=pool_link, link_in=link)
 
 
-_SKIPPOOL = ops._flag("SKIPPOOL", True)
-
-
 class MaxPool2(nn.MaxPool2d):
     """nn.MaxPool2d(2) (OV:67)."""
 
@@ -380,7 +377,7 @@ class UNet(nn.Module):
         def fork(t, returned=False, link=None, nxt=None):
             # skip tensors feed the next Down's pooling AND an Up's concat (x1 also leaves as the first output): one
             # node, so that their gradients are summed inside the pooling-backward kernel
-            if t.is_cuda and _SKIPPOOL:
+            if t.is_cuda:
                 am = ops.amax_of(t)
                 carry = {} if ops.presplit() else None        # (carries the pooled tensor's pre-split form back: "yP")
                 outs = Fn.SkipPoolFn.apply(t, returned, link, carry)
@@ -397,7 +394,7 @@ class UNet(nn.Module):
         c1 = self.down1.maxpool_conv[1].double_conv[3].out_channels
         c2 = self.down2.maxpool_conv[1].double_conv[3].out_channels
         c3 = self.down3.maxpool_conv[1].double_conv[3].out_channels
-        if x.dim() == 4 and x.is_cuda and _SKIPPOOL and ops.FUSE_POOL and not plain:
+        if x.dim() == 4 and x.is_cuda and ops.FUSE_POOL and not plain:
             # the four encoder outputs are max-pooled next: their BatchNorm + ReLU pass writes the pooled tensor too
             for i in range(4):
                 pl[i]["want_pool"] = {"p16": pool_p[i]}

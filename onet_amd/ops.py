@@ -33,15 +33,9 @@ _FLAGS = _flags_from_env()
 
 
 def _flag(name, default):
-    """Process default of switch `name`: ONET_FLAGS' value if given (bool switches: "0" = off; ints and strings as written)."""
+    """Process default of on/off switch `name`: ONET_FLAGS' value if given ("0" = off)."""
     v = _FLAGS.get(name)
-    if v is None:
-        return default
-    if isinstance(default, bool):
-        return v != "0"
-    if isinstance(default, int):
-        return int(v)
-    return v
+    return default if v is None else v != "0"
 
 
 class Settings:
@@ -152,7 +146,7 @@ def sync_bn():
 def presplit():
     """Pre-split storage (round 4): activations and BatchNorm-backward gradients whose consumers are the split convolution kernels
     are written by their producers as fp16 (hi, mid) parts in the kernels' slot layout; the MFMA kernels' staging is an LDS-DMA copy."""
-    if not bool(_setting("presplit", PRESPLIT)) or sync_bn() or not (FUSE_BN_STATS and FUSE_BN_REDUCE and FUSE_POOL):
+    if not bool(_setting("presplit", PRESPLIT)) or sync_bn() or not (FUSE_BN_REDUCE and FUSE_POOL):
         return False
     if conv_algo() == "bf16":           # BASELINE configs[2]: the same machinery with ONE part of plain bf16 operands (p16_parts() == 1)
         return True
@@ -660,9 +654,6 @@ def fp32_placeholder(shape, device):
     return t
 
 
-TWIN_VIRTUAL = _flag("TWIN_VIRTUAL", True)      # False (tests): TwinInputFn materialises the twin batch, the stem kernels read it like any batch
-
-
 def twin_virtual(x, bias):
     """The twin batch [X ; clip(1 - X + bias, 0, 1)] (OV:178-180 as one batch of 2B) WITHOUT its tensor: a placeholder of that shape
     carrying (X, bias).  The stem kernels (forward + statistics, weight gradient) form the complement half while they load X
@@ -803,10 +794,11 @@ def conv3x3_auto(x, pk, direction, out=None, amax=None):
     return conv_fwd(x, wq, Co, 3, out=out)
 
 
-FUSE_BN_STATS = _flag("FUSE_BN_STATS", True)
 BN_ON_LOAD = _flag("BN_ON_LOAD", True)        # 0: every BatchNorm + ReLU output is materialised
-BN_ON_LOAD_MAX_COUT = _flag("BN_ON_LOAD_MAX_COUT", 128)
-CONVT_SPLIT_MIN_BLOCKS = (int(_FLAGS["CONVT_SPLIT_MIN_BLOCKS"]) if "CONVT_SPLIT_MIN_BLOCKS" in _FLAGS else None)
+# every 64-channel output tile of the forward kernel normalises the input tile again: the extra staging work grows with
+# Cout / 64 while the saved pass does not -- measured worth it up to two output tiles (the 256- and 128-pixel levels)
+BN_ON_LOAD_MAX_COUT = 128
+CONVT_SPLIT_MIN_BLOCKS = None                 # tests may set a tile count; None: half the CUs (convt_operand_bf16)
 CONVT_SPLIT = _flag("CONVT_SPLIT", True)     # 0: the ConvTranspose2d GEMMs stay on the fp32 MFMA pipe
 SPLIT_F16 = _flag("SPLIT_F16", True)         # 0: the forward split kernel takes bf16 parts like the gradients
 SPLIT_DGRAD = _flag("SPLIT_DGRAD", True)     # 0 (diagnostic): input gradients stay on the fp32-MFMA kernels
@@ -819,7 +811,7 @@ PRESPLIT_KEEP_FP32 = _flag("PRESPLIT_KEEP_FP32", False)
 # the bf16 parts, but no change in the model-level worst gradient error -- 9.4e-5 either way on b4_c1_256 -- and +1.3 ms/step: the
 # fp16 MFMAs hold a lower clock); default 0: bf16 parts, as in round 3
 SPLIT_GRAD_F16 = _flag("SPLIT_GRAD_F16", False)
-SPLIT_WGRAD_MINW = _flag("SPLIT_WGRAD_MINW", 16)   # 64: the 32- and 16-pixel levels keep the Winograd weight gradients
+SPLIT_WGRAD_MINW = 16                        # the split weight gradient covers the 32- and 16-pixel levels too
 SPLIT_AUTO = _flag("SPLIT", True)          # 0: "auto" never selects the split-bf16 kernel (round-2 dispatch)
 STEM_FUSED = _flag("STEM_FUSED", True)      # 0: the stem takes the direct MFMA kernel + a statistics pass
 
@@ -836,7 +828,7 @@ def conv3x3_fwd_bn_partials(x, pk, norm=None, amax=None):
         require_gpu(z_prev, save)
         zs, zbs = plane(z_prev)
         B, _, H, W = zs.shape
-        nparts = int(_lib.load().onet_conv3x3_split_nparts(B, H, W)) if (FUSE_BN_STATS and not sync_bn()) else 0
+        nparts = int(_lib.load().onet_conv3x3_split_nparts(B, H, W)) if not sync_bn() else 0
         out = torch.empty((B, Co, H, W), dtype=F32, device=zs.device)
         cm = torch.empty((Co, nparts, 3), dtype=F32, device=zs.device) if nparts > 0 else None
         e0 = _prof_begin("conv3x3_split_kernel")
@@ -846,7 +838,7 @@ def conv3x3_fwd_bn_partials(x, pk, norm=None, amax=None):
         _prof_end("conv3x3_split_kernel", 2.0 * B * H * W * Ci * Co * 9, e0, 4.0 * (B * H * W * (Ci + Co) + 9 * Ci * Co))
         return out, cm
     B, _, H, W = x.shape
-    if Ci <= 4 and stem_fused() and FUSE_BN_STATS and not sync_bn() and hasattr(pk, "w"):
+    if Ci <= 4 and stem_fused() and not sync_bn() and hasattr(pk, "w"):
         # the stem (Cin = n_channels): one streaming pass writes z and its statistics records (stem.hip)
         nparts = int(_lib.load().onet_conv3x3_stem_nparts(B, Ci, Co, H, W))
         if nparts > 0:
@@ -863,9 +855,9 @@ def conv3x3_fwd_bn_partials(x, pk, norm=None, amax=None):
             return out, cm
     algo = _fp32_algo(B, Ci, Co, H, W)
     nparts = 0
-    if algo == "winograd4" and FUSE_BN_STATS and not sync_bn():
+    if algo == "winograd4" and not sync_bn():
         nparts = int(_lib.load().onet_conv3x3_winograd4_nparts(B, H, W))
-    if algo == "split" and FUSE_BN_STATS and not sync_bn():
+    if algo == "split" and not sync_bn():
         nparts = int(_lib.load().onet_conv3x3_split_nparts(B, H, W))
         if nparts > 0:
             wq = pk.get_pack(algo)[0]
@@ -989,20 +981,17 @@ def pack3x3_split(w):
     return wf, wd
 
 
-COUNT_FOREACH = _flag("COUNT_FOREACH", True)    # 0 (diagnostic): one add_ launch per BatchNorm counter
-
-
 class counting_batches:
     """Within the block BatchNorm's num_batches_tracked increments (count_batches) are collected and applied in ONE multi-tensor launch
     at the end (also when the block raises: the units that ran have updated their running statistics)."""
 
     def __enter__(self):
         self.outer = getattr(_TLS, "counters", None)
-        _TLS.counters = [] if COUNT_FOREACH else None
+        _TLS.counters = []
         return self
 
     def __exit__(self, *exc):
-        pending, _TLS.counters = _TLS.counters or [], self.outer
+        pending, _TLS.counters = _TLS.counters, self.outer
         by_inc = {}
         for t, n in pending:
             by_inc.setdefault(n, []).append(t)
@@ -1410,8 +1399,6 @@ def norm_on_load_ok(B, Cmid, Cout, H, W, groups):
         return False
     if conv3x3_algo(B, Cmid, Cout, H, W) != "split" or W < SPLIT_WGRAD_MINW:
         return False
-    # every 64-channel output tile of the forward kernel normalises the input tile again: the extra staging work grows with
-    # Cout / 64 while the saved pass does not -- measured worth it up to two output tiles (the 256- and 128-pixel levels)
     if Cout > BN_ON_LOAD_MAX_COUT:
         return False
     if not _lib.load().onet_conv3x3_split_wgrad_ok(B, Cmid, Cout, H, W) or max(Cmid, Cout) * H * W * 4 >= 2 ** 31:
@@ -1509,14 +1496,6 @@ def conv3x3_winograd4_wgrad(x, dz, dw_shape, out=None):
     return dw
 
 
-# WGRAD4 (ONET_FLAGS): "auto" (default) = the F(3x3,4x4) weight gradient where it is the faster one today: layers with at least
-# 256 input channels (or 128 -> >= 256), whose strips are re-read from L2 by many tiles (d2.*, d3.*, d4.*, up1.*, up2.*,
-# up3.c1 of the 256x256 U-Net: 224-298 TF against 205-238); below that its one-unit prefetch does not cover HBM latency
-# (64-channel layers: 130 TF against 200) or it only ties (128 -> 128).
-# "1": wherever legal; "0": never.
-WGRAD4 = _flag("WGRAD4", "auto")
-
-
 def winograd4_wgrad_ok(x, dz):
     B, Cin, H, W = x.shape
     return bool(_lib.load().onet_conv3x3_winograd4_wgrad_ok(B, Cin, dz.shape[1], H, W)) and \
@@ -1529,9 +1508,8 @@ def conv3x3_wgrad_auto(x, dz, dw_shape, out=None, dz_amax=None, x_amax=None):
     if conv_algo() in ("auto", "split", "bf16") and (split_enabled() or conv_algo() == "split") and Cin >= 16 and \
             x.shape[3] >= SPLIT_WGRAD_MINW and split_wgrad_ok(x, dz):
         return conv3x3_split_wgrad(x, dz, dw_shape, out=out, dz_amax=dz_amax if grad_f16() else None, x_amax=x_amax)
-    if use_winograd(Cin, Cout, x.shape[2], x.shape[3]):
-        if WGRAD4 != "0" and winograd4_wgrad_ok(x, dz):
-            return conv3x3_winograd4_wgrad(x, dz, dw_shape, out=out)
+    if use_winograd(Cin, Cout, x.shape[2], x.shape[3]) and winograd4_wgrad_ok(x, dz):
+        return conv3x3_winograd4_wgrad(x, dz, dw_shape, out=out)
     return conv_wgrad(x, dz, dw_shape, 3, out=out)
 
 
