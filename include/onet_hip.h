@@ -253,9 +253,12 @@ int onet_conv3x3_split_wgrad_ok(int B, int Cin, int Cout, int H, int W);
  * mean, invstd, scale, shift as onet_bn_train_coeffs writes them; statistics groups = n_groups equal runs of consecutive
  * images).  The staging threads compute max(fma(z - mean, scale, shift), 0) -- bit for bit what onet_bn_relu_apply writes --
  * before splitting; zero padding stays zero.  _fwd_norm: part != NULL also emits the statistics records (as _fwd_stats);
- * _wgrad_norm: n_groups 1 or 2.  Results are bit-identical to the plain entry points on the materialised activation. */
+ * _wgrad_norm: n_groups 1 or 2.  Results are bit-identical to the plain entry points on the materialised activation.
+ * _fwd_norm with an fp16 pack: x_amax (may be NULL) = magnitude slots bounding the activation (the BatchNorm bound onet_bn_finalize
+ * writes to act_amax), its fp16 range guard as in onet_conv3x3_split_conv_amax. */
 int onet_conv3x3_split_fwd_norm(const float* z_prev, int64_t z_bs, const float* save, int n_groups, const void* wq, int wq_f16,
-                                float* z, int64_t zo_bs, float* part, int B, int Cin, int Cout, int H, int W, void* stream);
+                                const void* x_amax, float* z, int64_t zo_bs, float* part, int B, int Cin, int Cout, int H, int W,
+                                void* stream);
 int onet_conv3x3_split_wgrad_norm(const float* z_prev, int64_t z_bs, const float* save, int n_groups, const float* dz, int64_t dz_bs,
                                   float* dw, void* ws, int64_t ws_bytes, int B, int Cin, int Cout, int H, int W, int accumulate,
                                   void* stream);

@@ -2301,9 +2301,10 @@ int onet_conv3x3_split_wgrad_f16(const float* x, int64_t x_bs, const void* x_ama
 }
 
 int onet_conv3x3_split_fwd_norm(const float* z_prev, int64_t z_bs, const float* save, int n_groups, const void* wq, int wq_f16,
-                                float* z, int64_t zo_bs, float* part, int B, int Cin, int Cout, int H, int W, void* stream) {
+                                const void* x_amax, float* z, int64_t zo_bs, float* part, int B, int Cin, int Cout, int H, int W,
+                                void* stream) {
     ONET_REQUIRE(save, "conv3x3_split_fwd_norm: null pointer");
-    return split_fwd(z_prev, z_bs, wq, z, zo_bs, B, Cin, Cout, H, W, stream, part, wq_f16, save, n_groups);
+    return split_fwd(z_prev, z_bs, wq, z, zo_bs, B, Cin, Cout, H, W, stream, part, wq_f16, save, n_groups, (const unsigned*)x_amax);
 }
 
 int onet_split_pack_act(const float* x, int64_t x_bs, void* xs, int64_t xs_bs, int B, int C, int H, int W, int f16, float scale,

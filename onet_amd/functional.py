@@ -67,7 +67,7 @@ class ConvBNReLUFn(torch.autograd.Function):
         ops.require_gpu(x, weight, gamma, beta)
         if p16 is not None and (p16.get("x") is not None or p16.get("want")):
             return ConvBNReLUFn._forward_pre(ctx, x, weight, gamma, beta, running_mean, running_var, training, momentum, eps, packed,
-                                             groups, link_out, link_in, p16)
+                                             groups, link_out, link_in, p16, aux)
         ctx.pre = False
         # an encoder output that is max-pooled next: a request left in the link dict by UNet.forward (read before the dict is refilled
         # below); the pooled tensor goes back through the same dict for SkipPoolFn
@@ -80,7 +80,7 @@ class ConvBNReLUFn(torch.autograd.Function):
         defer = defer and training and out is None and want_pool is None
         norm = None
         if link_in is not None and link_in.get("deferred"):
-            norm = (link_in["z"], link_in["save"])
+            norm = (link_in["z"], link_in["save"], link_in.get("slots"))
         # the magnitude slots x's producer left on it (ops.tag_amax): the fp16-split kernel's overflow guard
         # (aux: {"x_amax": slots of x or None} in, {"a_amax": slots of the output} out -- DoubleConv._unit tags the tensors)
         x_amax = aux.get("x_amax") if (aux is not None and norm is None) else None
@@ -96,9 +96,11 @@ class ConvBNReLUFn(torch.autograd.Function):
         save_all = torch.empty((G, 4, C), dtype=torch.float32, device=z.device)
         Bz, _, Hz, Wz = z.shape
         pooled = None
-        # magnitude slots of the activation written here (all statistics groups share them), for the convolution that consumes it
+        # magnitude slots of the activation written here (all statistics groups share them), for the convolution that consumes it;
+        # a deferred activation is never written: its BatchNorm bound (from the statistics finalize) guards the consumer's fp16 parts
         a_amax = ops.new_amax(z.device) if (not defer and z.is_cuda and ops.split_f16() and ops.split_enabled()
                                             and ops.conv_algo() in ("auto", "split", "bf16")) else None
+        act_slots = ops.new_amax(z.device) if (defer and ops.split_f16()) else None
         if want_pool is not None and ops.FUSE_POOL and Hz % 2 == 0 and Wz % 4 == 0:
             pooled = (torch.empty((Bz, C, Hz // 2, Wz // 2), dtype=torch.float32, device=z.device), None)
 
@@ -118,7 +120,7 @@ class ConvBNReLUFn(torch.autograd.Function):
         if G == 1:
             if training:
                 ops.bn_train_coeffs(z, gamma, beta, running_mean, running_var, momentum, eps,
-                                    cm=None if cm is None else (cm, 0, cm.shape[1]), save=save_all[0])
+                                    cm=None if cm is None else (cm, 0, cm.shape[1]), save=save_all[0], act_slots=act_slots)
             else:
                 ops.bn_eval_coeffs(gamma, beta, running_mean, running_var, eps, save=save_all[0])
             a = apply(z, save_all[0], dst, slice(0, Bz))
@@ -134,7 +136,7 @@ class ConvBNReLUFn(torch.autograd.Function):
                 zg = z[g * Bg:(g + 1) * Bg]
                 npg = 0 if cm is None else cm.shape[1] // G
                 ops.bn_train_coeffs(zg, gamma, beta, running_mean, running_var, momentum, eps,
-                                    cm=None if cm is None else (cm, g * npg, npg), save=save_all[g])
+                                    cm=None if cm is None else (cm, g * npg, npg), save=save_all[g], act_slots=act_slots)
                 apply(zg, save_all[g], None if defer else a[g * Bg:(g + 1) * Bg], slice(g * Bg, (g + 1) * Bg))
         if aux is not None:
             aux["a_amax"] = a_amax
@@ -154,6 +156,7 @@ class ConvBNReLUFn(torch.autograd.Function):
             link_out.update(z=z, save=save_all)
             if defer:
                 link_out["deferred"] = True
+                link_out["slots"] = act_slots
             ctx.link_out = link_out
         if below[0] is not None:
             ctx.link_in = link_in
@@ -163,7 +166,7 @@ class ConvBNReLUFn(torch.autograd.Function):
 
     @staticmethod
     def _forward_pre(ctx, x, weight, gamma, beta, running_mean, running_var, training, momentum, eps, packed, groups, link_out,
-                     link_in, p16):
+                     link_in, p16, aux=None):
         """Pre-split storage (Settings.presplit).  p16 in: "x" = the pre-split form of x (then the convolution, its input gradient
         and weight gradient run on pre-split operands, ops.pre_layer_ok) or None; "want": write the output activation pre-split
         ("out": its destination, e.g. the skip groups of a concat buffer; else allocated); "keep_fp32": write the fp32 activation too
@@ -176,8 +179,9 @@ class ConvBNReLUFn(torch.autograd.Function):
         x_slots = p16.get("x_slots") if xP is not None else None
         if xP is not None:
             z, cm = ops.conv3x3_pre_bn_partials(xP, packed, x_slots)
-        else:
-            z, cm = ops.conv3x3_fwd_bn_partials(x, packed) if training else (ops.conv3x3_auto(x, packed, 0), None)
+        else:       # (an fp32 x: the magnitude slots its producer left on it, as in forward)
+            x_amax = aux.get("x_amax") if aux is not None else None
+            z, cm = ops.conv3x3_fwd_bn_partials(x, packed, amax=x_amax) if training else (ops.conv3x3_auto(x, packed, 0, amax=x_amax), None)
         G = groups if (training and groups > 1) else 1
         Bz, C, Hz, Wz = z.shape
         Bg = Bz // G

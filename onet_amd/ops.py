@@ -779,7 +779,8 @@ def _fp32_algo(B, Cin, Cout, H, W):
 
 def conv3x3_auto(x, pk, direction, out=None, amax=None):
     """direction 0: forward (Cin -> Cout); 1: dgrad (Cout -> Cin) with the flipped/transposed pack.
-    amax: the 64 magnitude slots of x (int32 [64], written by its producer): what the fp16 split kernels scale x by."""
+    amax: the 64 magnitude slots of x (int32 [64], written by its producer): what the fp16 split kernels scale x by -- computed here
+    (one pass over x) where the fp16-split kernel takes the layer and the caller has none: without them an element >= 65520 is fp16 inf."""
     Ci, Co = (pk["Cin"], pk["Cout"]) if direction == 0 else (pk["Cout"], pk["Cin"])
     shp = x.shape
     algo = _fp32_algo(shp[0], Ci, Co, shp[2], shp[3])
@@ -790,6 +791,8 @@ def conv3x3_auto(x, pk, direction, out=None, amax=None):
     if algo == "winograd4":
         return conv3x3_winograd4(x, wq, Co, out=out)
     if algo == "split":
+        if direction == 0 and amax is None and wq.dtype == torch.float16:
+            amax = absmax_slots(x)
         return conv3x3_split(x, wq, Co, out=out, amax=amax, always=direction == 1)
     return conv_fwd(x, wq, Co, 3, out=out)
 
@@ -820,11 +823,13 @@ def conv3x3_fwd_bn_partials(x, pk, norm=None, amax=None):
     """Forward 3x3 convolution of a Conv-BatchNorm pair (OV:47-48, 51-52): -> (z, cm).  cm = the channel-major
     BatchNorm records [Cout, nparts, 3] the F(4x4) kernel's epilogue emits (image-major: nparts / B per image), or None
     where the selected kernel does not emit them (then `bn_train_coeffs` runs its own statistics pass).
-    norm = (z_prev, save [G, 4, Cin]): normalise on load -- x is NOT read; the input is relu(bn(z_prev)) of the unit below,
-    applied in the split kernel's staging (the caller has checked norm_on_load_ok)."""
+    norm = (z_prev, save [G, 4, Cin], slots): normalise on load -- x is NOT read; the input is relu(bn(z_prev)) of the unit below,
+    applied in the split kernel's staging (the caller has checked norm_on_load_ok); slots: magnitude slots bounding that activation
+    (its BatchNorm bound, bn_train_coeffs' act_slots), the fp16 parts' range guard, or None.
+    amax: the magnitude slots of x; where the fp16-split kernel takes the layer and x has none, they are computed here (one pass)."""
     Ci, Co = pk["Cin"], pk["Cout"]
     if norm is not None:
-        z_prev, save = norm
+        z_prev, save, slots = norm
         require_gpu(z_prev, save)
         zs, zbs = plane(z_prev)
         B, _, H, W = zs.shape
@@ -833,8 +838,9 @@ def conv3x3_fwd_bn_partials(x, pk, norm=None, amax=None):
         cm = torch.empty((Co, nparts, 3), dtype=F32, device=zs.device) if nparts > 0 else None
         e0 = _prof_begin("conv3x3_split_kernel")
         wq = pk.get_pack("split")[0]
-        _lib.call("onet_conv3x3_split_fwd_norm", _p(zs), zbs, _p(save), save.shape[0], _p(wq), int(wq.dtype == torch.float16), _p(out),
-                  Co * H * W, _p(cm), B, Ci, Co, H, W, _stream())
+        f16 = wq.dtype == torch.float16
+        _lib.call("onet_conv3x3_split_fwd_norm", _p(zs), zbs, _p(save), save.shape[0], _p(wq), int(f16), _p(slots) if f16 else None,
+                  _p(out), Co * H * W, _p(cm), B, Ci, Co, H, W, _stream())
         _prof_end("conv3x3_split_kernel", 2.0 * B * H * W * Ci * Co * 9, e0, 4.0 * (B * H * W * (Ci + Co) + 9 * Ci * Co))
         return out, cm
     B, _, H, W = x.shape
@@ -868,6 +874,8 @@ def conv3x3_fwd_bn_partials(x, pk, norm=None, amax=None):
                 xbs = xs.stride(0) if B > 1 else xs[0].numel()
             out = torch.empty((B, Co, H, W), dtype=F32, device=x.device)
             cm = torch.empty((Co, nparts, 3), dtype=F32, device=x.device)
+            if wq.dtype == torch.float16 and amax is None:
+                amax = absmax_slots(xs)
             e0 = _prof_begin("conv3x3_split_kernel")
             if wq.dtype == torch.float16:
                 _lib.call("onet_conv3x3_split_conv_amax", _p(xs), xbs, _p(amax), 0, _p(wq), _p(out), Co * H * W, _p(cm), B, Ci, Co, H, W,
@@ -1052,7 +1060,8 @@ def absmax_slots(x):
 
 def conv3x3_split(x, wq, Cout, out=None, norm=None, amax=None, always=False):
     """z = conv3x3(x) in fp32 accuracy on the 16-bit matrix cores (operands split into two fp16 / bf16 parts, three MFMAs per term).
-    norm = save [G, 4, Cin]: x is a pre-activation; the kernel convolves relu(bn(x)), applied in its staging.
+    norm = save [G, 4, Cin]: x is a pre-activation; the kernel convolves relu(bn(x)), applied in its staging (amax: slots bounding
+    that activation, or None).
     fp16 pack: amax = the magnitude slots of x; always = True (input gradients): x is scaled so that its amax lands in [2^13, 2^14)
     -- the slots are then REQUIRED and computed here when the caller has none; always = False: overflow guard only."""
     if wq is None or not wq.is_cuda or wq.dtype not in (torch.bfloat16, torch.float16):
@@ -1066,7 +1075,7 @@ def conv3x3_split(x, wq, Cout, out=None, norm=None, amax=None, always=False):
         if out is None:
             out = torch.empty((B, Cout, H, W), dtype=F32, device=x.device)
         e0 = _prof_begin("conv3x3_split_kernel")
-        _lib.call("onet_conv3x3_split_fwd_norm", _p(x), xbs, _p(norm), norm.shape[0], _p(wq), f16, _p(out),
+        _lib.call("onet_conv3x3_split_fwd_norm", _p(x), xbs, _p(norm), norm.shape[0], _p(wq), f16, _p(amax) if f16 else None, _p(out),
                   out.stride(0) if B > 1 else Cout * H * W, None, B, Cin, Cout, H, W, _stream())
         _prof_end("conv3x3_split_kernel", 2.0 * B * H * W * Cin * Cout * 9, e0, 4.0 * (B * H * W * (Cin + Cout) + 9 * Cin * Cout))
         return out

@@ -502,6 +502,25 @@ def predict_label(S):
     return torch.argmax(S, dim=1)
 
 
+def calibrated_state(sd, X, bilinear=False):
+    """A copy of the UNet state `sd` whose BatchNorm running statistics are those of ONE fp64 training-mode pass over the calibration
+    input X: running_mean = the batch mean, running_var = the unbiased batch variance of every BatchNorm's input (momentum 1).  What a
+    trained checkpoint holds: an eval forward then keeps its activations at training-mode scale, where the default randomised
+    statistics (det_state_dict) let the deep layers drift far from O(1).  Same dtype as `sd`; num_batches_tracked unchanged."""
+    global BN_MOMENTUM
+    st = OrderedDict((k, v.detach().double() if v.is_floating_point() else v.clone()) for k, v in sd.items())
+    prev, BN_MOMENTUM = BN_MOMENTUM, 1.0
+    try:
+        with torch.no_grad():
+            unet_pass(X.detach().double(), st, training=True, bilinear=bilinear)
+    finally:
+        BN_MOMENTUM = prev
+    out = OrderedDict()
+    for k, v in sd.items():
+        out[k] = st[k].to(v.dtype) if ("running_mean" in k or "running_var" in k) else v.detach().clone()
+    return out
+
+
 def clone_state(sd, requires_grad=True):
     """Fresh leaf tensors from a (un-prefixed) UNet state dict."""
     out = OrderedDict()

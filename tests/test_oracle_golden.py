@@ -108,6 +108,46 @@ def test_eval_mode_matches_reference():
     np.testing.assert_allclose(S.numpy(), g["S"], rtol=1e-4, atol=1e-5)
 
 
+@pytest.mark.parametrize("bilinear", [False, True])
+def test_calibrated_state_eval_equals_training_forward(bilinear):
+    """orc.calibrated_state (the running statistics of a trained checkpoint, for the eval-mode GPU tests): calibrated on the input it
+    then evaluates, the eval forward IS the training forward once the unbiased running variances are scaled back by (N - 1) / N --
+    every BatchNorm then normalises with the batch's own mean and biased variance.  fp64, both U-Net variants."""
+    B, H, W = 2, 32, 40
+    sd = orc.det_state_dict(1, 1981, bilinear=bilinear)
+    X = orc.det_input(B, 1, H, W, seed=5)
+    cal = orc.calibrated_state(sd, X, bilinear=bilinear)
+    assert [k for k in cal] == [k for k in sd]
+    assert all(cal[k].dtype == sd[k].dtype for k in sd)
+    assert all(torch.equal(cal[k], sd[k]) for k in sd if "running" not in k)
+    assert all(not torch.equal(cal[k], sd[k]) for k in sd if "running" in k)
+    # the unbiased batch variances: running_var * (N - 1) / N is the biased variance the training forward normalises with
+    enc, dec = orc.unet_channels(bilinear)
+    size = {"inc": (H, W)}
+    for i, (name, _, _) in enumerate(enc[1:]):
+        size[name] = (H >> (i + 1), W >> (i + 1))
+    for i, (name, _, _, _) in enumerate(dec):
+        size[name] = (H >> (3 - i), W >> (3 - i))
+    st = {}
+    for k, v in cal.items():
+        v = v.double() if v.is_floating_point() else v.clone()
+        if k.endswith("running_var"):
+            h, w = size[k.split(".")[0]]
+            n = B * h * w
+            v = v * ((n - 1) / n)
+        st[k] = v
+    with torch.no_grad():
+        x1e, y1e = orc.unet_pass(X.double(), st, training=False, bilinear=bilinear)
+        x1t, y1t = orc.unet_pass(X.double(), orc.clone_state(st, requires_grad=False), training=True, bilinear=bilinear)
+    for a, b in ((x1e, x1t), (y1e, y1t)):
+        assert float((a - b).abs().max()) <= 1e-5 * float(b.abs().max()), float((a - b).abs().max() / b.abs().max())
+    # ... and not by accident: the default randomised statistics give another function
+    with torch.no_grad():
+        _, y1d = orc.unet_pass(X.double(), {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()},
+                               training=False, bilinear=bilinear)
+    assert float((y1d - y1t).abs().max()) > 0.1 * float(y1t.abs().max())
+
+
 def test_adam_loss_sequence_matches_reference():
     """Harness contract: zero_grad -> fwd -> loss -> bwd -> Adam, 4 steps."""
     g = _load("onet_b2_c1_32_adam4.npz")
