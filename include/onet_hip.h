@@ -234,7 +234,8 @@ int onet_conv3x3_dgrad_bound(const float* w, int Cout, int Cin, int ci0, const v
  * transposing LDS read, staging by LDS-DMA; the producers' power-of-two scales (x_amax: guard rule, dz_amax: always; NULL:
  * unscaled) are undone on the slabs; deterministic split-K through ws
  * (onet_conv3x3_split_wgrad_ws_bytes).  _ok: W >= 64, or W = 32 / 16 with the batch a multiple of 2 / 4; Cin, Cout multiples of 8.
- * _fwd_pre also takes maps exactly 16 pixels wide (even batch, H % 16 == 0): two images side by side per tile. */
+ * _fwd_pre also takes maps exactly 16 pixels wide (even batch, H % 16 == 0): two images side by side per tile; with plain bf16
+ * operands (wq_f16 = 2) it needs W % 4 == 0. */
 int onet_conv3x3_split_pre_nparts(int B, int H, int W);    /* statistics records of _fwd_pre (16-pixel-wide maps: one per image pair) */
 int onet_conv3x3_split_wgrad_pre_ok(int B, int Cin, int Cout, int H, int W);
 int onet_conv3x3_split_wgrad_pre(const void* xs, int64_t xs_bs, const void* x_amax, const void* x_amax2, int split_ch, const void* dzs,

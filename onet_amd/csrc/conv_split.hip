@@ -2335,6 +2335,8 @@ int onet_conv3x3_split_fwd_pre(const void* xs, int64_t xs_bs, const void* x_amax
     ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && (W > 16 || (W == 16 && (B % 2) == 0 && (H % 16) == 0)),
                  "conv3x3_split_fwd_pre: bad shape (maps wider than 16 pixels, or exactly 16 wide with an even batch and H %% 16 == 0)");
     ONET_REQUIRE((Cin % (wq_f16 == 2 ? 32 : 16)) == 0, "conv3x3_split_fwd_pre: Cin must be a multiple of 16 (32 for plain bf16 operands)");
+    // plain bf16 operands take conv3x3_pre16_kernel at every width, and its epilogue stores whole 4-pixel vectors of a row
+    ONET_REQUIRE(wq_f16 != 2 || (W % 4) == 0, "conv3x3_split_fwd_pre: plain bf16 operands need W %% 4 == 0");
     ONET_REQUIRE((xs_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(xs) & 15) == 0, "conv3x3_split_fwd_pre: 16-byte aligned slots required");
     ONET_REQUIRE(xs_bs >= (int64_t)Cin * H * W / (wq_f16 == 2 ? 2 : 1) && z_bs >= (int64_t)Cout * H * W, "conv3x3_split_fwd_pre: batch stride too small");
     ONET_REQUIRE((int64_t)(Cin + 32) * H * W * 4 < (1ll << 31) && (int64_t)(Cin + 32) * 2 * 9 * Cout * 2 < (1ll << 31),

@@ -291,6 +291,20 @@ def _replayed(kind):
     return (None, None) if _ROUNDING_REPLAY is None else _ROUNDING_REPLAY[kind][i]
 
 
+REPLAY_FLOOR = 1e-6      # of the tensor's largest magnitude: elements near zero, where two fp32 evaluations cancel differently
+
+
+def _check_replayed(r, v, what):
+    """A replayed rounding r (the other implementation's stored bf16 operand) must lie within one bf16 ulp of the oracle's own
+    unrounded value v of the same quantity, element by element: a wrong pixel, channel or rounding in a bf16 store would otherwise
+    enter both evaluations and be masked."""
+    v = v.detach()
+    e = torch.frexp(v.abs())[1]                                   # |v| in [2^(e-1), 2^e): one bf16 ulp = 2^(e-8)
+    ulp = torch.where(v == 0, torch.zeros_like(v), torch.ldexp(torch.ones_like(v), e - 8))
+    over = (r.detach().to(v.dtype) - v).abs() - ulp - REPLAY_FLOOR * float(v.abs().max())
+    assert not bool((over > 0).any()), f"replayed {what} {tuple(v.shape)}: {int((over > 0).sum())} elements beyond one bf16 ulp"
+
+
 def _products(sel):
     """rule result -> the set of matrix products evaluated on rounded operands: True = all three"""
     return {"fwd", "dgrad", "wgrad"} if sel is True else set(sel)
@@ -298,11 +312,13 @@ def _products(sel):
 
 class _RoundedConv3x3(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, prods, x_r=None, g_r=None):
+    def forward(ctx, x, w, prods, x_r=None, g_r=None, check=False):
         xr, wr = (_rb(x) if x_r is None else x_r.to(x.dtype)), _rb(w)
         assert xr.shape == x.shape
+        if check and x_r is not None:
+            _check_replayed(xr, x, "conv3x3 input")
         ctx.save_for_backward(x, w, xr, wr)
-        ctx.g_r, ctx.prods = g_r, prods
+        ctx.g_r, ctx.prods, ctx.check = g_r, prods, check
         return F.conv2d(xr, wr, None, 1, 1) if "fwd" in prods else F.conv2d(x, w, None, 1, 1)
 
     @staticmethod
@@ -310,22 +326,26 @@ class _RoundedConv3x3(torch.autograd.Function):
         x, w, xr, wr = ctx.saved_tensors
         gr = _rb(g) if ctx.g_r is None else ctx.g_r.to(g.dtype)
         assert gr.shape == g.shape
+        if ctx.check and ctx.g_r is not None:
+            _check_replayed(gr, g, "conv3x3 output gradient")
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.nn.grad.conv2d_input(x.shape, wr, gr, padding=1) if "dgrad" in ctx.prods else \
                 torch.nn.grad.conv2d_input(x.shape, w, g, padding=1)
         dw = torch.nn.grad.conv2d_weight(xr, w.shape, gr, padding=1) if "wgrad" in ctx.prods else \
             torch.nn.grad.conv2d_weight(x, w.shape, g, padding=1)
-        return dx, dw, None, None, None
+        return dx, dw, None, None, None, None
 
 
 class _RoundedConvT2x2(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, prods, x_r=None, g_r=None):
+    def forward(ctx, x, w, b, prods, x_r=None, g_r=None, check=False):
         xr, wr = (_rb(x) if x_r is None else x_r.to(x.dtype)), _rb(w)
         assert xr.shape == x.shape
+        if check and x_r is not None:
+            _check_replayed(xr, x, "convT2x2 input")
         ctx.save_for_backward(x, w, xr, wr)
-        ctx.g_r, ctx.prods = g_r, prods
+        ctx.g_r, ctx.prods, ctx.check = g_r, prods, check
         return F.conv_transpose2d(xr, wr, b, stride=2) if "fwd" in prods else F.conv_transpose2d(x, w, b, stride=2)
 
     @staticmethod
@@ -333,13 +353,15 @@ class _RoundedConvT2x2(torch.autograd.Function):
         x, w, xr, wr = ctx.saved_tensors
         gr = _rb(g) if ctx.g_r is None else ctx.g_r.to(g.dtype)
         assert gr.shape == g.shape
+        if ctx.check and ctx.g_r is not None:
+            _check_replayed(gr, g, "convT2x2 output gradient")
         # y = convT(x, w)  <=>  x-gradient = conv2d(g, w, stride 2), whose weight gradient (with x as the output gradient) is dW
         dx = F.conv2d(gr, wr, None, 2) if "dgrad" in ctx.prods else F.conv2d(g, w, None, 2)
         dw = torch.nn.grad.conv2d_weight(gr, w.shape, xr, stride=2) if "wgrad" in ctx.prods else \
             torch.nn.grad.conv2d_weight(g, w.shape, x, stride=2)
         # ("dbias": the gradient itself is STORED rounded -- a path that hands the up-sampled half of the concat gradient to the
         # ConvTranspose2d backward as bf16 sums the bias gradient from those values too, as torch.autocast's bf16 grad_output does)
-        return dx, dw, (gr if "dbias" in ctx.prods else g).sum((0, 2, 3)), None, None, None
+        return dx, dw, (gr if "dbias" in ctx.prods else g).sum((0, 2, 3)), None, None, None, None
 
 
 def _conv3x3(x, w):
@@ -347,7 +369,7 @@ def _conv3x3(x, w):
         x_r, g_r = _replayed("conv3x3")
         sel = _ROUNDING_RULE("conv3x3", tuple(x.shape), tuple(w.shape))
         if sel:
-            return _RoundedConv3x3.apply(x, w, _products(sel), x_r, g_r)
+            return _RoundedConv3x3.apply(x, w, _products(sel), x_r, g_r, True)
     return F.conv2d(x, w, None, 1, 1)
 
 
@@ -391,6 +413,8 @@ def _conv_bn_relu(x, st, p, idx, training, routing=None):
     z_r = _stored_z(z, st[f"{p}.{idx}.weight"]) if training else None
     if z_r is not None:
         assert z_r.shape == z.shape
+        if _ROUNDING_REPLAY is not None:
+            _check_replayed(z_r, z, "bn_z")
         with torch.no_grad():       # running statistics: from the exact z, F.batch_norm's update (unbiased variance, momentum 0.1)
             n = z.numel() // z.shape[1]
             st[f"{p}.{b}.running_mean"].mul_(1 - BN_MOMENTUM).add_(BN_MOMENTUM * z.detach().mean((0, 2, 3)))
@@ -420,7 +444,7 @@ def upsample_cat(x1, x2, st, block, bilinear=False):
         x_r, g_r = _replayed("convT2x2") if _ROUNDING_RULE is not None else (None, None)
         sel = _ROUNDING_RULE("convT2x2", tuple(x1.shape), tuple(w.shape)) if _ROUNDING_RULE is not None else False
         if sel:
-            u = _RoundedConvT2x2.apply(x1, w, st[f"{block}.up.bias"], _products(sel), x_r, g_r)
+            u = _RoundedConvT2x2.apply(x1, w, st[f"{block}.up.bias"], _products(sel), x_r, g_r, True)
         else:
             u = F.conv_transpose2d(x1, w, st[f"{block}.up.bias"], stride=2)
     dy = x2.shape[2] - u.shape[2]

@@ -409,7 +409,9 @@ def test_bf16_path_every_gradient_element_vs_routed_rounded_oracle(dev, tag, mon
     unrounded (oracle.operand_rounding) -- under the HIP run's DECISIONS: its ReLU masks and pooling indices, and its roundings.
     The roundings must be replayed for the same reason as the masks: free rounding is chaotic (the oracle's note; the test
     measures it: with free rounding the two evaluations differ by ~1e-2 of the head logits' scale), while on the same rounded
-    operands the two differ by fp32 summation only."""
+    operands the two differ by fp32 summation only.  Every replayed tensor (bn_z, conv3x3 and convT2x2 operands) must lie within
+    one bf16 ulp of the oracle's own unrounded value, element by element (oracle._check_replayed): otherwise a wrong pixel,
+    channel or rounding in a bf16 store would enter both evaluations and be masked."""
     from onet_amd import ops
     B, C, H, W, gain, _ = CASES[tag]
     monkeypatch.setattr(ops, "CONV_ALGO", "bf16")

@@ -151,6 +151,12 @@ def test_conv3x3_split_presplit_kernels(dev, B, Cin, Cout, H, W):
         ref = ops.conv3x3_split(x, qf, Cout)
         got = ops.conv3x3_split_pre(ops.split_pack_act(x, f16=True), qf, Cout)
         assert torch.equal(ref, got), float((ref - got).abs().max())
+        with ops.using(ops.Settings(conv="auto", split_f16=False, grad_f16=False)):
+            qb, _ = ops.pack3x3_split(w)
+        assert qb.dtype == torch.bfloat16
+        ref = ops.conv3x3_split(x, qb, Cout)
+        got = ops.conv3x3_split_pre(ops.split_pack_act(x, f16=False), qb, Cout)
+        assert torch.equal(ref, got), ("bf16 parts", float((ref - got).abs().max()))
     if W == 16:
         # maps 16 pixels wide (two images side by side per tile; the fp32-operand split kernel has no such variant): against fp64,
         # forward with the statistics epilogue == the separate statistics pass, and the input-gradient orientation
@@ -904,8 +910,9 @@ def test_cpu_tensor_is_refused():
 
 
 def test_conv_kernels_random_shapes_fuzz(dev):
-    """40 random layer shapes (ragged maps down to 1x1, odd batches, channel counts off the 32/64 tile grid) through all
-    four 3x3 kernels -- direct, F(2x2,3x3), F(4x4,3x3), and both weight-gradient kernels -- against the CPU convolution."""
+    """40 random layer shapes (ragged maps down to 1x1, odd batches, channel counts off the 32/64 tile grid) through the direct
+    kernels (forward, input gradient, weight gradient) and F(4x4,3x3) (forward, input gradient) against the CPU convolution.
+    The split kernels the default path runs have their own fuzz over each entry's domain: test_gpu_presplit_kernels.py."""
     from onet_amd import ops
     rng = np.random.default_rng(20240606)
     for it in range(40):
