@@ -397,6 +397,11 @@ int onet_bn_bwd_bound(const float* save, const float* coef, const void* da_amax,
 int onet_bn_relu_bwd_apply_split(const float* da, int64_t da_bs, const void* z, int z_bf16, int64_t z_bs, const float* save, const float* coef,
                                  void* dzs, int64_t dzs_bs, const void* dz_amax, int nparts, int group_images, int B, int C, int H, int W,
                                  void* stream);
+/* the same pass with da = g[b][p] * L[b][c][p] formed on load (fp32 z; g: onet_head_grad_map's map [B][HW]; the product is rounded to
+ * fp32 first: the bits of the pass fed the stored tensor) */
+int onet_bn_relu_bwd_apply_split_gl(const float* L, int64_t L_bs, const float* g, const float* z, int64_t z_bs, const float* save,
+                                    const float* coef, void* dzs, int64_t dzs_bs, const void* dz_amax, int nparts, int group_images, int B, int C,
+                                    int H, int W, void* stream);
 
 /* ---- K4: MaxPool2d(2) (OV:67) ------------------------------------------- */
 int onet_maxpool2_fwd(const float* x, int64_t x_bs, float* y, int64_t y_bs,
@@ -463,6 +468,16 @@ int onet_head_softmax_bwd(const float* dVt, const float* dVd, const float* dS, c
                           const float* Lt, int64_t Lt_bs, const float* Ht, int64_t Ht_bs, const float* Ld, int64_t Ld_bs, const float* Hd,
                           int64_t Hd_bs, float* dLt, float* dHt, float* dLd, float* dHd, const float* h_save_t, const float* h_save_d, int B,
                           int C, int HW, void* stream);
+
+/* The twin head's backward with the last unit's BatchNorm-backward reduce fused in (training, h_save_* form of the head):
+ * onet_head_grad_map writes the per-pixel gradients g[2B][HW] (top half gt, down half gd; onet_head_softmax_bwd's expressions, dVt /
+ * dVd / dS nullable); onet_head_bwd_reduce then reads L and the unit's pre-activation z [B = 2 x half batch][C][HW] once, writes
+ * dL = g H + gsL (onet_head_softmax_bwd's bits) and -- instead of dH = g L -- the unit's reduce records [nparts][C][4] and max |dH|
+ * (da_amax, nullable) exactly as onet_bn_relu_bwd_reduce would from the stored dH (save [2][4][C], group = half batch; nparts as
+ * there).  dH is never written: onet_bn_relu_bwd_apply_split_gl forms it on load (below). */
+int onet_head_grad_map(const float* dVt, const float* dVd, const float* dS, const float* S, float* g, int B, int HW, void* stream);
+int onet_head_bwd_reduce(const float* L, int64_t L_bs, const float* z, int64_t z_bs, const float* g, const float* gsLt, const float* gsLd,
+                         const float* save, float* dL, float* part2, int nparts, void* da_amax, int B, int C, int HW, void* stream);
 
 /* ---- K10: JSD loss with the reference's log1pexp quirk (OV:221-267) ---------- */
 /* One jsd term, Onet.jensen_shannon_divergence(Li, Si, Sprime) (OV:221-235):

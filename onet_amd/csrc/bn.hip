@@ -561,11 +561,15 @@ __global__ __launch_bounds__(256) void bn_relu_apply_pool_split_kernel(const ZT*
 // BEFORE this pass; the consumers read the same slots and undo 2^k on their accumulators).  8 channels x 4 pixels per thread.
 // blocks per CU with a bf16 `z`: kept packed in registers until use, it fits a fourth block (126 VGPRs); the fp32 form spills at four
 constexpr int BN_BWD_OCC16 = 4;
-template <typename ZT = float>
+// GL (the network's last unit behind the fused head backward): da = g L is formed on load -- `da` points at L, `gmap` at the head's
+// per-pixel gradient map g[B][HW] (one float4 of it per thread serves its eight channels), the product rounded to fp32 as the stored
+// tensor was: the same dz bits as the pass fed a materialised da, which is then never written.
+template <typename ZT = float, bool GL = false>
 __global__ __launch_bounds__(256, sizeof(ZT) == 2 ? BN_BWD_OCC16 : 3) void bn_relu_bwd_apply_split_kernel(const float* __restrict__ da, int64_t da_bs, const ZT* __restrict__ z,
                                                                       int64_t z_bs, const float* __restrict__ save, const float* __restrict__ coef,
                                                                       unsigned* __restrict__ dzs, int64_t dzs_bs, const unsigned* __restrict__ slots,
-                                                                      int C, int H, int W, int bpp, int np, int gimg) {
+                                                                      int C, int H, int W, int bpp, int np, int gimg,
+                                                                      const float* __restrict__ gmap = nullptr) {
     float inv;
     const float s = np == 1 ? 1.f : amax_scale(amax_read(slots), true, inv);     // (plain bf16: fp32's exponent range, no scale)
     const int plane = blockIdx.x / bpp, blk = blockIdx.x % bpp;
@@ -584,6 +588,10 @@ __global__ __launch_bounds__(256, sizeof(ZT) == 2 ? BN_BWD_OCC16 : 3) void bn_re
     constexpr bool Z16 = sizeof(ZT) == 2;
     typename std::conditional<Z16, uint2, float4>::type zq[8];
     float4 gq[8];
+    float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (GL) {
+        if (live) g4 = *reinterpret_cast<const float4*>(gmap + (int64_t)b * HW + p);
+    }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {                 // all sixteen loads in flight before the first use
         if constexpr (Z16) zq[k] = live ? *reinterpret_cast<const uint2*>(zs + (int64_t)k * HW) : make_uint2(0u, 0u);
@@ -604,7 +612,10 @@ __global__ __launch_bounds__(256, sizeof(ZT) == 2 ? BN_BWD_OCC16 : 3) void bn_re
         } else {
             zz[0] = zq[k].x; zz[1] = zq[k].y; zz[2] = zq[k].z; zz[3] = zq[k].w;
         }
-        const float gg[4] = {gq[k].x, gq[k].y, gq[k].z, gq[k].w};
+        float gg[4] = {gq[k].x, gq[k].y, gq[k].z, gq[k].w};
+        if constexpr (GL) {
+            gg[0] *= g4.x; gg[1] *= g4.y; gg[2] *= g4.z; gg[3] *= g4.w;
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const double dy = fmaf(zz[e] - mean, sc, sh) > 0.f ? (double)gg[e] : 0.0;
@@ -699,6 +710,79 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(const float* __
     block_sum_256<double, 2>(v, red);
     if (threadIdx.x == 0) {
         // two floats per sum (hi + lo) keep ~48 bits through the float partial buffer
+        float* o = part2 + ((int64_t)p * C + c) * 4;
+        o[0] = (float)v[0];
+        o[1] = (float)(v[0] - (double)o[0]);
+        o[2] = (float)v[1];
+        o[3] = (float)(v[1] - (double)o[2]);
+    }
+}
+
+// The twin head's backward with the LAST unit's BatchNorm-backward reduce riding in it (H = relu(bn(z)) of that unit, formed on load
+// as in head_softmax_bwd_kernel; g = the head's per-pixel gradient map [B][HW], at = d loss / d sum_c L, top / down half or NULL):
+//   dL = fma(g, H, at)   written (head_softmax_bwd_kernel's bits);
+//   dH = g L             NOT written: it is the unit's da, summed here as bn_relu_bwd_reduce_kernel sums a stored da -- same blocks,
+//                        same order, fp64, same records (hi, lo, hi, lo) and max |da| -- and formed again on load by the apply pass.
+// Plane-oriented like the reduce pass (channel fastest in blockIdx: concurrent blocks share a chunk of g and at in L2); per thread
+// eight 16-byte loads of L and z plus the eight of the maps in flight.  HW, the batch strides and chunk_len are multiples of 4.
+__global__ __launch_bounds__(256) void head_bwd_reduce_kernel(const float* __restrict__ L, int64_t L_bs, const float* __restrict__ z,
+                                                              int64_t z_bs, const float* __restrict__ g, const float* __restrict__ at_t,
+                                                              const float* __restrict__ at_d, const float* __restrict__ save,
+                                                              float* __restrict__ dL, float* __restrict__ part2, int C, int HW, int chunks,
+                                                              int chunk_len, unsigned* __restrict__ amax, int gimg) {
+    __shared__ double red[8];
+    float vmax = 0.f;
+    const int c = blockIdx.x % C;
+    const int p = blockIdx.x / C;
+    const int b = p / chunks, ch = p % chunks;
+    save += (int64_t)(b / gimg) * 4 * C;                  // the two statistics groups: save [2][4][C]
+    const float mean = save[c], invstd = save[C + c], sc = save[2 * C + c], sh = save[3 * C + c];
+    const double meand = mean, invd = invstd;
+    const float* zs = z + (int64_t)b * z_bs + (int64_t)c * HW;
+    const float* ls = L + (int64_t)b * L_bs + (int64_t)c * HW;
+    const float* gs = g + (int64_t)b * HW;
+    const float* as = b < gimg ? at_t : at_d;             // (NULL: no gradient came through the channel sums)
+    if (as) as += (int64_t)(b % gimg) * HW;
+    float* os = dL + ((int64_t)b * C + c) * HW;
+    const int beg = ch * chunk_len, end = min(beg + chunk_len, HW);
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    double v[2] = {0.0, 0.0};
+    auto four = [&](const float4& q, const float4& l, const float4& gv, const float4& av) -> float4 {
+        const float zz[4] = {q.x, q.y, q.z, q.w}, ll[4] = {l.x, l.y, l.z, l.w}, gg[4] = {gv.x, gv.y, gv.z, gv.w}, aa[4] = {av.x, av.y, av.z, av.w};
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float x = fmaf(zz[e] - mean, sc, sh);
+            o[e] = fmaf(gg[e], fmaxf(x, 0.f), aa[e]);
+            const float da = gg[e] * ll[e];               // rounded to fp32, as the stored tensor was
+            const double dy = x > 0.f ? (double)da : 0.0;
+            v[0] += dy;
+            v[1] += dy * (((double)zz[e] - meand) * invd);
+            vmax = fmaxf(vmax, fabsf(da));
+        }
+        return make_float4(o[0], o[1], o[2], o[3]);
+    };
+    int i = beg + threadIdx.x * 4;
+    for (; i + 3072 < end; i += 4096) {           // bn_relu_bwd_reduce_kernel's summation order
+        float4 q[4], l[4], gv[4], av[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            q[k] = *reinterpret_cast<const float4*>(zs + i + 1024 * k);
+            l[k] = *reinterpret_cast<const float4*>(ls + i + 1024 * k);
+            gv[k] = *reinterpret_cast<const float4*>(gs + i + 1024 * k);
+            av[k] = as ? *reinterpret_cast<const float4*>(as + i + 1024 * k) : zero4;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(os + i + 1024 * k) = four(q[k], l[k], gv[k], av[k]);
+    }
+    for (; i < end; i += 1024) {
+        const float4 q = *reinterpret_cast<const float4*>(zs + i), l = *reinterpret_cast<const float4*>(ls + i);
+        const float4 gv = *reinterpret_cast<const float4*>(gs + i), av = as ? *reinterpret_cast<const float4*>(as + i) : zero4;
+        *reinterpret_cast<float4*>(os + i) = four(q, l, gv, av);
+    }
+    amax_commit(vmax, amax);
+    block_sum_256<double, 2>(v, red);
+    if (threadIdx.x == 0) {
         float* o = part2 + ((int64_t)p * C + c) * 4;
         o[0] = (float)v[0];
         o[1] = (float)(v[0] - (double)o[0]);
@@ -1033,6 +1117,37 @@ int onet_bn_relu_bwd_apply_split(const float* da, int64_t da_bs, const void* z, 
     else
         hipLaunchKernelGGL(bn_relu_bwd_apply_split_kernel<float>, dim3((unsigned)blocks), dim3(256), bn_tr_bytes(nparts), as_stream(stream), da, da_bs,
                            (const float*)z, z_bs, save, coef, (unsigned*)dzs, dzs_bs, (const unsigned*)dz_amax, C, H, W, bpp, nparts, group_images);
+    return check_launch("bn_relu_bwd_apply_split_kernel");
+}
+
+int onet_head_bwd_reduce(const float* L, int64_t L_bs, const float* z, int64_t z_bs, const float* g, const float* gsLt, const float* gsLd,
+                         const float* save, float* dL, float* part2, int nparts, void* da_amax, int B, int C, int HW, void* stream) {
+    ONET_REQUIRE(L && z && g && save && dL && part2 && B > 0 && (B % 2) == 0 && C > 0 && HW > 0, "head_bwd_reduce: bad args (B = images of the twin batch)");
+    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    ONET_REQUIRE((HW & 3) == 0 && (L_bs & 3) == 0 && (z_bs & 3) == 0 && al(L) && al(z) && al(g) && al(gsLt) && al(gsLd) && al(dL),
+                 "head_bwd_reduce: HW %% 4 == 0 and 16-byte aligned rows required");
+    int chunks, chunk_len;
+    ONET_REQUIRE(split_plan(nparts, B, HW, chunks, chunk_len), "head_bwd_reduce: nparts=%d must be a multiple of B=%d", nparts, B);
+    ONET_REQUIRE((int64_t)nparts * C < (1ll << 31), "head_bwd_reduce: grid too large");
+    hipLaunchKernelGGL(head_bwd_reduce_kernel, dim3((unsigned)((int64_t)nparts * C)), dim3(256), 0, as_stream(stream), L, L_bs, z, z_bs, g, gsLt,
+                       gsLd, save, dL, part2, C, HW, chunks, chunk_len, (unsigned*)da_amax, B / 2);
+    return check_launch("head_bwd_reduce_kernel");
+}
+
+int onet_bn_relu_bwd_apply_split_gl(const float* L, int64_t L_bs, const float* g, const float* z, int64_t z_bs, const float* save,
+                                    const float* coef, void* dzs, int64_t dzs_bs, const void* dz_amax, int nparts, int group_images, int B, int C,
+                                    int H, int W, void* stream) {
+    ONET_REQUIRE(nparts == 1 || nparts == 2, "bn_relu_bwd_apply_split_gl: nparts must be 2 (fp16 hi | mid) or 1 (plain bf16)");
+    ONET_REQUIRE(L && g && z && save && dzs && (dz_amax || nparts == 1) && B > 0 && C > 0 && (C % 8) == 0 && H > 0 && W > 0 && (W % 4) == 0,
+                 "bn_relu_bwd_apply_split_gl: bad args");
+    ONET_REQUIRE((reinterpret_cast<uintptr_t>(dzs) & 15) == 0 && (dzs_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && (z_bs & 3) == 0 &&
+                 (reinterpret_cast<uintptr_t>(L) & 15) == 0 && (L_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(g) & 15) == 0,
+                 "bn_relu_bwd_apply_split_gl: 16-byte aligned rows and slots required");
+    const int bpp = cdiv((int64_t)H * W, 1024);
+    const int64_t blocks = (int64_t)B * (C / 8) * bpp;
+    ONET_REQUIRE(blocks < (1ll << 31) && (int64_t)H * W < (1 << 24), "bn_relu_bwd_apply_split_gl: grid too large");
+    hipLaunchKernelGGL((bn_relu_bwd_apply_split_kernel<float, true>), dim3((unsigned)blocks), dim3(256), bn_tr_bytes(nparts), as_stream(stream), L, L_bs,
+                       z, z_bs, save, coef, (unsigned*)dzs, dzs_bs, (const unsigned*)dz_amax, C, H, W, bpp, nparts, group_images, g);
     return check_launch("bn_relu_bwd_apply_split_kernel");
 }
 

@@ -81,6 +81,23 @@ __global__ __launch_bounds__(256) void head_softmax_fwd_kernel(const float* __re
     }
 }
 
+// d loss / d Vt, d loss / d Vd of pixel i = (b, p) from the upstream gradients of Vt, Vd and S (each may be NULL)
+__device__ __forceinline__ void head_px_grad(const float* __restrict__ dVt, const float* __restrict__ dVd, const float* __restrict__ dS,
+                                             const float* __restrict__ S, int64_t i, int b, int p, int HW, float& gt, float& gd) {
+    gt = dVt ? dVt[i] : 0.f;
+    gd = dVd ? dVd[i] : 0.f;
+    if (dS) {
+        const float st = S[((int64_t)b * 2 + 0) * HW + p], sd = S[((int64_t)b * 2 + 1) * HW + p];
+        const float a = dS[((int64_t)b * 2 + 0) * HW + p], d = dS[((int64_t)b * 2 + 1) * HW + p];
+        // 2-class softmax backward in its cancellation-free form: with St + Sd = 1,
+        // St*(a - (a*St + d*Sd)) == St*Sd*(a - d) and the Vd component is its negative.
+        // (the textbook form loses everything once St rounds to 1, which it does at init: |V| ~ 47)
+        const float t = st * sd * (a - d);
+        gt += t;
+        gd -= t;
+    }
+}
+
 __global__ __launch_bounds__(256) void head_softmax_bwd_kernel(
     const float* __restrict__ dVt, const float* __restrict__ dVd, const float* __restrict__ dS,
     const float* __restrict__ S, const float* __restrict__ Lt, int64_t Lt_bs, const float* __restrict__ Ht,
@@ -93,17 +110,8 @@ __global__ __launch_bounds__(256) void head_softmax_bwd_kernel(
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int b = (int)(i / HW);
         const int p = (int)(i % HW);
-        float gt = dVt ? dVt[i] : 0.f, gd = dVd ? dVd[i] : 0.f;
-        if (dS) {
-            const float st = S[((int64_t)b * 2 + 0) * HW + p], sd = S[((int64_t)b * 2 + 1) * HW + p];
-            const float a = dS[((int64_t)b * 2 + 0) * HW + p], d = dS[((int64_t)b * 2 + 1) * HW + p];
-            // 2-class softmax backward in its cancellation-free form: with St + Sd = 1,
-            // St*(a - (a*St + d*Sd)) == St*Sd*(a - d) and the Vd component is its negative.
-            // (the textbook form loses everything once St rounds to 1, which it does at init: |V| ~ 47)
-            const float t = st * sd * (a - d);
-            gt += t;
-            gd -= t;
-        }
+        float gt, gd;
+        head_px_grad(dVt, dVd, dS, S, i, b, p, HW, gt, gd);
         const float* lt = Lt + b * Lt_bs + p;
         const float* ht = Ht + b * Ht_bs + p;
         const float* ld = Ld + b * Ld_bs + p;
@@ -125,6 +133,20 @@ __global__ __launch_bounds__(256) void head_softmax_bwd_kernel(
             old_[o] = fmaf(gd, h2, ad);
             ohd[o] = gd * ld[o];
         }
+    }
+}
+
+// The per-pixel head gradients as a map g[2B][HW] (top half gt, down half gd: the twin batch's image order) for the fused head
+// backward (bn.hip: head_bwd_reduce_kernel) and the last unit's apply pass, which form dL = g H + at and dH = g L from it.
+__global__ __launch_bounds__(256) void head_grad_map_kernel(const float* __restrict__ dVt, const float* __restrict__ dVd,
+                                                            const float* __restrict__ dS, const float* __restrict__ S,
+                                                            float* __restrict__ g, int B, int HW) {
+    const int64_t n = (int64_t)B * HW;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float gt, gd;
+        head_px_grad(dVt, dVd, dS, S, i, (int)(i / HW), (int)(i % HW), HW, gt, gd);
+        g[i] = gt;
+        g[n + i] = gd;
     }
 }
 
@@ -231,6 +253,12 @@ int onet_head_softmax_bwd(const float* dVt, const float* dVd, const float* dS, c
     hipLaunchKernelGGL(head_softmax_bwd_kernel, dim3(grid_px((int64_t)B * HW)), dim3(256), 0, as_stream(stream), dVt,
                        dVd, dS, S, Lt, Lt_bs, Ht, Ht_bs, Ld, Ld_bs, Hd, Hd_bs, dLt, dHt, dLd, dHd, gsLt, gsLd, h_save_t, h_save_d, B, C, HW);
     return check_launch("head_softmax_bwd_kernel");
+}
+
+int onet_head_grad_map(const float* dVt, const float* dVd, const float* dS, const float* S, float* g, int B, int HW, void* stream) {
+    ONET_REQUIRE(g && (S || !dS) && B > 0 && HW > 0, "head_grad_map: bad args");
+    hipLaunchKernelGGL(head_grad_map_kernel, dim3(grid_px((int64_t)B * HW)), dim3(256), 0, as_stream(stream), dVt, dVd, dS, S, g, B, HW);
+    return check_launch("head_grad_map_kernel");
 }
 
 int onet_jsd_nparts(void) { return JSD_BLOCKS; }

@@ -226,6 +226,9 @@ class ConvBNReLUFn(torch.autograd.Function):
         gi = Bg if G > 1 else 0
         if defer_head:
             head["z"], head["save"] = z, save_all
+            # (the head's backward may then keep dH = g L unwritten and hand this unit the reduce records instead: _backward_pre takes
+            # that hand-off only on its pre-split branch)
+            head["bwd_fuse"] = xP is not None
             a_amax = None
         elif pooled is not None:
             if not ops.bn_relu_apply_pool_split(z, save_all, aP, a if keep else None, pooled[2], pooled[0], slots=act_slots, group_images=gi):
@@ -241,6 +244,7 @@ class ConvBNReLUFn(torch.autograd.Function):
         ctx.up_link = p16.get("up_link")
         ctx.up_want = None if ctx.up_link is None else ctx.up_link.get("want")
         ctx.twin = ops.twin_src_of(x)       # a virtual twin batch (placeholder + (X, bias)): backward re-attaches the tag
+        ctx.head_link = head if defer_head else None      # (every backward of the head publishes in it anew: kept on this node)
         # the unit below's (z, save): saved tensors of this node (see ConvBNReLUFn.forward)
         below = (link_in.pop("z"), link_in.pop("save")) if (training and link_in is not None and "z" in link_in) else (None, None)
         ctx.save_for_backward(x, z, save_all, xP, *below)
@@ -269,6 +273,20 @@ class ConvBNReLUFn(torch.autograd.Function):
         return x
 
     @staticmethod
+    def _take_head_handoff(link, da):
+        """What the fused head backward (HeadSoftmaxTwinFn.backward) left for the network's last unit: (rec4, da_amax, (g, L)) or None.
+        The unit's da = g L then exists nowhere, so `da` must be the placeholder the head returned for it -- under the identity check
+        of the other hand-offs; anything else (the activation got a second consumer, whose gradient autograd added) is refused: there
+        is no tensor to fall back on."""
+        if link is None or "gl" not in link:
+            return None
+        rda, rec4, da_amax, gl = link.pop("da"), link.pop("rec4"), link.pop("da_amax", None), link.pop("gl")
+        if not ops.is_placeholder(da) or rda.data_ptr() != da.data_ptr() or rda.shape != da.shape or rda.stride() != da.stride():
+            raise RuntimeError("onet_amd: the head kept the gradient of the last activation unwritten, but autograd handed its unit "
+                               "another tensor (a second consumer of that activation?)")
+        return rec4, da_amax, gl
+
+    @staticmethod
     def _backward_pre(ctx, da):
         x, z, save_all, xP, z_below, save_below = ctx.saved_tensors
         x = ConvBNReLUFn._retag_twin(ctx, x)
@@ -283,6 +301,12 @@ class ConvBNReLUFn(torch.autograd.Function):
             lk.pop("rec", None)
             if rda.data_ptr() != da.data_ptr() or rda.shape != da.shape or rda.stride() != da.stride():
                 rec4 = da_amax = None
+        # the network's last unit behind the fused head backward: da = g L was never written (`da` is its placeholder); the records
+        # and max |da| came with (g, L), from which the apply pass forms it
+        da_gl = None
+        hand = ConvBNReLUFn._take_head_handoff(getattr(ctx, "head_link", None), da)
+        if hand is not None:
+            rec4, da_amax, da_gl = hand
         nones = (None,) * 12
         if xP is None:
             # fp32 input (the stem): dz in fp32 for the fp32-input kernels; no input gradient path on pre-split operands
@@ -296,7 +320,7 @@ class ConvBNReLUFn(torch.autograd.Function):
             dx = ops.conv3x3_auto(dz, ctx.packed, 1) if need_x else None
             return (dx, dw, (dgamma if need_g else None), (dbeta if need_b else None)) + nones
         dzP, dz_slots, dgamma, dbeta = ops.bn_relu_bwd_split(da, z, save_all, ctx.training, need_affine_grads=(need_g or need_b),
-                                                             affine_out=aff, rec4=rec4, da_amax=da_amax)
+                                                             affine_out=aff, rec4=rec4, da_amax=da_amax, da_gl=da_gl)
         s1, s2, sc = ops._slots3(getattr(ctx, "x_slots", None))
         dw = ops.conv3x3_split_wgrad_pre(xP, dzP, ctx.wshape, out=ops.grad_slot_if_free(pw), x_slots=s1, dz_slots=dz_slots, x_slots2=s2,
                                          split_ch=sc) if need_w else None
@@ -723,10 +747,14 @@ class HeadSoftmaxTwinFn(torch.autograd.Function):
         (H is a placeholder): the head normalises and rectifies z on load -- the same bits -- in forward and backward."""
         B = L.shape[0] // 2
         ctx.h_save = None
+        ctx.unit_link = None
         if head_link is not None and "z" in head_link:
             z, save = head_link.pop("z"), head_link.pop("save")
             assert z.shape == H.shape and z.dtype == torch.float32 and save.shape[0] == 2
             ctx.h_save = save
+            # the unit can take dH = g L unwritten (its placeholder H has this one reader, so its gradient arrives there as returned here)
+            if head_link.pop("bwd_fuse", False) and ops.is_placeholder(H):
+                ctx.unit_link = head_link
             H = z
         elif ops.is_placeholder(H):
             raise RuntimeError("onet_amd: the head received a placeholder for the last activation without its pre-activation")
@@ -739,6 +767,16 @@ class HeadSoftmaxTwinFn(torch.autograd.Function):
     def backward(ctx, dVt, dVd, dS, gsLt, gsLd):
         L, H, S = ctx.saved_tensors
         B = L.shape[0] // 2
+        lk = ctx.unit_link
+        if lk is not None and ops.HEAD_BWD_FUSE and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and ops.head_bwd_fuse_ok(L, H):
+            # one pass over L and z writes dL and sums dH = g L into the last unit's BatchNorm-backward records; that unit gets a
+            # placeholder for dH and forms it on load from (g, L)
+            g = ops.head_grad_map(dVt, dVd, dS, S)
+            dL, rec4, da_amax = ops.head_bwd_reduce(g, (gsLt, gsLd), L, H, ctx.h_save, want_amax=ops.p16_parts() == 2)
+            dH = ops.fp32_placeholder(H.shape, H.device)
+            lk.clear()
+            lk.update(da=dH, rec4=rec4, da_amax=da_amax, gl=(g, L))
+            return dL, dH, None
         nrm = None if ctx.h_save is None else (ctx.h_save[0], ctx.h_save[1])
         dL, dH = ops.head_softmax_bwd(dVt, dVd, dS, S, L[:B], H[:B], L[B:], H[B:], twin=True, gsums=(gsLt, gsLd), h_norm=nrm)
         return dL, dH, None

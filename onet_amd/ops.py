@@ -1326,13 +1326,22 @@ def _bn_bwd_groups(da, dabs, z, zbs, save_all, training, affine_out, rec4, da_am
     return coef, dgamma, dbeta
 
 
-def bn_relu_bwd_split(da, z, save_all, training, need_affine_grads=True, affine_out=None, rec=None, rec4=None, da_amax=None):
+def bn_relu_bwd_split(da, z, save_all, training, need_affine_grads=True, affine_out=None, rec=None, rec4=None, da_amax=None, da_gl=None):
     """BatchNorm + ReLU backward of a layer whose dz is consumed by the pre-split kernels, all statistics groups of the tensor per
     launch: the reduce pass (also recording max |da|, unless the records -- and da's magnitude slots -- came fused from da's producer),
     then the finalize pass, which also writes the bound of |dz| into fresh magnitude slots, then dz written pre-split, scaled by the
     power of two those slots select.  Plain bf16 operands (conv == "bf16", one part): no magnitudes, no scale.
+    da_gl = (g, L) (the network's last unit behind the fused head backward, head_bwd_reduce, which also wrote rec4 and da_amax): da is
+    g[b, 0, y, x] * L[b, c, y, x] and exists nowhere -- `da` is its placeholder -- the apply pass forms it on load.
     -> (dzP, dz_slots | None, dgamma, dbeta)."""
-    da, dabs = plane(da)
+    if da_gl is not None:
+        if rec4 is None or _z16(z) or (p16_parts() == 2 and da_amax is None):
+            raise RuntimeError("onet_amd: a BatchNorm backward on an unmaterialised g * L needs the records of the fused head backward")
+        gmap = da_gl[0]
+        da, dabs = plane(da_gl[1])
+        assert gmap.is_contiguous() and gmap.shape[0] == z.shape[0] and gmap.numel() == z.shape[0] * z.shape[2] * z.shape[3] and da.shape == z.shape
+    else:
+        da, dabs = plane(da)
     z, zbs = plane(z)
     B, C, H, W = z.shape
     G = save_all.shape[0]
@@ -1346,6 +1355,10 @@ def bn_relu_bwd_split(da, z, save_all, training, need_affine_grads=True, affine_
     if rec4 is None:
         da_amax = new_amax(dev) if scaled else None
     coef, dgamma, dbeta = _bn_bwd_groups(da, dabs, z, zbs, save_all, training, affine_out, rec4, da_amax, dz_slots)
+    if da_gl is not None:
+        _lib.call("onet_bn_relu_bwd_apply_split_gl", _p(da), dabs, _p(gmap), _p(z), zbs, _p(save_all), _p(coef), _p(dzP), _pbs(dzP), _p(dz_slots), np_,
+                  B // G if G > 1 else 0, B, C, H, W, _stream(), nbytes=(8 + 2 * np_) * z.numel() + 4 * gmap.numel())
+        return dzP, dz_slots, dgamma, dbeta
     _lib.call("onet_bn_relu_bwd_apply_split", _p(da), dabs, _p(z), _z16(z), zbs, _p(save_all), _p(coef), _p(dzP), _pbs(dzP), _p(dz_slots), np_,
               B // G if G > 1 else 0, B, C, H, W, _stream(), nbytes=(4 + z.element_size() + 2 * np_) * z.numel())
     return dzP, dz_slots, dgamma, dbeta
@@ -1968,6 +1981,60 @@ def head_softmax_bwd(dVt, dVd, dS, S, Lt, Ht, Ld, Hd, twin=False, gsums=(None, N
               _p(Ld), c, _p(Hd), d, _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(nt), _p(nd), B, C, H * W, _stream(),
               nbytes=32 * Lt.numel())
     return (dL, dH) if twin else outs
+
+
+# The twin head's backward carries the last unit's BatchNorm-backward reduce and dH = g L is never written (head_bwd_reduce; the unit's
+# apply pass forms it on load, bn_relu_bwd_split(da_gl=...)).  0 (tests / A-B): head_softmax_bwd writes dH and the unit reduces it.
+HEAD_BWD_FUSE = _flag("HEAD_BWD_FUSE", True)
+
+
+def head_bwd_fuse_ok(L, z):
+    """Do the fused head backward's 16-byte loads fit these tensors (the twin batch's L and the last unit's fp32 pre-activation z)?"""
+    if L.shape != z.shape or z.dtype != F32 or L.dtype != F32 or L.shape[0] % 2 or is_placeholder(L) or is_placeholder(z):
+        return False
+    B, C, H, W = L.shape
+    for t in (L, z):
+        ok = (W == 1 or t.stride(3) == 1) and (H == 1 or t.stride(2) == W) and (C == 1 or t.stride(1) == H * W) and t.stride(0) >= C * H * W
+        if not ok or t.stride(0) % 4 or t.data_ptr() % 16:
+            return False
+    return (H * W) % 4 == 0 and W % 4 == 0 and C % 8 == 0
+
+
+def head_grad_map(dVt, dVd, dS, S):
+    """The head's per-pixel gradients as one map [2B,1,H,W] (top half d loss / d Vt, down half d loss / d Vd) from the upstream
+    gradients of Vt, Vd [B,1,H,W] and S [B,2,H,W] (each may be None), head_softmax_bwd's expressions."""
+    B, _, H, W = S.shape
+    dVt = None if dVt is None else dVt.contiguous()
+    dVd = None if dVd is None else dVd.contiguous()
+    dS = None if dS is None else dS.contiguous()
+    S = S.contiguous()
+    g = torch.empty((2 * B, 1, H, W), dtype=F32, device=S.device)
+    _lib.call("onet_head_grad_map", _p(dVt), _p(dVd), _p(dS), _p(S), _p(g), B, H * W, _stream(),
+              nbytes=4.0 * B * H * W * (2 + (dVt is not None) + (dVd is not None) + 4 * (dS is not None)))
+    return g
+
+
+def head_bwd_reduce(g, gsums, L, z, save_all, want_amax=True):
+    """The twin head's backward fused with the BatchNorm-backward reduce of the unit whose pre-activation z the head normalised on load
+    (save_all [2][4][C]); g: head_grad_map's map, gsums as in head_softmax_bwd.  One pass over L and z: dL = g relu(bn(z)) + gsums is
+    written (head_softmax_bwd's bits), dH = g L is only summed.  -> (dL, rec4 [2 * np][C][4], da_amax | None): what
+    bn_relu_bwd_split takes as rec4 / da_amax beside da_gl=(g, L)."""
+    require_gpu(g, L, z)
+    L, lbs = plane(L)
+    z, zbs = plane(z)
+    B2, C, H, W = L.shape
+    HW = H * W
+    dev = L.device
+    assert save_all.shape == (2, 4, C) and save_all.is_contiguous() and g.is_contiguous() and g.numel() == B2 * HW
+    gst = None if gsums[0] is None else gsums[0].contiguous()
+    gsd = None if gsums[1] is None else gsums[1].contiguous()
+    dL = torch.empty((B2, C, H, W), dtype=F32, device=dev)
+    nparts = 2 * _bn_nparts(B2 // 2, HW)
+    rec4 = torch.empty((nparts, C, 4), dtype=F32, device=dev)
+    da_amax = new_amax(dev) if want_amax else None
+    _lib.call("onet_head_bwd_reduce", _p(L), lbs, _p(z), zbs, _p(g), _p(gst), _p(gsd), _p(save_all), _p(dL), _p(rec4), nparts, _p(da_amax),
+              B2, C, HW, _stream(), nbytes=12.0 * L.numel() + 4.0 * B2 * HW * (1 + (gst is not None)))
+    return dL, rec4, da_amax
 
 
 def _rows(t):

@@ -1,5 +1,6 @@
 """Turn gpurun_out/prof_TAG (tools/profile_round.sh) into the committed summaries under profiles/:
   TAG_kernel_stats_{sfx}.{csv,md}, TAG_pmc_{sfx}.json (+ pmc_bench_latest.json), TAG_sq_counters_{sfx}.md
+A set with the kernel-stats pass only (no fetch/ and write/ directories) yields the kernel-stats files alone.
 usage: python tools/profile_to_md.py TAG "one-line description of the code state" """
 import collections, csv, glob, json, os, shutil, subprocess, sys
 tag, desc = sys.argv[1], sys.argv[2]
@@ -63,6 +64,9 @@ with open(f"profiles/{tag}_kernel_stats_{sfx}.md", "w") as f:
     f.write("\n| kernel | calls | total ms | avg us | % |\n|---|---:|---:|---:|---:|\n")
     for r in rows[:40]:
         f.write(f"| `{r['Name'][:90]}` | {r['Calls']} | {int(r['TotalDurationNs'])/1e6:.2f} | {float(r['AverageNs'])/1e3:.1f} | {r['Percentage']} |\n")
+if not (os.path.isdir(f"{src}/fetch") and os.path.isdir(f"{src}/write")):      # a kernel-stats-only set (profile_round.sh's first pass)
+    print("written profiles/ for", tag, "(kernel stats only: no counter passes in the set)")
+    sys.exit(0)
 # ---- PMC traffic
 out = f"profiles/{tag}_pmc_{sfx}.json"
 subprocess.run([sys.executable, "tools/pmc_parse.py", f"{src}/fetch", f"{src}/write", "--json", out], check=True, stdout=subprocess.DEVNULL)
