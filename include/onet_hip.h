@@ -230,6 +230,19 @@ int onet_conv3x3_split_dgrad_pre_slots(const void* dzs, int64_t dzs_bs, const vo
                                        float* da, int64_t da_bs, void* daP, int64_t daP_bs, int ch0, const void* daP_amax, int B, int Cin,
                                        int Cout, int H, int W, void* stream);
 int onet_conv3x3_dgrad_bound(const float* w, int Cout, int Cin, int ci0, const void* dz_amax, void* out_slots, void* stream);
+/* Round 7 -- eval-mode inference (Settings.fused_eval).  onet_conv3x3_split_fwd_pre's convolution on fp16 (hi | mid) parts with a FIXED
+ * BatchNorm + ReLU in the epilogue, a = max(0, fma(z - mean, sc, sh)) from save [4][Cout] (onet_bn_eval_coeffs' format), leaving as slots:
+ * aP [B][Cout/8][H][2][W][8] (batch stride aP_bs in 4-byte units) = parts of 2^k a, k by the guard rule from the bound aP_slots holds
+ * BEFORE the launch (onet_conv3x3_act_bound) -- bit for bit what the plain launch + onet_bn_relu_apply_split(z, save, act_amax = aP_slots)
+ * write; z is never stored.  a_amax (may be NULL; zeroed by the caller): receives the exact max a.  a (may be NULL): the activation as
+ * fp32 NCHW too.  Maps made of full 16 x 32 tiles, Cin % 16 == 0, Cout % 64 == 0: returns 1 (nothing launched) elsewhere.
+ * onet_conv3x3_act_bound: max over co of |sc| (S1 max1 + S2 max2) + |sh - mean sc|, S1 / S2 = sum of |w[co][ci][.]| over ci < / >= split_ch,
+ * max1 / max2 from x_amax / x_amax2 (split_ch = 0, x_amax2 = NULL: one group), in fp64 rounded up to fp32, atomicMax into out_slots. */
+int onet_conv3x3_split_fwd_pre_act(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
+                                   const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
+                                   int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream);
+int onet_conv3x3_act_bound(const float* w, int Cout, int Cin, const float* save, const void* x_amax, const void* x_amax2, int split_ch,
+                           void* out_slots, void* stream);
 /* Weight gradient (OV:47,51 backward) from pre-split x and dz (both in the slot layout, same 16-bit type): fragments by the gfx950
  * transposing LDS read, staging by LDS-DMA; the producers' power-of-two scales (x_amax: guard rule, dz_amax: always; NULL:
  * unscaled) are undone on the slabs; deterministic split-K through ws

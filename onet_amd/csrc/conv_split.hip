@@ -658,6 +658,15 @@ struct SpPreArgs {
     int64_t zP_bs = 0;
     int zP_ch0 = 0;
     const unsigned* zP_slots = nullptr;
+    // conv3x3_split_pre_kernel<false, 1, false, ACT = true> (eval-mode inference): the epilogue applies a fixed BatchNorm + ReLU to the
+    // accumulator tile -- a = max(0, fma(z - mean, sc, sh)) with act_save [4][Cout] in bn_eval_coeffs' format, bn_relu_apply_split's
+    // arithmetic -- and EVERY channel leaves as slots through zP (zP_ch0 = 0), as parts of 2^k a with k by the GUARD rule (always = false)
+    // from the bound in zP_slots.  z is never written.  act_amax (may be NULL): magnitude slots that receive the exact max a;
+    // act_a (may be NULL): the activation in fp32 NCHW too, batch stride act_a_bs
+    const float* act_save = nullptr;
+    unsigned* act_amax = nullptr;
+    float* act_a = nullptr;
+    int64_t act_a_bs = 0;
 };
 
 // PM: 0 = bf16 (hi | mid) parts, 1 = fp16 (hi | mid) parts -- three MFMAs per term on 16-channel chunks; 2 = PLAIN bf16 operands
@@ -677,9 +686,10 @@ template <bool W16> struct SpPreCfg {
     static constexpr int NB = (NT - 1) + 3;
     static constexpr int LAST_TAP = 4;                                  // the next chunk's DMA pieces go out during taps 0 .. LAST_TAP
 };
-template <bool ST, int PM, bool W16>
+template <bool ST, int PM, bool W16, bool ACT = false>
 __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void conv3x3_split_pre_kernel(SpPreArgs a) {
     constexpr bool F16 = PM == 1;
+    static_assert(!ACT || (PM == 1 && !ST && !W16), "conv3x3_split_pre_kernel: the activation epilogue goes with the fp16 slot store");
     using C = SpPreCfg<W16>;
     constexpr int NT = C::NT, IN_COLS = C::IN_COLS, NWI = C::NWI, CO_T = C::CO_T, NPIXP = C::NPIXP, NB = C::NB;
     constexpr int BUF = C::BUF_SLOTS, W_PART = C::W_PART, IN_PART = C::IN_PART, ROWS = C::ROWS, TW = C::TW;
@@ -791,9 +801,28 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
     float zP_scale = 1.f;
     if constexpr (PM == 1 && !ST && !W16) {
         float zinv;
-        if (a.zP) zP_scale = amax_scale(amax_read(a.zP_slots), true, zinv);
+        if (a.zP) zP_scale = amax_scale(amax_read(a.zP_slots), !ACT, zinv);
     }
+    // ACT: the tile's 64 x (mean, sc, sh) wait in LDS behind the chunk buffers, [tile parity][3][64] floats -- no registers per lane.
+    // Threads 0 .. 191 fetch the NEXT tile's while this tile's chunks run (the load lands under the chunk loop's own waits) and commit
+    // them at the top of that tile; its chunk barriers publish them.  Two copies: a wave still in the previous tile's epilogue reads
+    // the other one (nobody gets two tiles ahead of a barrier)
+    [[maybe_unused]] float* const act_cf = reinterpret_cast<float*>(lds + 2 * BUF);
+    [[maybe_unused]] float cf_next = 0.f;
+    [[maybe_unused]] int cf_par = 0;
+    auto act_fetch = [&](int t) __attribute__((always_inline)) {
+        if (tid < 192 && t < t_end) {
+            const int k = tid >> 6;                                 // 0: mean, 1: sc, 2: sh   (save rows 0, 2, 3)
+            cf_next = a.act_save[(int64_t)(k + (k > 0)) * a.Cout + (t % a.coTiles) * CO_T + (tid & 63)];
+        }
+    };
+    if constexpr (ACT) act_fetch(t_first);
     for (int tile = t_first; tile < t_end; tile += t_stride) {
+        if constexpr (ACT) {
+            cf_par ^= 1;
+            if (tid < 192) act_cf[cf_par * 192 + tid] = cf_next;
+            act_fetch(tile + t_stride);
+        }
         f32x16 acc[2][NT];
 #pragma unroll
         for (int m = 0; m < 2; ++m)
@@ -951,8 +980,54 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
         }
         float* zb = a.z + (int64_t)(W16 ? 2 * b + (l31 >> 4) : b) * a.z_bs;      // (W16: b is the image pair, lanes 16-31 hold the second image)
         const int xo = W16 ? (l31 & 15) : x0 + l31;
+        if constexpr (ACT) {
+            // BatchNorm (fixed coefficients) + ReLU on the accumulators, bn_relu_apply_split_kernel's expression; register r of
+            // acc[m][n] is channel m 32 + 8 (r / 4) + 4 kh + r % 4 of the tile: four consecutive floats per coefficient and group
+            const float* cf = act_cf + cf_par * 192;
+            float vmax = 0.f;
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int cl = m * 32 + 8 * g + 4 * kh;
+                    const f32x4s mean = *reinterpret_cast<const f32x4s*>(cf + cl);
+                    const f32x4s sc = *reinterpret_cast<const f32x4s*>(cf + 64 + cl);
+                    const f32x4s sh = *reinterpret_cast<const f32x4s*>(cf + 128 + cl);
+#pragma unroll
+                    for (int n = 0; n < NT; ++n)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const float v = fmaxf(fmaf(acc[m][n][4 * g + j] - mean[j], sc[j], sh[j]), 0.f);
+                            acc[m][n][4 * g + j] = v;
+                            vmax = fmaxf(vmax, v);
+                        }
+                }
+            if (a.act_amax) {
+                // the exact maximum of what this wave wrote: one atomicMax on the fp32 bit pattern per wave and tile
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o, 64));
+                if (lane == 0 && vmax == vmax)
+                    atomicMax(a.act_amax + ((tile * NWV + wn) & (AMAX_SLOTS - 1)) * AMAX_STRIDE, __builtin_bit_cast(unsigned, vmax));
+            }
+            if (a.act_a) {
+                float* ab = a.act_a + (int64_t)b * a.act_a_bs;
+#pragma unroll
+                for (int m = 0; m < 2; ++m)
+#pragma unroll
+                    for (int n = 0; n < NT; ++n) {
+                        const int yo = y0 + wn * NT + n;
+                        if (yo < a.H && xo < a.W) {
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) {
+                                const int co = co0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                                if (co < a.Cout) ab[(int64_t)co * HW + (int64_t)yo * a.W + xo] = acc[m][n][r];
+                            }
+                        }
+                    }
+            }
+        }
         if constexpr (PM == 1 && !ST && !W16) {
-            if (a.zP && co0 >= a.zP_ch0) {
+            if (ACT || (a.zP && co0 >= a.zP_ch0)) {
                 // Pre-split output (SpPreArgs::zP).  A lane holds channels 8 g + 4 kh + {0 .. 3} of its pixel for the four groups g of a
                 // 32-row accumulator; v_permlane32_swap trades halves with the partner lane (kh ^ 1): afterwards a kh = 0 lane owns all
                 // 8 channels of groups 0 and 2, a kh = 1 lane those of groups 1 and 3 -- whole slots, 512 contiguous bytes per half-wave
@@ -1462,10 +1537,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     }
 }
 
-template <bool ST, int PM, bool W16, bool RD = false>
+template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false>
 int launch_split_pre(SpPreArgs a, hipStream_t st) {
     using C = SpPreCfg<W16>;
-    const int LDS_BYTES = C::LDS_BYTES + (ST ? C::NW * 64 * 2 * 4 : 0);
+    const int LDS_BYTES = C::LDS_BYTES + (ST ? C::NW * 64 * 2 * 4 : 0) + (ACT ? 2 * 3 * 64 * 4 : 0);
     a.tilesX = W16 ? 1 : cdiv(a.W, C::TW);
     a.tilesY = cdiv(a.H, C::ROWS);
     a.coTiles = cdiv(a.Cout, C::CO_T);
@@ -1479,7 +1554,7 @@ int launch_split_pre(SpPreArgs a, hipStream_t st) {
     constexpr bool P16 = RD || PM == 2 || (ST && !W16);
     void (*kern)(SpPreArgs);
     if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD>;      // (constexpr: the instances not dispatched are not built)
-    else kern = conv3x3_split_pre_kernel<ST, PM, W16>;
+    else kern = conv3x3_split_pre_kernel<ST, PM, W16, ACT>;
     static PerDeviceOnce attr_once;
     if (attr_once.first()) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
@@ -1487,7 +1562,7 @@ int launch_split_pre(SpPreArgs a, hipStream_t st) {
     const int64_t resident = (int64_t)device_cu_count();
     const int64_t blocks = std::min<int64_t>((tiles + 7) / 8 * 8, std::max<int64_t>(8, resident / 8 * 8));
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(C::NW * 64), LDS_BYTES, st, a);
-    return check_launch("conv3x3_split_pre_kernel");
+    return check_launch(ACT ? "conv3x3_split_pre_act_kernel" : "conv3x3_split_pre_kernel");
 }
 
 int split_nparts(int B, int H, int W) {
@@ -2418,6 +2493,83 @@ int onet_conv3x3_split_dgrad_pre_slots(const void* dzs, int64_t dzs_bs, const vo
     a.zP_slots = (const unsigned*)daP_amax;
     if (wq_f16 == 2) return launch_split_pre<false, 2, false>(a, as_stream(stream));      // plain bf16: one part, unscaled (conv3x3_pre16_kernel)
     return launch_split_pre<false, 1, false>(a, as_stream(stream));
+}
+
+// Eval-mode inference: the forward convolution of onet_conv3x3_split_fwd_pre (fp16 hi | mid parts) with a FIXED BatchNorm + ReLU in
+// the epilogue and the activation leaving as slots (SpPreArgs::act_*): aP [B][Cout/8][H][2][W][8] = parts of 2^k relu(bn(z)), k by the
+// guard rule from the bound aP_slots holds BEFORE the launch (onet_conv3x3_act_bound).  Bit for bit what the plain launch followed by
+// onet_bn_relu_apply_split(z, save, slots = aP_slots) writes; z itself is never stored.  Returns 1 (nothing launched) where the map is
+// not made of full 16 x 32 tiles or Cout is not a multiple of 64.
+int onet_conv3x3_split_fwd_pre_act(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
+                                   const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
+                                   int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    ONET_REQUIRE(xs && wq && save && aP && aP_slots, "conv3x3_split_fwd_pre_act: null pointer");
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv3x3_split_fwd_pre_act: bad shape");
+    if (W < 32 || (W % 32) || (H % 16) || (Cin % 16) || (Cout % 64)) return 1;
+    ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "conv3x3_split_fwd_pre_act: split_ch must be a multiple of 32 inside Cin");
+    ONET_REQUIRE((xs_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(xs) & 15) == 0 && (aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0,
+                 "conv3x3_split_fwd_pre_act: 16-byte aligned slots required");
+    ONET_REQUIRE(xs_bs >= (int64_t)Cin * H * W && aP_bs >= (int64_t)Cout * H * W && (!a || a_bs >= (int64_t)Cout * H * W),
+                 "conv3x3_split_fwd_pre_act: batch stride too small");
+    ONET_REQUIRE((int64_t)(Cin + 32) * H * W * 4 < (1ll << 31) && (int64_t)(Cin + 32) * 2 * 9 * Cout * 2 < (1ll << 31),
+                 "conv3x3_split_fwd_pre_act: operand exceeds the 2 GiB buffer-resource range");
+    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)x_amax, scale_always,
+                (const unsigned*)x_amax2, split_ch};
+    p.zP = aP;
+    p.zP_bs = aP_bs;
+    p.zP_ch0 = 0;
+    p.zP_slots = (const unsigned*)aP_slots;
+    p.act_save = save;
+    p.act_amax = (unsigned*)a_amax;
+    p.act_a = a;
+    p.act_a_bs = a_bs;
+    return launch_split_pre<false, 1, false, false, true>(p, as_stream(stream));
+}
+
+// a[co] = relu(sc (z - mean) + sh) with |z[co]| <= sum_ci |w[co][ci][.]| max |x[ci]|:  |a[co]| <= |sc| (S1 max1 + S2 max2) + |sh - mean sc|,
+// S1 / S2 = the L1 norms of the output channel's weights over the input channels below / from split_ch, max1 / max2 the two producers'
+// magnitudes (x_amax, x_amax2; one group: split_ch = 0).  The largest over co goes into out_slots (zeroed by the caller): the bound
+// onet_conv3x3_split_fwd_pre_act scales its slots by -- evaluated in fp64 and rounded UP to fp32.  save: [4][Cout], bn_eval_coeffs' format
+__global__ __launch_bounds__(256) void conv3x3_act_bound_kernel(const float* __restrict__ w, int Cout, int Cin, const float* __restrict__ save,
+                                                                const unsigned* __restrict__ x_slots, const unsigned* __restrict__ x_slots2,
+                                                                int split_ch, unsigned* __restrict__ out_slots) {
+    __shared__ double red[2][4];
+    const double m1 = (double)amax_read(x_slots), m2 = x_slots2 ? (double)amax_read(x_slots2) : m1;
+    const int co = blockIdx.x;
+    const int n1 = (x_slots2 && split_ch > 0 ? split_ch : Cin) * 9;
+    double s1 = 0.0, s2 = 0.0;
+    for (int i = threadIdx.x; i < Cin * 9; i += 256) {
+        const double v = (double)fabsf(w[(int64_t)co * Cin * 9 + i]);
+        if (i < n1) s1 += v;
+        else s2 += v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s1 += __shfl_xor(s1, o, 64);
+        s2 += __shfl_xor(s2, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = s1;
+        red[1][threadIdx.x >> 6] = s2;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double S1 = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]), S2 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        const double mean = save[co], sc = save[2 * Cout + co], sh = save[3 * Cout + co];
+        const double bound = fabs(sc) * (S1 * m1 + S2 * m2) + fabs(sh - mean * sc);
+        float f = (float)bound;
+        if ((double)f < bound) f = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, f) + 1u);      // round up (f >= 0, finite)
+        if (f == f) atomicMax(out_slots + (blockIdx.x & (AMAX_SLOTS - 1)) * AMAX_STRIDE, __builtin_bit_cast(unsigned, f));
+    }
+}
+
+int onet_conv3x3_act_bound(const float* w, int Cout, int Cin, const float* save, const void* x_amax, const void* x_amax2, int split_ch,
+                           void* out_slots, void* stream) {
+    ONET_REQUIRE(w && save && x_amax && out_slots && Cout > 0 && Cin > 0, "conv3x3_act_bound: bad args");
+    ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (x_amax2 || split_ch == 0), "conv3x3_act_bound: split_ch must lie inside Cin and go with x_amax2");
+    hipLaunchKernelGGL(conv3x3_act_bound_kernel, dim3((unsigned)Cout), dim3(256), 0, as_stream(stream), w, Cout, Cin, save,
+                       (const unsigned*)x_amax, (const unsigned*)x_amax2, split_ch, (unsigned*)out_slots);
+    return check_launch("conv3x3_act_bound_kernel");
 }
 
 // |da[ci]| <= max |dz| * sum over (co, tap) of |w[co][ci][tap]|: the bound of the input gradient's channels >= ci0 from the bound of dz

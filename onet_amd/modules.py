@@ -311,6 +311,11 @@ class UNet(nn.Module):
         """head_link (Onet.forward, twin batch): a dict through which the LAST unit hands its pre-activation and coefficients to the head
         instead of writing its activation (the second returned tensor is then a placeholder: Onet's head is its only reader)."""
         # the 18 num_batches_tracked counters of a pass take their increments in one multi-tensor launch when the pass is through
+        if head_link is None and groups == 1 and not self.training and ops.fused_eval():
+            from . import inference
+            fused = inference.unet_forward(self, x)        # (Settings.fused_eval: None wherever the plan does not apply)
+            if fused is not None:
+                return fused
         plain = _hooked(self)
         with ops.counting_batches():
             return self._forward(x, groups, None if plain else head_link, plain)
@@ -450,6 +455,11 @@ class Onet(nn.Module):
             return self._forward(X)
 
     def _forward(self, X):
+        if not self.training and ops.fused_eval():
+            from . import inference
+            fused = inference.onet_forward(self, X)        # (Settings.fused_eval: None wherever the plan does not apply)
+            if fused is not None:
+                return fused
         if X.dim() == 4 and X.is_cuda and ops.split_enabled():
             ops.amax_arena_reset(X.device)          # this step's magnitude slots: one fill instead of one per tensor
         if self.dwnu is self.topu and ops.twin_enabled() and X.dim() == 4 and X.is_cuda:

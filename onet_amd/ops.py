@@ -58,14 +58,18 @@ class Settings:
       stem_fused    the stem convolution + its BatchNorm statistics in one streaming pass                          (default STEM_FUSED)
       sync_bn       BatchNorm statistics all-gathered over the process group                                       (default SYNC_BN)
       presplit      the split kernels' operands are written pre-split (fp16 hi | mid slots) by their producers     (default PRESPLIT)
-      z_bf16        under conv == "bf16" with pre-split operands: the convolution outputs z are STORED as bf16          (default Z_BF16)"""
+      z_bf16        under conv == "bf16" with pre-split operands: the convolution outputs z are STORED as bf16          (default Z_BF16)
+      fused_eval    eval-mode forward under no_grad as a straight-line plan on the pre-split kernels: BatchNorm(eval) + ReLU in
+                    the convolution's epilogue, activations kept as slots (onet_amd/inference.py); opt-in                (default FUSED_EVAL)"""
     __slots__ = ("conv", "twin", "convt_bf16", "lazy_nan", "split", "bn_on_load", "split_f16", "grad_f16", "split_dgrad",
-                 "stem_fused", "sync_bn", "presplit", "z_bf16")
+                 "stem_fused", "sync_bn", "presplit", "z_bf16", "fused_eval")
 
     def __init__(self, conv=None, twin=None, convt_bf16=None, lazy_nan=None, split=None, bn_on_load=None,
-                 split_f16=None, grad_f16=None, split_dgrad=None, stem_fused=None, sync_bn=None, presplit=None, z_bf16=None):
+                 split_f16=None, grad_f16=None, split_dgrad=None, stem_fused=None, sync_bn=None, presplit=None, z_bf16=None,
+                 fused_eval=None):
         self.presplit = presplit
         self.z_bf16 = z_bf16
+        self.fused_eval = fused_eval
         self.conv, self.twin, self.convt_bf16, self.lazy_nan = conv, twin, convt_bf16, lazy_nan
         self.split, self.bn_on_load = split, bn_on_load
         self.split_f16, self.grad_f16, self.split_dgrad, self.stem_fused, self.sync_bn = split_f16, grad_f16, split_dgrad, stem_fused, sync_bn
@@ -151,6 +155,13 @@ def presplit():
     if conv_algo() == "bf16":           # BASELINE configs[2]: the same machinery with ONE part of plain bf16 operands (p16_parts() == 1)
         return True
     return split_enabled() and conv_algo() in ("auto", "split") and split_f16() and split_dgrad()
+
+
+FUSED_EVAL = _flag("FUSED_EVAL", False)     # 1: eval forwards under no_grad take the fused inference plan (Settings.fused_eval)
+
+
+def fused_eval():
+    return bool(_setting("fused_eval", FUSED_EVAL))
 
 
 Z_BF16 = _flag("Z_BF16", True)       # BASELINE configs[2] (conv == "bf16", pre-split operands): conv outputs stored as bf16 (Settings.z_bf16)
@@ -569,19 +580,19 @@ class PackedT:
         return v[1]
 
 
-def convT2x2_fwd_slots(xP, wP, bias, outP, Ct, x_slots=None, slots=None):
+def convT2x2_fwd_slots(xP, wP, bias, outP, Ct, x_slots=None, slots=None, kind="convt_gemm_kernel"):
     """ConvTranspose2d(k=2, s=2) + bias from the PRE-SPLIT input xP [B, Cin/8, h, parts, w, 8] and the slot pack wP (packT2x2_slots),
     written pre-split into outP [B, Ct/8, 2h, parts, 2w, 8]: both GEMM operands are LDS-DMA copies.  x_slots / slots: the magnitude slots
     of the input / output.  -> False where the kernel does not take the shape (nothing written)."""
     B, C8, h, parts, w, _ = xP.shape
     assert outP.shape[3] == parts and outP.shape[2] == 2 * h and outP.shape[4] == 2 * w and xP.dtype == wP.dtype == outP.dtype
     Cin = C8 * 8
-    e0 = _prof_begin("convt_gemm_kernel")
+    e0 = _prof_begin(kind)       # (the fused eval plan records its launches under the device kernel's own name)
     rc = _lib.load().onet_convT2x2_fwd_slots(_p(xP), _pbs(xP), _p(x_slots), _p(wP), _p(bias), _p(outP), _pbs(outP), _p(slots), parts, B, Cin, Ct,
                                              h, w, _stream())
     eb = 2.0 * parts
     flops, nb = 2.0 * B * h * w * Cin * 4 * Ct, eb * (B * h * w * (Cin + 4 * Ct) + 4 * Cin * Ct)
-    _prof_end("convt_gemm_kernel", flops if rc == 0 else 0.0, e0, nb if rc == 0 else 0.0)
+    _prof_end(kind, flops if rc == 0 else 0.0, e0, nb if rc == 0 else 0.0)
     if rc < 0:
         raise _lib.OnetHipError(f"onet_convT2x2_fwd_slots failed ({rc}): {_lib.last_error()}")
     return rc == 0
@@ -1164,6 +1175,54 @@ def conv3x3_split_dgrad_pre_bnreduce(dzP, wq, Cout, z_prev, save_prev, slots=Non
     if rc < 0:
         raise _lib.OnetHipError(f"onet_conv3x3_split_dgrad_pre_bnreduce failed ({rc}): {_lib.last_error()}")
     return (da, rec4, am) if rc == 0 else None
+
+
+def eval_layer_ok(B, Cin, Cout, H, W):
+    """Does the fused eval plan (onet_amd/inference.py) take a 3x3 convolution layer (Cin -> Cout on B maps of H x W) on pre-split
+    operands?  Yes wherever today's eval dispatch selects the in-staging split kernel for the layer and the shape lies in the domain
+    of onet_conv3x3_split_fwd_pre_act: fp16 (hi | mid) parts, maps made of full 16 x 32 tiles, Cin % 16 == 0, Cout % 64 == 0.  A
+    function of shapes, settings and -- through conv3x3_algo's tile threshold -- the current device's compute-unit count (n_cu): no
+    tensor is looked at, nothing is launched, but the fused depth of a small batch can differ between devices."""
+    if not presplit() or p16_parts() != 2:
+        return False
+    if Cin % 16 or Cout % 64 or W < 32 or W % 32 or H % 16 or H * W >= 2 ** 24:
+        return False
+    return conv3x3_algo(B, Cin, Cout, H, W) == "split"
+
+
+def conv3x3_act_bound(weight, save, x_amax, x_amax2=None, split_ch=0):
+    """Magnitude slots bounding relu(bn_eval(conv3x3(x))) from the layer's weights, the coefficients `save` [4, Cout] and the magnitude
+    slots of x (two producers of a concat buffer: x_amax2 for the channels from split_ch): the scale slots of the fused eval kernel."""
+    w = weight.detach()
+    w = w if w.is_contiguous() else w.contiguous()
+    slots = new_amax(w.device)
+    _lib.call("onet_conv3x3_act_bound", _p(w), w.shape[0], w.shape[1], _p(save), _p(x_amax), _p(x_amax2), int(split_ch if x_amax2 is not None else 0),
+              _p(slots), _stream())
+    return slots
+
+
+def conv3x3_split_pre_act(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None):
+    """aP = relu(bn(conv3x3(xs))) written PRE-SPLIT, BatchNorm with the fixed coefficients `save` [4, Cout] (bn_eval_coeffs) in the
+    convolution's epilogue: conv3x3_split_pre followed by bn_relu_apply_split(.., slots=aP_slots), bit for bit, without the tensor z.
+    aP_slots: the bound the parts are scaled by (conv3x3_act_bound, before this launch); a_amax: slots that receive the exact max a;
+    a: optional fp32 destination.  -> aP, or None where the kernel does not take the shape (nothing launched)."""
+    if wq is None or not wq.is_cuda or wq.dtype != torch.float16 or xs.dtype != torch.float16 or xs.shape[3] != 2:
+        raise TypeError("conv3x3_split_pre_act: xs and wq must be fp16 (hi | mid) split packs on the GPU")
+    B, C8, H, _, W, _ = xs.shape
+    Cin = C8 * 8
+    if W < 32 or W % 32 or H % 16 or Cin % 16 or Cout % 64:
+        return None
+    if out is None:
+        out = p16_empty(B, Cout, H, W, xs.device, parts=2)
+    e0 = _prof_begin("conv3x3_split_pre_act_kernel")
+    rc = _lib.load().onet_conv3x3_split_fwd_pre_act(_p(xs), _pbs(xs), _p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0),
+                                                    _p(wq), _p(save), _p(out), _pbs(out), _p(aP_slots), _p(a_amax), _p(a),
+                                                    0 if a is None else (a.stride(0) if B > 1 else Cout * H * W), B, Cin, Cout, H, W, _stream())
+    _prof_end("conv3x3_split_pre_act_kernel", 2.0 * B * H * W * Cin * Cout * 9 if rc == 0 else 0.0, e0,
+              (B * H * W * (4.0 * Cin + (4.0 + 4.0 * (a is not None)) * Cout) + 4.0 * 9 * Cin * Cout) if rc == 0 else 0.0)
+    if rc < 0:
+        raise _lib.OnetHipError(f"onet_conv3x3_split_fwd_pre_act failed ({rc}): {_lib.last_error()}")
+    return out if rc == 0 else None
 
 
 FUSE_DGRAD_REDUCE = _flag("FUSE_DGRAD_REDUCE", True)      # False (tests / A-B): the first unit of a DoubleConv runs its own BatchNorm-backward reduce pass
