@@ -48,6 +48,14 @@ inline int device_cu_count() {
     return n;
 }
 
+// XCD-aware block order: workgroups are dealt round-robin over the 8 XCDs (each with a private L2); the logical block id
+// returned here gives every XCD a CONTIGUOUS range of the grid's logical blocks, so that neighbours in a kernel's tile order run
+// on one XCD and share their operands in its L2 (bijective for any grid size; placement only affects speed, never results)
+__device__ __forceinline__ int xcd_block_id() {
+    const int n = gridDim.x, q = n >> 3, r = n & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+}
+
 // wave64 reductions via DPP/shuffles
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {

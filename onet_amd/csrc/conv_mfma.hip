@@ -126,11 +126,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_kernel(ConvArgs a) {
     // L2), so give every XCD a CONTIGUOUS range of logical tiles -- horizontally adjacent tiles share
     // halo columns / 128-B lines and the co-tiles of one pixel tile share the whole input tile.
     // (bijective for any grid size; placement only affects speed, never results)
-    int bid;
-    {
-        const int n = gridDim.x, q = n >> 3, r = n & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    int bid = xcd_block_id();
     // pixel tile fastest, output-channel tile slowest: the ~32 blocks resident on one XCD at a time then
     // stream the SAME packed weights (the larger operand per K-chunk) through its L2 once, and
     // neighbouring pixel tiles share their halo lines.
@@ -453,11 +449,7 @@ __global__ __launch_bounds__(256 * KS, KS == 3 ? 3 : 2) void conv_wgrad_kernel(W
     // XCD-aware order (see conv_fwd_kernel): every XCD gets a contiguous range of logical blocks,
     // ordered split-K slice major / (ci,co) tile minor, so the blocks that stream the SAME pixel strips
     // (all tiles of one slice) run back to back on one XCD and share them through its L2.
-    int bid;
-    {
-        const int n = gridDim.x, q = n >> 3, r = n & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    int bid = xcd_block_id();
     const int tiles = a.ciTiles * a.coTiles;
     const int ks = bid / tiles;
     const int tile = bid % tiles;

@@ -170,6 +170,38 @@ struct SpCfg {
     static constexpr int NB = (NT - 1) + 3;                             // distinct B row-fragments per horizontal tap
 };
 
+// ---- shared by conv3x3_split_kernel, conv3x3_split_pre_kernel and conv3x3_pre16_kernel: the persistent tile walk
+
+// tiles of this block: every XCD (blockIdx % 8) owns a contiguous range of the tile list; its blocks stride through the range.
+// Tile list order: OUTPUT-CHANNEL tile fastest, then x, y, image -- the Cout / 64 blocks that need the same input tile run on
+// one XCD at the same time and share it in that L2 (with the channel tile slowest every one of the Cout / 64 passes over the
+// batch streamed the whole input from HBM again: 1.8 x the compulsory bytes per launch on average); the weight slices of
+// all channel tiles (<= 9 MB) then live in L2 / MALL instead of one slice at a time
+__device__ __forceinline__ void sp_tile_range(int ntiles, int& t_first, int& t_end, int& t_stride) {
+    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+    const int q = ntiles >> 3, r = ntiles & 7;
+    const int start = xcd * q + min(xcd, r);
+    t_stride = (gridDim.x + 7 - xcd) >> 3;
+    t_first = start + j;
+    t_end = start + q + (xcd < r ? 1 : 0);
+}
+// entry v of the tile list: output channels co0 .. + 63 of rows y0 .. + 15, pixels x0 .. + 31 of image b (W16: of image PAIR b)
+struct SpTile {
+    int co0, tx, ty, b, y0, x0;
+};
+__device__ __forceinline__ SpTile sp_tile(int v, int coTiles, int tilesX, int tilesY) {
+    SpTile t;
+    t.co0 = (v % coTiles) * SpCfg::CO_T;             // output-channel tile fastest: see the tile order note above
+    v /= coTiles;
+    t.tx = v % tilesX;
+    v /= tilesX;
+    t.ty = v % tilesY;
+    t.b = v / tilesY;
+    t.y0 = t.ty * SpCfg::ROWS;
+    t.x0 = t.tx * SpCfg::TW;
+    return t;
+}
+
 // PERSISTENT blocks: a block walks over output tiles and the chunk pipeline -- global loads two 16-channel
 // chunks ahead of the MFMAs, LDS commit one ahead -- runs ACROSS tile boundaries.
 // ST: the forward of a Conv-BatchNorm pair (OV:47-48, 51-52) also emits the BatchNorm statistics of its output, one (n, mean,
@@ -182,25 +214,12 @@ template <bool ST, bool NORM, bool F16>
 __global__ __launch_bounds__(512, 2) void conv3x3_split_kernel(SpArgs a) {
     using C = SpCfg;
     constexpr int NT = C::NT, IN_COLS = C::IN_COLS, NWI = C::NWI, CO_T = C::CO_T, NPIXP = C::NPIXP, NB = C::NB;
-    constexpr int BUF = C::BUF_SLOTS, W_PART = C::W_PART, IN_PART = C::IN_PART, ROWS = C::ROWS, TW = C::TW;
+    constexpr int BUF = C::BUF_SLOTS, W_PART = C::W_PART, IN_PART = C::IN_PART, TW = C::TW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];
     u32x4s* lds = reinterpret_cast<u32x4s*>(smem_s);                   // [2 buffers][weights hi|mid | input hi|mid]
 
-    // tiles of this block: every XCD (blockIdx % 8) owns a contiguous range of the tile list; its blocks stride through the range.
-    // Tile list order: OUTPUT-CHANNEL tile fastest, then x, y, image -- the Cout / 64 blocks that need the same input tile run on
-    // one XCD at the same time and share it in that L2 (with the channel tile slowest every one of the Cout / 64 passes over the
-    // batch streamed the whole input from HBM again: 1.8 x the compulsory bytes per launch on average); the weight slices of
-    // all channel tiles (<= 9 MB) then live in L2 / MALL instead of one slice at a time
-    const int ntiles = a.tilesX * a.tilesY * a.B * a.coTiles;
-    int t_first, t_end, t_stride;
-    {
-        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        const int q = ntiles >> 3, r = ntiles & 7;
-        const int start = xcd * q + min(xcd, r);
-        t_stride = (gridDim.x + 7 - xcd) >> 3;
-        t_first = start + j;
-        t_end = start + q + (xcd < r ? 1 : 0);
-    }
+    int t_first, t_end, t_stride;                                      // tile list order: see sp_tile_range
+    sp_tile_range(a.tilesX * a.tilesY * a.B * a.coTiles, t_first, t_end, t_stride);
     if (t_first >= t_end) return;
 
     const int tid = threadIdx.x, lane = tid & 63, wn = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -242,14 +261,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_split_kernel(SpArgs a) {
     bool pend_keep = false;                          // validity of the item whose loads are in flight
     auto setup_stage = [&]() __attribute__((always_inline)) {
         const bool live = st_tile < t_end;
-        int v = live ? st_tile : t_first;
-        const int co0 = (v % a.coTiles) * CO_T;      // output-channel tile fastest: see the tile order note at the top of the kernel
-        v /= a.coTiles;
-        const int tx = v % a.tilesX;
-        v /= a.tilesX;
-        const int ty = v % a.tilesY;
-        const int b = v / a.tilesY;
-        const int y0 = ty * ROWS, x0 = tx * TW;
+        const auto [co0, tx, ty, b, y0, x0] = sp_tile(live ? st_tile : t_first, a.coTiles, a.tilesX, a.tilesY);
         st_b = b;
         xr = s_rsrc(a.x + (int64_t)b * a.x_bs, (int64_t)a.Cin * HW * 4);
         {
@@ -484,14 +496,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_split_kernel(SpArgs a) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[m][n][r] *= acc_scale;
         }
-        int v = tile;
-        const int co0 = (v % a.coTiles) * CO_T;      // output-channel tile fastest: see the tile order note at the top of the kernel
-        v /= a.coTiles;
-        const int tx = v % a.tilesX;
-        v /= a.tilesX;
-        const int ty = v % a.tilesY;
-        const int b = v / a.tilesY;
-        const int y0 = ty * ROWS, x0 = tx * TW;
+        const auto [co0, tx, ty, b, y0, x0] = sp_tile(tile, a.coTiles, a.tilesX, a.tilesY);
         if constexpr (ST) {
             float* sc = reinterpret_cast<float*>(lds + 2 * BUF);       // [8 waves][64 channels][mean, M2]
             constexpr float npw = (float)(NT * 32), inv_npw = 1.f / npw;
@@ -685,6 +690,7 @@ template <bool W16> struct SpPreCfg {
     static constexpr int LDS_BYTES = 2 * BUF_SLOTS * 16;
     static constexpr int NB = (NT - 1) + 3;
     static constexpr int LAST_TAP = 4;                                  // the next chunk's DMA pieces go out during taps 0 .. LAST_TAP
+    static_assert(CO_T == SpCfg::CO_T && ROWS == SpCfg::ROWS && TW == SpCfg::TW, "sp_tile: one tile shape for every kernel of the family");
 };
 template <bool ST, int PM, bool W16, bool ACT = false>
 __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void conv3x3_split_pre_kernel(SpPreArgs a) {
@@ -692,22 +698,14 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
     static_assert(!ACT || (PM == 1 && !ST && !W16), "conv3x3_split_pre_kernel: the activation epilogue goes with the fp16 slot store");
     using C = SpPreCfg<W16>;
     constexpr int NT = C::NT, IN_COLS = C::IN_COLS, NWI = C::NWI, CO_T = C::CO_T, NPIXP = C::NPIXP, NB = C::NB;
-    constexpr int BUF = C::BUF_SLOTS, W_PART = C::W_PART, IN_PART = C::IN_PART, ROWS = C::ROWS, TW = C::TW;
+    constexpr int BUF = C::BUF_SLOTS, W_PART = C::W_PART, IN_PART = C::IN_PART;
     constexpr int NWV = C::NW, NTH = NWV * 64;
     constexpr int NII = (2 * IN_PART + NTH - 1) / NTH;                     // 5 (6) input DMA rounds per wave and chunk (2560 / 2624 slot positions)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];
     u32x4s* lds = reinterpret_cast<u32x4s*>(smem_s);                   // [2 buffers][weights hi|mid | input hi|mid]
 
-    const int ntiles = a.tilesX * a.tilesY * a.B * a.coTiles;          // tile list order: see conv3x3_split_kernel
-    int t_first, t_end, t_stride;
-    {
-        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        const int q = ntiles >> 3, r = ntiles & 7;
-        const int start = xcd * q + min(xcd, r);
-        t_stride = (gridDim.x + 7 - xcd) >> 3;
-        t_first = start + j;
-        t_end = start + q + (xcd < r ? 1 : 0);
-    }
+    int t_first, t_end, t_stride;                                      // tile list order: see sp_tile_range
+    sp_tile_range(a.tilesX * a.tilesY * a.B * a.coTiles, t_first, t_end, t_stride);
     if (t_first >= t_end) return;
 
     const int tid = threadIdx.x, lane = tid & 63, wn = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -735,14 +733,7 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
     unsigned cin_bytes = 0, cw_bytes = 0;
     auto setup_stage = [&]() __attribute__((always_inline)) {
         const bool live = st_tile < t_end;
-        int v = live ? st_tile : t_first;
-        const int co0 = (v % a.coTiles) * CO_T;
-        v /= a.coTiles;
-        const int tx = v % a.tilesX;
-        v /= a.tilesX;
-        const int ty = v % a.tilesY;
-        const int b = v / a.tilesY;
-        const int y0 = ty * ROWS, x0 = tx * TW;
+        const auto [co0, tx, ty, b, y0, x0] = sp_tile(live ? st_tile : t_first, a.coTiles, a.tilesX, a.tilesY);
         // (W16: b is the image PAIR; the resource spans both images, the second one's offset rides in the lane's byte offset)
         xr = sp_rsrc4(reinterpret_cast<const unsigned*>(a.xs) + (int64_t)(W16 ? 2 * b : b) * a.xs_bs,
                       (W16 ? a.xs_bs * 4 : 0) + (int64_t)a.Cin * HW * (PM == 2 ? 2 : 4));
@@ -813,7 +804,7 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
     auto act_fetch = [&](int t) __attribute__((always_inline)) {
         if (tid < 192 && t < t_end) {
             const int k = tid >> 6;                                 // 0: mean, 1: sc, 2: sh   (save rows 0, 2, 3)
-            cf_next = a.act_save[(int64_t)(k + (k > 0)) * a.Cout + (t % a.coTiles) * CO_T + (tid & 63)];
+            cf_next = a.act_save[(int64_t)(k + (k > 0)) * a.Cout + sp_tile(t, a.coTiles, a.tilesX, a.tilesY).co0 + (tid & 63)];
         }
     };
     if constexpr (ACT) act_fetch(t_first);
@@ -923,14 +914,7 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
             for (int n = 0; n < NT; ++n)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[m][n][r] *= acc_scale;
-        int v = tile;
-        const int co0 = (v % a.coTiles) * CO_T;
-        v /= a.coTiles;
-        const int tx = v % a.tilesX;
-        v /= a.tilesX;
-        const int ty = v % a.tilesY;
-        const int b = v / a.tilesY;
-        const int y0 = ty * ROWS, x0 = tx * TW;
+        const auto [co0, tx, ty, b, y0, x0] = sp_tile(tile, a.coTiles, a.tilesX, a.tilesY);
         if constexpr (ST) {
             float* sc = reinterpret_cast<float*>(lds + 2 * BUF);       // [8 waves][64 channels][mean, M2]
             constexpr float npw = (float)(NT * 32), inv_npw = 1.f / npw;
@@ -1091,8 +1075,9 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
 // ------------------------------------------------------------------ the same tile on v_mfma_f32_16x16x32 (round 5)
 // MI355X_MICROARCH.md, 'DVFS give-back' (7): in clock-limited MFMA loops the chip holds a higher clock on the 16x16x32 shape than on
 // 32x32x16 at equal cycles per FLOP (half the accumulator traffic per FLOP).  Measured in this kernel (profiles/r05_mfma_shape_ab.md):
-// the same matrix work issued as 16x16x32 runs 8-9 % faster on every layer shape.  So: the block, its LDS image, the DMA schedule and
-// the persistent tile walk of conv3x3_split_pre_kernel, with the wave's 64 channels x 2 rows x 32 pixels held as SIXTEEN 16 x 16
+// the same matrix work issued as 16x16x32 runs 8-9 % faster on every layer shape.  So: the block, its LDS image (SpPreCfg) and the DMA
+// schedule of conv3x3_split_pre_kernel and the family's persistent tile walk (sp_tile_range, sp_tile), with the wave's 64 channels
+// x 2 rows x 32 pixels held as SIXTEEN 16 x 16
 // accumulators, M = 16 pixels of a row (A = input fragment), N = 16 output channels (B = weight fragment): a lane then owns four
 // CONSECUTIVE pixels of one channel -- the epilogue stores float4s (16 store instructions per wave and tile instead of 64) and the
 // BatchNorm statistics need in-lane sums plus two cross-lane steps per channel tile (the 32x32 form: 5 DPP steps per register).
@@ -1112,23 +1097,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     using C = SpPreCfg<W16>;
     static_assert(C::NW == 8 && C::NT == 2, "conv3x3_pre16_kernel: 8 waves of 2 rows");
     constexpr int NT = 2, IN_COLS = C::IN_COLS, NWI = C::NWI, CO_T = C::CO_T, NPIXP = C::NPIXP;
-    constexpr int BUF = C::BUF_SLOTS, IN_PART = C::IN_PART, ROWS = C::ROWS, TW = C::TW;
+    constexpr int BUF = C::BUF_SLOTS, IN_PART = C::IN_PART;
     constexpr int NII = (2 * IN_PART + 511) / 512;
     constexpr int CH_OFF = W16 ? 18 : 16;                              // column of the second 16-pixel tile in the halo image
     constexpr int NSTEP = PM == 2 ? 9 : 14;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];
     u32x4s* lds = reinterpret_cast<u32x4s*>(smem_s);
 
-    const int ntiles = a.tilesX * a.tilesY * a.B * a.coTiles;
-    int t_first, t_end, t_stride;
-    {
-        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        const int q = ntiles >> 3, r = ntiles & 7;
-        const int start = xcd * q + min(xcd, r);
-        t_stride = (gridDim.x + 7 - xcd) >> 3;
-        t_first = start + j;
-        t_end = start + q + (xcd < r ? 1 : 0);
-    }
+    int t_first, t_end, t_stride;                                      // tile list order: see sp_tile_range
+    sp_tile_range(a.tilesX * a.tilesY * a.B * a.coTiles, t_first, t_end, t_stride);
     if (t_first >= t_end) return;
 
     const int tid = threadIdx.x, lane = tid & 63, wn = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1153,14 +1130,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     unsigned cin_bytes = 0, cw_bytes = 0;
     auto setup_stage = [&]() __attribute__((always_inline)) {
         const bool live = st_tile < t_end;
-        int v = live ? st_tile : t_first;
-        const int co0 = (v % a.coTiles) * CO_T;
-        v /= a.coTiles;
-        const int tx = v % a.tilesX;
-        v /= a.tilesX;
-        const int ty = v % a.tilesY;
-        const int b = v / a.tilesY;
-        const int y0 = ty * ROWS, x0 = tx * TW;
+        const auto [co0, tx, ty, b, y0, x0] = sp_tile(live ? st_tile : t_first, a.coTiles, a.tilesX, a.tilesY);
         xr = sp_rsrc4(reinterpret_cast<const unsigned*>(a.xs) + (int64_t)(W16 ? 2 * b : b) * a.xs_bs,
                       (W16 ? a.xs_bs * 4 : 0) + (int64_t)a.Cin * HW * (PM == 2 ? 2 : 4));
 #pragma unroll
@@ -1312,14 +1282,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
             for (int n = 0; n < NT; ++n)
 #pragma unroll
                 for (int ch = 0; ch < 2; ++ch) acc[ct][n][ch] *= acc_scale;
-        int v = tile;
-        const int co0 = (v % a.coTiles) * CO_T;
-        v /= a.coTiles;
-        const int tx = v % a.tilesX;
-        v /= a.tilesX;
-        const int ty = v % a.tilesY;
-        const int b = v / a.tilesY;
-        const int y0 = ty * ROWS, x0 = tx * TW;
+        const auto [co0, tx, ty, b, y0, x0] = sp_tile(tile, a.coTiles, a.tilesX, a.tilesY);
         if constexpr (ST) {
             // BatchNorm (n, mean, M2) record of the tile per channel.  Lane = channel r16 of tile ct, 16 pixel values in registers:
             // own pivot-shifted sums -> (mean, M2) of 16; the four lane groups merged pairwise (equal counts: Chan's formula); the
@@ -1537,6 +1500,19 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     }
 }
 
+// The launch of a persistent tile-walking kernel: its dynamic LDS size once per device, then one 8-wave block per CU -- a multiple of the
+// 8 XCDs (sp_tile_range), no more blocks than tiles rounded up to 8.  `once`: the kernel instance's own flag
+template <class Args>
+int sp_launch_persistent(void (*kern)(Args), PerDeviceOnce& once, int lds_bytes, int64_t tiles, int block, const char* name, const Args& a, hipStream_t st) {
+    if (once.first()) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    }
+    const int64_t resident = (int64_t)device_cu_count();
+    const int64_t blocks = std::min<int64_t>((tiles + 7) / 8 * 8, std::max<int64_t>(8, resident / 8 * 8));
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(block), lds_bytes, st, a);
+    return check_launch(name);
+}
+
 template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false>
 int launch_split_pre(SpPreArgs a, hipStream_t st) {
     using C = SpPreCfg<W16>;
@@ -1556,13 +1532,7 @@ int launch_split_pre(SpPreArgs a, hipStream_t st) {
     if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD>;      // (constexpr: the instances not dispatched are not built)
     else kern = conv3x3_split_pre_kernel<ST, PM, W16, ACT>;
     static PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    }
-    const int64_t resident = (int64_t)device_cu_count();
-    const int64_t blocks = std::min<int64_t>((tiles + 7) / 8 * 8, std::max<int64_t>(8, resident / 8 * 8));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(C::NW * 64), LDS_BYTES, st, a);
-    return check_launch(ACT ? "conv3x3_split_pre_act_kernel" : "conv3x3_split_pre_kernel");
+    return sp_launch_persistent(kern, attr_once, LDS_BYTES, tiles, C::NW * 64, ACT ? "conv3x3_split_pre_act_kernel" : "conv3x3_split_pre_kernel", a, st);
 }
 
 int split_nparts(int B, int H, int W) {
@@ -1580,16 +1550,8 @@ int launch_split(SpArgs a, hipStream_t st) {
     a.coTiles = cdiv(a.Cout, C::CO_T);
     const int64_t tiles = (int64_t)a.B * a.tilesX * a.tilesY * a.coTiles;
     ONET_REQUIRE(tiles > 0 && tiles < (1ll << 31), "conv3x3_split: tile count %lld out of range", (long long)tiles);
-    auto kern = conv3x3_split_kernel<ST, NORM, F16>;
     static PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    }
-    // persistent grid: one 8-wave block per CU, a multiple of the 8 XCDs
-    const int64_t resident = (int64_t)device_cu_count();
-    const int64_t blocks = std::min<int64_t>((tiles + 7) / 8 * 8, std::max<int64_t>(8, resident / 8 * 8));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), LDS_BYTES, st, a);
-    return check_launch("conv3x3_split_kernel");
+    return sp_launch_persistent(conv3x3_split_kernel<ST, NORM, F16>, attr_once, LDS_BYTES, tiles, 512, "conv3x3_split_kernel", a, st);
 }
 
 int split_fwd(const float* x, int64_t x_bs, const void* wq, float* z, int64_t z_bs, int B, int Cin, int Cout, int H, int W,
@@ -1671,11 +1633,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_split_wgrad_kernel(SwArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned dz_lds[2 * 2 * SR_DZ_PART];     // [buf][part][COT co][SR_SDZ]
     __shared__ __attribute__((aligned(16))) unsigned x_lds[2 * SR_X_PART];           // [part][64 ci][SR_SX]
 
-    int bid;
-    {
-        const int n = gridDim.x, q = n >> 3, r = n & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    int bid = xcd_block_id();
     const int tiles = a.ciTiles * a.coTiles;
     const int ks = bid / tiles, tile = bid % tiles;
     const int ci0 = (tile % a.ciTiles) * 64, co0 = (tile / a.ciTiles) * COT;
@@ -1990,11 +1948,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_pre16_kernel(SwPreArgs a
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem_w;
     const unsigned x_base = lds0, dz_base = lds0 + 4 * X_ROW * 16;
 
-    int bid;
-    {
-        const int n = gridDim.x, q = n >> 3, r = n & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    int bid = xcd_block_id();
     const int tiles = a.ciTiles * a.coTiles;
     const int ks = bid / tiles, tile = bid % tiles;
     const int ci0 = (tile % a.ciTiles) * 64, co0 = (tile / a.ciTiles) * COT;
@@ -2394,6 +2348,19 @@ int onet_split_pack_act(const float* x, int64_t x_bs, void* xs, int64_t xs_bs, i
     return check_launch("split_pack_act_kernel");
 }
 
+// The checks on the pre-split operand xs (activation or output gradient, batch stride xs_bs) and on the sizes that the four pre-split
+// entries share: 0, or ONET_EINVAL with the entry's name in the message.  What is peculiar to one entry is checked there
+static int pre_operand_checks(const char* entry, const void* xs, int64_t xs_bs, int wq_f16, int Cin, int Cout, int H, int W) {
+    ONET_REQUIRE((Cin % (wq_f16 == 2 ? 32 : 16)) == 0, "%s: Cin must be a multiple of 16 (32 for plain bf16 operands)", entry);
+    ONET_REQUIRE((xs_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(xs) & 15) == 0, "%s: 16-byte aligned slots required", entry);
+    ONET_REQUIRE(xs_bs >= (int64_t)Cin * H * W / (wq_f16 == 2 ? 2 : 1), "%s: batch stride too small", entry);
+    ONET_REQUIRE((int64_t)(Cin + 32) * H * W * 4 < (1ll << 31) && (int64_t)(Cin + 32) * 2 * 9 * Cout * 2 < (1ll << 31),
+                 "%s: operand exceeds the 2 GiB buffer-resource range", entry);
+    // 16-pixel maps: a tile's buffer resource spans an image pair
+    ONET_REQUIRE(W != 16 || xs_bs * 4 + (int64_t)Cin * H * W * 4 < (1ll << 31), "%s: image pair exceeds the buffer-resource range", entry);
+    return 0;
+}
+
 // BatchNorm statistics records of onet_conv3x3_split_fwd_pre: one per 16 x 32 tile; 16-pixel-wide maps: one per image PAIR and 16 rows
 int onet_conv3x3_split_pre_nparts(int B, int H, int W) {
     if (W == 16) return (B > 0 && (B % 2) == 0 && (H % 16) == 0) ? (B / 2) * (H / 16) : 0;
@@ -2409,20 +2376,16 @@ int onet_conv3x3_split_fwd_pre(const void* xs, int64_t xs_bs, const void* x_amax
     ONET_REQUIRE(xs && wq && z, "conv3x3_split_fwd_pre: null pointer");
     ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && (W > 16 || (W == 16 && (B % 2) == 0 && (H % 16) == 0)),
                  "conv3x3_split_fwd_pre: bad shape (maps wider than 16 pixels, or exactly 16 wide with an even batch and H %% 16 == 0)");
-    ONET_REQUIRE((Cin % (wq_f16 == 2 ? 32 : 16)) == 0, "conv3x3_split_fwd_pre: Cin must be a multiple of 16 (32 for plain bf16 operands)");
     // plain bf16 operands take conv3x3_pre16_kernel at every width, and its epilogue stores whole 4-pixel vectors of a row
     ONET_REQUIRE(wq_f16 != 2 || (W % 4) == 0, "conv3x3_split_fwd_pre: plain bf16 operands need W %% 4 == 0");
-    ONET_REQUIRE((xs_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(xs) & 15) == 0, "conv3x3_split_fwd_pre: 16-byte aligned slots required");
-    ONET_REQUIRE(xs_bs >= (int64_t)Cin * H * W / (wq_f16 == 2 ? 2 : 1) && z_bs >= (int64_t)Cout * H * W, "conv3x3_split_fwd_pre: batch stride too small");
-    ONET_REQUIRE((int64_t)(Cin + 32) * H * W * 4 < (1ll << 31) && (int64_t)(Cin + 32) * 2 * 9 * Cout * 2 < (1ll << 31),
-                 "conv3x3_split_fwd_pre: operand exceeds the 2 GiB buffer-resource range");
+    if (const int rc = pre_operand_checks("conv3x3_split_fwd_pre", xs, xs_bs, wq_f16, Cin, Cout, H, W)) return rc;
+    ONET_REQUIRE(z_bs >= (int64_t)Cout * H * W, "conv3x3_split_fwd_pre: batch stride too small");
     SpPreArgs a{xs, xs_bs, (const __bf16*)wq, (float*)z, z_bs, B, Cin, Cout, H, W, 0, 0, 0, part, (const unsigned*)x_amax, scale_always,
                 (const unsigned*)x_amax2, split_ch};
     a.z16 = z_bf16 ? 1 : 0;
     if (part) ONET_REQUIRE(onet_conv3x3_split_pre_nparts(B, H, W) > 0, "conv3x3_split_fwd_pre: statistics need a map made of full 16 x 32 tiles");
     hipStream_t st = as_stream(stream);
     if (W == 16) {
-        ONET_REQUIRE(xs_bs * 4 + (int64_t)Cin * H * W * 4 < (1ll << 31), "conv3x3_split_fwd_pre: image pair exceeds the buffer-resource range");
         if (wq_f16 == 2) return part ? launch_split_pre<true, 2, true>(a, st) : launch_split_pre<false, 2, true>(a, st);
         if (wq_f16) return part ? launch_split_pre<true, 1, true>(a, st) : launch_split_pre<false, 1, true>(a, st);
         return part ? launch_split_pre<true, 0, true>(a, st) : launch_split_pre<false, 0, true>(a, st);
@@ -2445,14 +2408,12 @@ int onet_conv3x3_split_dgrad_pre_bnreduce(const void* dzs, int64_t dzs_bs, const
     // a tile of fewer than four chunks is too short to cover the epilogue's z loads (plain bf16 operands, 64 channels of dz: two chunks --
     // measured at BASELINE configs[2]: the fused launches cost more than the reduce pass they replace)
     if (Cin / (wq_f16 == 2 ? 32 : 16) < 4) return 1;
-    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && (Cin % (wq_f16 == 2 ? 32 : 16)) == 0, "conv3x3_split_dgrad_pre_bnreduce: bad shape");
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0, "conv3x3_split_dgrad_pre_bnreduce: bad shape");
     ONET_REQUIRE(group_images >= 0 && (group_images == 0 || B % group_images == 0), "conv3x3_split_dgrad_pre_bnreduce: bad statistics groups");
-    ONET_REQUIRE((dzs_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(dzs) & 15) == 0 && (z_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(z_prev) & (z_bf16 ? 7 : 15)) == 0 &&
-                 (da_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(da) & 15) == 0, "conv3x3_split_dgrad_pre_bnreduce: 16-byte aligned rows required");
-    ONET_REQUIRE(dzs_bs >= (int64_t)Cin * H * W / (wq_f16 == 2 ? 2 : 1) && da_bs >= (int64_t)Cout * H * W && z_bs >= (int64_t)Cout * H * W,
-                 "conv3x3_split_dgrad_pre_bnreduce: batch stride too small");
-    ONET_REQUIRE((int64_t)(Cin + 32) * H * W * 4 < (1ll << 31) && (int64_t)(Cin + 32) * 2 * 9 * Cout * 2 < (1ll << 31),
-                 "conv3x3_split_dgrad_pre_bnreduce: operand exceeds the 2 GiB buffer-resource range");
+    if (const int rc = pre_operand_checks("conv3x3_split_dgrad_pre_bnreduce", dzs, dzs_bs, wq_f16, Cin, Cout, H, W)) return rc;
+    ONET_REQUIRE((z_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(z_prev) & (z_bf16 ? 7 : 15)) == 0 && (da_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(da) & 15) == 0,
+                 "conv3x3_split_dgrad_pre_bnreduce: 16-byte aligned rows required");
+    ONET_REQUIRE(da_bs >= (int64_t)Cout * H * W && z_bs >= (int64_t)Cout * H * W, "conv3x3_split_dgrad_pre_bnreduce: batch stride too small");
     SpPreArgs a{dzs, dzs_bs, (const __bf16*)wq, da, da_bs, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)dz_amax, scale_always, nullptr, 0};
     a.rd_z = (const float*)z_prev;
     a.rd_z16 = z_bf16 ? 1 : 0;
@@ -2462,10 +2423,7 @@ int onet_conv3x3_split_dgrad_pre_bnreduce(const void* dzs, int64_t dzs_bs, const
     a.rd_rec = rec4;
     a.rd_amax = (unsigned*)da_amax;
     hipStream_t st = as_stream(stream);
-    if (W == 16) {
-        ONET_REQUIRE(dzs_bs * 4 + (int64_t)Cin * H * W * 4 < (1ll << 31), "conv3x3_split_dgrad_pre_bnreduce: image pair exceeds the buffer-resource range");
-        return launch_split_pre<false, 2, true, true>(a, st);
-    }
+    if (W == 16) return launch_split_pre<false, 2, true, true>(a, st);
     if (wq_f16 == 2) return launch_split_pre<false, 2, false, true>(a, st);
     return wq_f16 ? launch_split_pre<false, 1, false, true>(a, st) : launch_split_pre<false, 0, false, true>(a, st);
 }
@@ -2476,16 +2434,13 @@ int onet_conv3x3_split_dgrad_pre_slots(const void* dzs, int64_t dzs_bs, const vo
                                        float* da, int64_t da_bs, void* daP, int64_t daP_bs, int ch0, const void* daP_amax, int B, int Cin,
                                        int Cout, int H, int W, void* stream) {
     ONET_REQUIRE(dzs && wq && da && daP && (daP_amax || wq_f16 == 2) && (wq_f16 == 1 || wq_f16 == 2), "conv3x3_split_dgrad_pre_slots: bad args");
-    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W >= 32 && (W % 32) == 0 && (H % 16) == 0 && (Cin % (wq_f16 == 2 ? 32 : 16)) == 0,
-                 "conv3x3_split_dgrad_pre_slots: maps made of full 16 x 32 tiles, Cin %% 16 == 0 (32: plain bf16)");
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W >= 32 && (W % 32) == 0 && (H % 16) == 0,
+                 "conv3x3_split_dgrad_pre_slots: maps made of full 16 x 32 tiles");
     ONET_REQUIRE(ch0 > 0 && ch0 < Cout && (ch0 % 64) == 0 && (Cout % 64) == 0, "conv3x3_split_dgrad_pre_slots: ch0 and Cout must be multiples of 64");
-    ONET_REQUIRE((dzs_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(dzs) & 15) == 0 && (daP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(daP) & 15) == 0,
-                 "conv3x3_split_dgrad_pre_slots: 16-byte aligned slots required");
-    ONET_REQUIRE(dzs_bs >= (int64_t)Cin * H * W / (wq_f16 == 2 ? 2 : 1) && da_bs >= (int64_t)ch0 * H * W &&
-                     daP_bs >= (int64_t)(Cout - ch0) * H * W / (wq_f16 == 2 ? 2 : 1),
+    if (const int rc = pre_operand_checks("conv3x3_split_dgrad_pre_slots", dzs, dzs_bs, wq_f16, Cin, Cout, H, W)) return rc;
+    ONET_REQUIRE((daP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(daP) & 15) == 0, "conv3x3_split_dgrad_pre_slots: 16-byte aligned slots required");
+    ONET_REQUIRE(da_bs >= (int64_t)ch0 * H * W && daP_bs >= (int64_t)(Cout - ch0) * H * W / (wq_f16 == 2 ? 2 : 1),
                  "conv3x3_split_dgrad_pre_slots: batch stride too small");
-    ONET_REQUIRE((int64_t)(Cin + 32) * H * W * 4 < (1ll << 31) && (int64_t)(Cin + 32) * 2 * 9 * Cout * 2 < (1ll << 31),
-                 "conv3x3_split_dgrad_pre_slots: operand exceeds the 2 GiB buffer-resource range");
     SpPreArgs a{dzs, dzs_bs, (const __bf16*)wq, da, da_bs, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)dz_amax, scale_always, nullptr, 0};
     a.zP = daP;
     a.zP_bs = daP_bs;
@@ -2507,12 +2462,9 @@ int onet_conv3x3_split_fwd_pre_act(const void* xs, int64_t xs_bs, const void* x_
     ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv3x3_split_fwd_pre_act: bad shape");
     if (W < 32 || (W % 32) || (H % 16) || (Cin % 16) || (Cout % 64)) return 1;
     ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "conv3x3_split_fwd_pre_act: split_ch must be a multiple of 32 inside Cin");
-    ONET_REQUIRE((xs_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(xs) & 15) == 0 && (aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0,
-                 "conv3x3_split_fwd_pre_act: 16-byte aligned slots required");
-    ONET_REQUIRE(xs_bs >= (int64_t)Cin * H * W && aP_bs >= (int64_t)Cout * H * W && (!a || a_bs >= (int64_t)Cout * H * W),
-                 "conv3x3_split_fwd_pre_act: batch stride too small");
-    ONET_REQUIRE((int64_t)(Cin + 32) * H * W * 4 < (1ll << 31) && (int64_t)(Cin + 32) * 2 * 9 * Cout * 2 < (1ll << 31),
-                 "conv3x3_split_fwd_pre_act: operand exceeds the 2 GiB buffer-resource range");
+    if (const int rc = pre_operand_checks("conv3x3_split_fwd_pre_act", xs, xs_bs, 1, Cin, Cout, H, W)) return rc;
+    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "conv3x3_split_fwd_pre_act: 16-byte aligned slots required");
+    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W && (!a || a_bs >= (int64_t)Cout * H * W), "conv3x3_split_fwd_pre_act: batch stride too small");
     SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)x_amax, scale_always,
                 (const unsigned*)x_amax2, split_ch};
     p.zP = aP;

@@ -221,11 +221,7 @@ static __device__ __forceinline__ void wino4_body(const Wino4Args& a, float* sme
     constexpr int NWK = (NPIECE + 7) / 8;             // 5 pieces for waves 0..3, 4 for the rest
     constexpr int PG = RH * 2 + CH;
 
-    int bid;
-    {   // XCD-aware tile order (see conv_mfma.hip)
-        const int n = gridDim.x, q = n >> 3, r = n & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    int bid = xcd_block_id();                         // XCD-aware tile order (see conv_mfma.hip)
     const int tx = bid % a.tilesX;
     bid /= a.tilesX;
     const int ty = bid % a.tilesY;

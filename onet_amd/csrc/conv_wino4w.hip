@@ -75,11 +75,7 @@ struct W4C {
 template <int RH, int CH, int W16>
 static __device__ __forceinline__ void wino4w_body(const W4wArgs a, float* lds) {
     constexpr int W4_XROW = W4C<W16>::XROW, W4_SX = W4C<W16>::SX, W4_BUF_FLOATS = W4C<W16>::BUF_FLOATS;
-    int bid;
-    {
-        const int n = gridDim.x, q = n >> 3, r = n & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    int bid = xcd_block_id();
     const int tiles = a.ciTiles * a.coTiles;
     const int ks = bid / tiles, tile = bid % tiles;
     const int ci0 = (tile % a.ciTiles) * 32, co0 = (tile / a.ciTiles) * 64;

@@ -140,11 +140,6 @@ struct GArgs {
     const unsigned* out_slots;   // ... whose fp16 parts are those of 2^k y, k = the guard exponent these magnitude slots select (NULL: k = 0)
 };
 
-__device__ __forceinline__ int xcd_order(int n) {
-    const int q = n >> 3, r = n & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
-
 // sum over the 32 lanes of a wave half, valid in lanes 31 / 63 (DPP row rotations + row broadcast, as in conv_wino4.hip)
 #define ONET_G_DPP_ADD(v, ctrl, rmask) \
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, rmask, 0xf, false))
@@ -167,7 +162,7 @@ constexpr int TILE_F = KC * 128;       // floats of one operand tile
 template <int MODE, int PREC = 0>
 __global__ __launch_bounds__(256, 2) void convt_gemm_kernel(GArgs g) {
     __shared__ __attribute__((aligned(16))) float lds[2 * 2 * TILE_F];      // [buf][A | B]
-    int bid = xcd_order(gridDim.x);
+    int bid = xcd_block_id();
     const int mt = bid % g.mTiles;                 // m tile fastest: the blocks of one pixel tile share its B rows in L2
     const int nt = bid / g.mTiles;
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform (SGPR)
@@ -374,7 +369,7 @@ constexpr int WB_F = 64 * 2 * KP;               // B tile: 64 (c, di) rows x (32
 template <int PREC = 0>
 __global__ __launch_bounds__(256, 2) void convt_wgrad_gemm_kernel(GArgs g) {
     __shared__ __attribute__((aligned(16))) float lds[2 * (WA_F + WB_F)];
-    int bid = xcd_order(gridDim.x);
+    int bid = xcd_block_id();
     const int tiles = g.mTiles * g.nTiles;
     const int ks = bid / tiles, tile = bid % tiles;
     const int mt = tile % g.mTiles, nt = tile / g.mTiles;
@@ -588,7 +583,7 @@ __global__ __launch_bounds__(256, SLOT_OCC) void convt_slot_fwd_kernel(SArgs g) 
                                                    // deeper ring -- timing builds without MFMAs / without stores: 0.27 / 0.37 of 0.53 ms on
                                                    // the 128-channel level, unchanged by the ring depth
     __shared__ __attribute__((aligned(16))) u32x4g lds[NST * 2 * TILE];     // [stage][A | B]
-    const int bid = xcd_order(gridDim.x);
+    const int bid = xcd_block_id();
     const int mt = bid % g.mTiles;                 // m tile fastest: the blocks of one pixel tile share its x slots in L2
     const int nt = bid / g.mTiles;
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -757,7 +752,7 @@ __global__ __launch_bounds__(256, SLOT_OCC) void convt_slot_dgrad_kernel(SDArgs 
     constexpr int NPC = TILE / 256;
     constexpr int NST = SLOT_NST;
     __shared__ __attribute__((aligned(16))) u32x4g lds[NST * 2 * TILE];
-    const int bid = xcd_order(gridDim.x);
+    const int bid = xcd_block_id();
     const int mt = bid % g.mTiles, nt = bid / g.mTiles;
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wid >> 1, wc = wid & 1, l31 = lane & 31, kh = lane >> 5;
@@ -925,7 +920,7 @@ __global__ __launch_bounds__(SwCfg<BIG>::NWAVE * 64, BIG ? 1 : 2) void convt_slo
     constexpr int LOG_CP = __builtin_ctz(CP);
     extern __shared__ __attribute__((aligned(16))) unsigned char sw_smem[];
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)sw_smem;
-    const int bid = xcd_order(gridDim.x);
+    const int bid = xcd_block_id();
     const int tiles = g.mTiles * g.nTiles;
     const int ks = bid / tiles, tile = bid % tiles;
     const int mt = tile % g.mTiles, nt = tile / g.mTiles;

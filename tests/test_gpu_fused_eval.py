@@ -15,6 +15,8 @@ import torch
 
 from oracle import onet_oracle as orc
 
+from multi_tile import multi_tile_cout
+
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-4          # eval outputs, of each tensor's largest magnitude (tests/test_gpu_inference.py)
@@ -104,12 +106,15 @@ def _check_fused(dev, P, w, save, x_slots, x_slots2=None, split_ch=0, want_guard
     return v
 
 
-@pytest.mark.parametrize("B,Cin,Cout,H,W", [(2, 64, 128, 128, 128), (1, 256, 256, 64, 64), (1, 1024, 512, 32, 32)],
-                         ids=["64-128@128", "256-256@64", "1024-512@32"])
+@pytest.mark.parametrize("B,Cin,Cout,H,W", [(2, 64, 128, 128, 128), (1, 256, 256, 64, 64), (1, 1024, 512, 32, 32), (3, 32, None, 48, 96)],
+                         ids=["64-128@128", "256-256@64", "1024-512@32", "multi-tile"])
 def test_fused_epilogue_bit_identical(dev, B, Cin, Cout, H, W):
     """64 -> 128 at 128 x 128, 256 -> 256 at 64 x 64, 1024 -> 512 at 32 x 32.  Measured looseness of the bound (bound / max a): 29x, 69x,
-    136x -- it grows with sum |w| over the effective gain, i.e. with sqrt(Cin)."""
+    136x -- it grows with sum |w| over the effective gain, i.e. with sqrt(Cin).  multi-tile: Cout = multi_tile_cout(27), where blocks
+    walk more than one tile and the coefficient double buffer turns over."""
     from onet_amd import ops
+    if Cout is None:
+        Cout = multi_tile_cout(B * (H // 16) * (W // 32))
     x = rnd(B, Cin, H, W, seed=200).abs().to(dev)
     w = rnd(Cout, Cin, 3, 3, seed=201, scale=(2.0 / (Cin * 9)) ** 0.5)
     s = ops.absmax_slots(x)

@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from multi_tile import multi_tile_cout
+
 pytestmark = pytest.mark.gpu
 
 
@@ -207,13 +209,16 @@ def test_split_f16_range_guard(dev):
 
 
 @pytest.mark.parametrize("B,Cin,Cout,H,W,G", [(4, 64, 64, 32, 64, 2), (2, 32, 48, 20, 40, 1), (4, 128, 128, 16, 32, 2), (6, 48, 256, 33, 96, 1),
-                                               (8, 64, 128, 16, 16, 2), (2, 16, 64, 48, 128, 2)])
+                                               (8, 64, 128, 16, 16, 2), (2, 16, 64, 48, 128, 2),
+                                               (3, 32, None, 48, 96, 1)])     # Cout = multi_tile_cout(27): blocks walk more than one tile
 def test_conv3x3_split_norm_on_load_is_bit_identical(dev, B, Cin, Cout, H, W, G):
     """Normalise on load: the split forward kernel and the split weight-gradient kernel given the PRE-activation of the unit
     below plus its BatchNorm coefficients (one or two statistics groups) must produce, bit for bit, what they produce on the
     activation bn_relu_apply materialises -- interior, zero padding (the halo must stay zero, not relu(shift)), ragged tiles,
     the 128-channel weight-gradient tiles, 32- / 16-pixel-wide maps (weight gradient only at 16)."""
     from onet_amd import ops
+    if Cout is None:
+        Cout = multi_tile_cout(B * (H // 16) * (W // 32))
     zp = rnd(B, Cin, H, W, seed=41).to(dev)
     save = torch.empty(G, 4, Cin)
     g = torch.Generator().manual_seed(42)
@@ -240,13 +245,16 @@ def test_conv3x3_split_norm_on_load_is_bit_identical(dev, B, Cin, Cout, H, W, G)
 
 
 @pytest.mark.parametrize("B,Cin,Cout,H,W", [(2, 64, 64, 40, 48), (1, 32, 128, 64, 64), (3, 16, 36, 33, 28), (2, 128, 80, 16, 96),
-                                             (9, 48, 64, 32, 32), (1, 512, 64, 17, 40)])
+                                             (9, 48, 64, 32, 32), (1, 512, 64, 17, 40),
+                                             (3, 32, None, 48, 96)])          # Cout = multi_tile_cout(27): an uneven tile walk
 def test_conv3x3_split_fwd_dgrad_stats(dev, B, Cin, Cout, H, W, monkeypatch):
     """conv_split.hip -- fp32 convolution on the bf16 matrix cores by operand splitting (x = hi + mid, w = hi + mid, three MFMAs
     per term) -- against the fp64 convolution: forward and input-gradient orientation at 2e-5 of the output scale (measured
     5e-6; the fp32 Winograd F(4x4) kernel it replaces in the default dispatch: 1e-5 .. 4e-5), ragged edges, channel tails,
     several tiles per persistent block (B = 9), long reductions; fused BatchNorm statistics == the separate pass."""
     from onet_amd import _lib, ops
+    if Cout is None:
+        Cout = multi_tile_cout(B * (H // 16) * (W // 32))
     x = rnd(B, Cin, H, W, seed=1)
     w = rnd(Cout, Cin, 3, 3, seed=2, scale=(2.0 / (Cin * 9)) ** 0.5)
     g = rnd(B, Cout, H, W, seed=3)

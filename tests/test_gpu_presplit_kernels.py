@@ -12,6 +12,9 @@ Forward, onet_conv3x3_split_fwd_pre -> launch_split_pre<ST, PM, W16>.  PM: 0 bf1
 bf16 pack (wq_f16 = 2); ST: a statistics buffer is passed (`stats=`); W16: W == 16 (even B, H % 16 == 0).  Kernel: conv3x3_pre16_kernel
 where P16 = RD || PM == 2 || (ST && !W16), else conv3x3_split_pre_kernel (32x32x16).  Each instance runs on the shapes of
 FWD_SHAPES[W16]; ragged: W = 48 with H = 20 (partial column tile and row band, ST = 0 only), Cout = 72 / 40 (partial Cout tile).
+Those shapes have at most a few dozen tiles, one per persistent block; the multi-tile shapes (Cout = multi_tile_cout(..), derived from
+the device's CU count) give the blocks two tiles or one, unevenly -- once per kernel and path that walks tiles, in the forward, fused-reduce
+and pre-split-half tables here and in the fp32-in and fused-eval kernel tests of test_gpu_ops.py / test_gpu_fused_eval.py.
 
     ST PM W16  kernel       test
     0  0  0    split_pre    test_forward_instance[bf16x2-wide-*], test_presplit_entries_fuzz
@@ -60,6 +63,8 @@ import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+from multi_tile import multi_tile_cout
 
 pytestmark = pytest.mark.gpu
 
@@ -189,13 +194,19 @@ def unsplit(P, scale=1.0):
 FWD_SHAPES = {
     False: [(2, 64, 40, 20, 48, False),        # partial column tile, H % 16 != 0, partial Cout tile (no statistics: not full tiles)
             (2, 64, 72, 32, 64, True),         # partial Cout tile
-            (1, 160, 64, 16, 96, True)],       # three column tiles, > 128 channels
+            (1, 160, 64, 16, 96, True),        # three column tiles, > 128 channels
+            (3, 32, None, 48, 96, True)],      # 27 spatial tiles, Cout = multi_tile_cout(27): more than one tile per block
     True: [(4, 64, 40, 16, 16, True),          # partial Cout tile
-           (2, 160, 64, 32, 16, True)],
+           (2, 160, 64, 32, 16, True),
+           (6, 32, None, 48, 16, True)],       # 9 pair-tiles, Cout = multi_tile_cout(9)
 }
+# the multi-tile shapes run once per kernel and path that walks tiles: conv3x3_split_pre_kernel without (fp16 parts, wide) and with
+# statistics (W16), conv3x3_pre16_kernel with statistics (fp16 parts, wide) and on plain bf16 operands (W16)
+MULTI_TILE_FWD = {(1, False), (1, True), (2, True)}
 
 
-FWD_CASES = [(pm, w16, i) for pm in (0, 1, 2) for w16 in (False, True) for i in range(len(FWD_SHAPES[w16]))]
+FWD_CASES = [(pm, w16, i) for pm in (0, 1, 2) for w16 in (False, True) for i in range(len(FWD_SHAPES[w16]))
+             if FWD_SHAPES[w16][i][2] is not None or (pm, w16) in MULTI_TILE_FWD]
 
 
 @pytest.mark.parametrize("pm,w16,shape", FWD_CASES, ids=[f"{PM_NAMES[p]}-{'w16' if w else 'wide'}-{i}" for p, w, i in FWD_CASES])
@@ -204,6 +215,8 @@ def test_forward_instance(dev, pm, w16, shape):
     the statistics records against the fp64 mean and variance; both launches store the same z bit for bit."""
     from onet_amd import _lib
     B, Cin, Cout, H, W, st = FWD_SHAPES[w16][shape]
+    if Cout is None:
+        Cout = multi_tile_cout((B // 2 if w16 else B * (W // 32)) * (H // 16))
     x = rnd(B, Cin, H, W, seed=101)
     w = rnd(Cout, Cin, 3, 3, seed=102, scale=(2.0 / (Cin * 9)) ** 0.5)
     z64 = conv64(ref_op(x, pm), ref_op(w, pm))
@@ -230,12 +243,13 @@ def test_forward_instance(dev, pm, w16, shape):
 RD_SHAPES = {
     (0, False): [(2, 64, 80, 32, 64, 1), (4, 128, 64, 16, 96, 2)],
     (1, False): [(2, 64, 80, 32, 64, 1), (4, 192, 64, 16, 96, 2)],
-    (2, False): [(2, 128, 80, 32, 64, 1), (4, 160, 64, 16, 96, 2)],
+    (2, False): [(2, 128, 80, 32, 64, 1), (4, 160, 64, 16, 96, 2),
+                 (3, 128, None, 48, 96, 3)],      # Ca = multi_tile_cout(27): more than one tile per block (four chunks: the entry's minimum)
     (2, True): [(4, 128, 48, 16, 16, 2), (2, 128, 64, 32, 16, 1)],
 }
 
 
-RD_CASES = [(pm, w16, i) for (pm, w16) in RD_SHAPES for i in range(2)]
+RD_CASES = [(pm, w16, i) for (pm, w16) in RD_SHAPES for i in range(len(RD_SHAPES[(pm, w16)]))]
 
 
 @pytest.mark.parametrize("pm,w16,shape", RD_CASES, ids=[f"{PM_NAMES[p]}-{'w16' if w else 'wide'}-{i}" for p, w, i in RD_CASES])
@@ -245,6 +259,8 @@ def test_dgrad_bnreduce_instance(dev, pm, w16, shape):
     first shape has a partial Cout tile (Ca % 64 != 0)."""
     from onet_amd import ops
     B, Cd, Ca, H, W, G = RD_SHAPES[(pm, w16)][shape]
+    if Ca is None:
+        Ca = multi_tile_cout(B * (W // 32) * (H // 16))
     dz = rnd(B, Cd, H, W, seed=111, scale=1e-3)
     w = rnd(Cd, Ca, 3, 3, seed=112, scale=(2.0 / (9 * Ca)) ** 0.5)
     zp = (rnd(B, Ca, H, W, seed=113) * 1.5 + 0.2).to(dev)
@@ -280,12 +296,16 @@ def test_dgrad_bnreduce_instance(dev, pm, w16, shape):
 
 # -------------------------------------------------------------------------------------- input gradient with a pre-split half
 @pytest.mark.parametrize("pm", [1, 2], ids=lambda p: PM_NAMES[p])
-@pytest.mark.parametrize("B,Cd,Ca,H,W,ch0", [(2, 64, 128, 16, 32, 64), (1, 96, 192, 32, 64, 64)])
+@pytest.mark.parametrize("B,Cd,Ca,H,W,ch0", [(2, 64, 128, 16, 32, 64), (1, 96, 192, 32, 64, 64),
+                                             (3, 32, None, 48, 96, None)])    # Ca = multi_tile_cout(27), ch0 = about half of it: blocks walk more than one tile
 def test_dgrad_pre_slots_instance(dev, pm, B, Cd, Ca, H, W, ch0):
     """launch_split_pre<0, PM, 0> with SpPreArgs::zP: channels < ch0 of da as fp32, channels >= ch0 pre-split.  Both against the fp64
     input gradient: the fp32 half at the forward tolerance, the pre-split half unscaled by the bound's `always` scale (fp16 parts) or
     within one bf16 rounding of the fp64 value (plain bf16)."""
     from onet_amd import ops
+    if Ca is None:
+        Ca = multi_tile_cout(B * (W // 32) * (H // 16))
+        ch0 = Ca // 128 * 64
     dz = rnd(B, Cd, H, W, seed=121, scale=1e-3)
     w = rnd(Cd, Ca, 3, 3, seed=122, scale=(2.0 / (9 * Ca)) ** 0.5)
     da64 = dgrad64(ref_op(dz, pm), ref_op(w, pm))
