@@ -243,6 +243,16 @@ int onet_conv3x3_split_fwd_pre_act(const void* xs, int64_t xs_bs, const void* x_
                                    int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream);
 int onet_conv3x3_act_bound(const float* w, int Cout, int Cin, const float* save, const void* x_amax, const void* x_amax2, int split_ch,
                            void* out_slots, void* stream);
+/* Round 8 -- eval-mode inference on PLAIN bf16 operands (Settings.fused_eval = "bf16").  onet_conv3x3_split_fwd_pre's convolution with
+ * wq_f16 = 2 (xs [B][Cin/8][H][W][8] bf16, one part, unscaled; wq the plain16 forward pack) and the same FIXED BatchNorm + ReLU epilogue,
+ * a = max(0, fma(z - mean, sc, sh)) from save [4][Cout], leaving as ONE part of bf16(a), round to nearest even, unscaled (bf16 has
+ * fp32's exponent range: no bound, no guard): aP [B][Cout/8][H][W][8], batch stride aP_bs in 4-byte units (the leading channel groups of
+ * a concat buffer qualify) -- bit for bit what onet_conv3x3_split_fwd_pre (wq_f16 = 2, fp32 z) + onet_bn_relu_apply_split (nparts = 1)
+ * write; z is never stored.  a_amax (may be NULL; zeroed by the caller): receives the exact max a.  a (may be NULL): the activation as
+ * fp32 NCHW too (16-byte aligned, a_bs % 4 == 0).  Maps made of full 16 x 32 tiles, Cin % 32 == 0, Cout % 64 == 0: returns 1 (nothing
+ * launched) elsewhere. */
+int onet_conv3x3_plain16_fwd_pre_act(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs, void* a_amax,
+                                     float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream);
 /* Weight gradient (OV:47,51 backward) from pre-split x and dz (both in the slot layout, same 16-bit type): fragments by the gfx950
  * transposing LDS read, staging by LDS-DMA; the producers' power-of-two scales (x_amax: guard rule, dz_amax: always; NULL:
  * unscaled) are undone on the slabs; deterministic split-K through ws

@@ -1091,9 +1091,14 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
 //      'S' step, tap (2,2):                 A = [x_mid(row n+2) | same],  B = [w_hi(2,2) | 0]   (27 K16 products are an odd number:
 //    one half instruction per tile and chunk is padding -- 14 steps for 13.5 steps' worth, +3.7 %; the zero half reads the zero padding
 //    behind the halo image).  Lanes pick their K group by address: every fragment is still ONE conflict-free ds_read_b128.
-template <bool ST, int PM, bool W16, bool RD = false>
+//
+// ACT (eval-mode inference on plain bf16 operands): conv3x3_split_pre_kernel's activation epilogue in this lane layout -- the fixed
+// BatchNorm + ReLU of SpPreArgs::act_* on the accumulators, every channel out through the one-part slot store (zP, zP_ch0 = 0, unscaled:
+// bf16 has fp32's exponent range, there is no guard), z never written.
+template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     constexpr bool F16 = PM == 1;
+    static_assert(!ACT || (PM == 2 && !ST && !W16 && !RD), "conv3x3_pre16_kernel: the activation epilogue goes with the one-part bf16 slot store");
     using C = SpPreCfg<W16>;
     static_assert(C::NW == 8 && C::NT == 2, "conv3x3_pre16_kernel: 8 waves of 2 rows");
     constexpr int NT = 2, IN_COLS = C::IN_COLS, NWI = C::NWI, CO_T = C::CO_T, NPIXP = C::NPIXP;
@@ -1193,7 +1198,25 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int buf = 0;
+    // ACT: the tile's 64 x (mean, sc, sh) in LDS behind the chunk buffers, [tile parity][3][64] floats, fetched one tile ahead and
+    // committed at the top of the tile (conv3x3_split_pre_kernel's act_fetch / act_cf: a wave still in the previous tile's epilogue
+    // reads the other copy, and nobody gets two tiles ahead of a chunk barrier)
+    [[maybe_unused]] float* const act_cf = reinterpret_cast<float*>(lds + 2 * BUF);
+    [[maybe_unused]] float cf_next = 0.f;
+    [[maybe_unused]] int cf_par = 0;
+    auto act_fetch = [&](int t) __attribute__((always_inline)) {
+        if (tid < 192 && t < t_end) {
+            const int k = tid >> 6;                                 // 0: mean, 1: sc, 2: sh   (save rows 0, 2, 3)
+            cf_next = a.act_save[(int64_t)(k + (k > 0)) * a.Cout + sp_tile(t, a.coTiles, a.tilesX, a.tilesY).co0 + (tid & 63)];
+        }
+    };
+    if constexpr (ACT) act_fetch(t_first);
     for (int tile = t_first; tile < t_end; tile += t_stride) {
+        if constexpr (ACT) {
+            cf_par ^= 1;
+            if (tid < 192) act_cf[cf_par * 192 + tid] = cf_next;
+            act_fetch(tile + t_stride);
+        }
         f32x4s acc[4][NT][2];                       // [channel tile][row][16-pixel tile]
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
@@ -1338,6 +1361,34 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
             }
             __syncthreads();
         }
+        if constexpr (ACT) {
+            // BatchNorm (fixed coefficients) + ReLU on the accumulators, bn_relu_apply_split_kernel's expression: the lane's channel of
+            // channel tile ct is 16 ct + r16 -- one (mean, sc, sh) per channel tile
+            const float* cf = act_cf + cf_par * 192;
+            float vmax = 0.f;
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct) {
+                const float mean = cf[ct * 16 + r16], sc = cf[64 + ct * 16 + r16], sh = cf[128 + ct * 16 + r16];
+#pragma unroll
+                for (int n = 0; n < NT; ++n)
+#pragma unroll
+                    for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float v = fmaxf(fmaf(acc[ct][n][ch][r] - mean, sc, sh), 0.f);
+                            acc[ct][n][ch][r] = v;
+                            vmax = fmaxf(vmax, v);
+                        }
+            }
+            if (a.act_amax) {
+                // the exact maximum of what this wave wrote (bf16 rounding is monotone: the slots' maximum is bf16 of it): one atomicMax
+                // on the fp32 bit pattern per wave and tile
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o, 64));
+                if (lane == 0 && vmax == vmax)
+                    atomicMax(a.act_amax + ((tile * 8 + wn) & (AMAX_SLOTS - 1)) * AMAX_STRIDE, __builtin_bit_cast(unsigned, vmax));
+            }
+        }
         // RD, part 1: the z tile of the unit below goes into registers FIRST (16 loads in flight; the fragment registers of the main loop
         // are dead here), the da stores below run while they travel, and the sums are taken after the stores
         f32x4s zr[4][NT][2];
@@ -1389,7 +1440,16 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
                                        __builtin_amdgcn_update_dpp(vb.z, va.z, 0x128, 0xf, 0x3, false), __builtin_amdgcn_update_dpp(vb.w, va.w, 0x128, 0xf, 0x3, false)};
                     const f32x4s d1 = __builtin_bit_cast(f32x4s, e1), d2 = __builtin_bit_cast(f32x4s, e2);
                     if constexpr (PM == 2 && !ST && !W16 && !RD) {
-                        if (a.zP && co0 >= a.zP_ch0) {
+                        if constexpr (ACT) {
+                            // the activation in fp32 NCHW too, for a reader that takes no slots: the plain z store's float4s
+                            if (a.act_a && yo < a.H && xo < a.W) {
+                                const int co = co0 + ct * 16 + c8;
+                                float* o = a.act_a + (int64_t)b * a.act_a_bs + (int64_t)co * HW + (int64_t)yo * a.W + xo;
+                                if (co < a.Cout) *reinterpret_cast<f32x4s*>(o) = d1;
+                                if (co + 8 < a.Cout) *reinterpret_cast<f32x4s*>(o + (int64_t)8 * HW) = d2;
+                            }
+                        }
+                        if (ACT || (a.zP && co0 >= a.zP_ch0)) {
                             // Pre-split output, plain bf16 (SpPreArgs::zP, one part): the eight lanes c8 = 0 .. 7 of a (pixel quad, tile half)
                             // hold 8 channels x 4 pixels of channel group A (d1: channels 16 ct + c8) and of group B (d2: + 8).  Three
                             // butterfly exchanges (lane ^ 1, ^ 2, ^ 4) transpose them: afterwards lane c8 owns one whole slot -- the 8
@@ -1529,10 +1589,11 @@ int launch_split_pre(SpPreArgs a, hipStream_t st) {
     // level (that instance of the new kernel exceeds the register budget).
     constexpr bool P16 = RD || PM == 2 || (ST && !W16);
     void (*kern)(SpPreArgs);
-    if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD>;      // (constexpr: the instances not dispatched are not built)
+    if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD, ACT>;      // (constexpr: the instances not dispatched are not built)
     else kern = conv3x3_split_pre_kernel<ST, PM, W16, ACT>;
     static PerDeviceOnce attr_once;
-    return sp_launch_persistent(kern, attr_once, LDS_BYTES, tiles, C::NW * 64, ACT ? "conv3x3_split_pre_act_kernel" : "conv3x3_split_pre_kernel", a, st);
+    return sp_launch_persistent(kern, attr_once, LDS_BYTES, tiles, C::NW * 64,
+                                ACT ? (PM == 2 ? "conv3x3_pre16_act_kernel" : "conv3x3_split_pre_act_kernel") : "conv3x3_split_pre_kernel", a, st);
 }
 
 int split_nparts(int B, int H, int W) {
@@ -2476,6 +2537,33 @@ int onet_conv3x3_split_fwd_pre_act(const void* xs, int64_t xs_bs, const void* x_
     p.act_a = a;
     p.act_a_bs = a_bs;
     return launch_split_pre<false, 1, false, false, true>(p, as_stream(stream));
+}
+
+// Eval-mode inference on PLAIN bf16 operands (one part, unscaled: bf16 has fp32's exponent range, so no magnitude slots, bound or guard):
+// the forward convolution of onet_conv3x3_split_fwd_pre (wq_f16 = 2) with the fixed BatchNorm + ReLU of `save` [4][Cout]
+// (onet_bn_eval_coeffs) in the epilogue and the activation leaving as slots: aP [B][Cout/8][H][W][8] bf16 (round to nearest even), batch
+// stride aP_bs in 4-byte units (the leading channel groups of a concat buffer qualify).  a_amax (may be NULL): magnitude slots that
+// receive the exact max a; a (may be NULL): the activation as fp32 NCHW too.  Bit for bit what the plain launch (fp32 z) followed by
+// onet_bn_relu_apply_split(nparts = 1) writes; z itself is never stored.  Returns 1 (nothing launched) where the map is not made of full
+// 16 x 32 tiles, Cin is not a multiple of 32 or Cout not one of 64.
+int onet_conv3x3_plain16_fwd_pre_act(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs, void* a_amax,
+                                     float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    ONET_REQUIRE(xs && wq && save && aP, "conv3x3_plain16_fwd_pre_act: null pointer");
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv3x3_plain16_fwd_pre_act: bad shape");
+    if (W < 32 || (W % 32) || (H % 16) || (Cin % 32) || (Cout % 64)) return 1;
+    if (const int rc = pre_operand_checks("conv3x3_plain16_fwd_pre_act", xs, xs_bs, 2, Cin, Cout, H, W)) return rc;
+    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "conv3x3_plain16_fwd_pre_act: 16-byte aligned slots required");
+    ONET_REQUIRE(!a || ((a_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0), "conv3x3_plain16_fwd_pre_act: 16-byte aligned rows required");
+    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W / 2 && (!a || a_bs >= (int64_t)Cout * H * W), "conv3x3_plain16_fwd_pre_act: batch stride too small");
+    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, nullptr, 0, nullptr, 0};
+    p.zP = aP;
+    p.zP_bs = aP_bs;
+    p.zP_ch0 = 0;
+    p.act_save = save;
+    p.act_amax = (unsigned*)a_amax;
+    p.act_a = a;
+    p.act_a_bs = a_bs;
+    return launch_split_pre<false, 2, false, false, true>(p, as_stream(stream));
 }
 
 // a[co] = relu(sc (z - mean) + sh) with |z[co]| <= sum_ci |w[co][ci][.]| max |x[ci]|:  |a[co]| <= |sc| (S1 max1 + S2 max2) + |sh - mean sc|,

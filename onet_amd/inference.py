@@ -16,7 +16,11 @@ Every tensor kept as slots carries two sets of magnitude slots:
 
 Levels: level k is the part of the U-Net on maps of H / 2^k x W / 2^k.  The plan is fused down to depth d, the deepest level all of
 whose layers ops.eval_layer_ok accepts; the levels below run the existing eval kernels on fp32 tensors (the pooled tensor of level
-d - 1 is written as fp32 going down, ops.convT2x2_fwd_p writes slots coming back up)."""
+d - 1 is written as fp32 going down, ops.convT2x2_fwd_p writes slots coming back up).
+
+Settings.fused_eval = "bf16" runs the same plan on ONE part of plain bf16 per slot (ops.conv3x3_plain16_pre_act; layer predicate
+ops.eval_layer_ok_bf16): the operands conv == "bf16" trains with, one MFMA per product term instead of three and 2-byte slot elements.
+bf16 has fp32's exponent range, so that plan carries no magnitude slots at all: scale = amax = None on every tensor, no bound launches."""
 from __future__ import annotations
 
 import torch
@@ -48,9 +52,17 @@ def _static_reason(unet):
             return "a BatchNorm without running statistics (or in training mode)"
     if _hooked(unet):
         return "a forward hook watches a block"
-    if not (ops.presplit() and ops.p16_parts() == 2):
+    if _parts() == 1:
+        if not ops.presplit():
+            return "pre-split storage is off under the effective convolution algorithm"
+    elif not (ops.presplit() and ops.p16_parts() == 2):
         return "the effective convolution algorithm is not the fp16-split one with pre-split storage"
     return None
+
+
+def _parts():
+    """Parts per slot of the active plan: 2 = fp16 (hi | mid), 1 = plain bf16 (Settings.fused_eval = "bf16")"""
+    return 1 if ops.fused_eval_operands() == "bf16" else 2
 
 
 def _level_layers(unet):
@@ -73,13 +85,14 @@ def _depth(unet, N, H, W):
     """-> (d, why level d is not fused | None): levels 0 .. d - 1 are fused"""
     enc, _, ups = _blocks(unet)
     levels = _level_layers(unet)
+    layer_ok = ops.eval_layer_ok_bf16 if _parts() == 1 else ops.eval_layer_ok
     for k in range(5):
         if (H % (1 << k)) or (W % (1 << k)):
             return k, f"level {k}: the input size is not a multiple of {1 << k}"
         h, w = H >> k, W >> k
         for name, conv in levels[k]:
-            if not ops.eval_layer_ok(N, conv.in_channels, conv.out_channels, h, w):
-                return k, f"level {k}: {name} ({conv.in_channels} -> {conv.out_channels} on {N} maps of {h} x {w}) is outside ops.eval_layer_ok"
+            if not layer_ok(N, conv.in_channels, conv.out_channels, h, w):
+                return k, f"level {k}: {name} ({conv.in_channels} -> {conv.out_channels} on {N} maps of {h} x {w}) is outside ops.{layer_ok.__name__}"
         if k < 4:
             C = _units(enc[k])[2].out_channels
             d1 = _units(ups[k].conv)[0]
@@ -91,9 +104,10 @@ def _depth(unet, N, H, W):
 def unet_plan(unet, shape, device=None):
     """What the fused plan does with a U-Net pass over an input of `shape` = (N, C, H, W): a pure query, nothing is launched.
     -> {"fused": bool, "reason": why not | None, "depth": d, "batch": N, "layers": {name: "stem" | "fused" | "two-pass" | "plain+head"
-    | "fallback"}, "convt": {name: "slots" | "fp32->slots" | "fallback"}, "fallback_reason": why level d is not fused | None}"""
+    | "fallback"}, "convt": {name: "slots" | "fp32->slots" | "fallback"}, "fallback_reason": why level d is not fused | None,
+    "operands": the slot format the settings select, "fp16x2" | "bf16" (None: Settings.fused_eval is off)}"""
     out = {"fused": False, "reason": None, "depth": 0, "batch": int(shape[0]) if len(shape) == 4 else 0, "layers": {}, "convt": {},
-           "fallback_reason": None}
+           "fallback_reason": None, "operands": ops.fused_eval_operands()}
     if len(shape) != 4:
         out["reason"] = "the input is not 4-D"
         return out
@@ -137,7 +151,7 @@ def unet_plan(unet, shape, device=None):
         up = ups[k].up
         if k >= d:
             out["convt"][unames[k]] = "fallback"
-        elif k + 1 < d and ops.convt_slots_ok(N, up.in_channels, up.out_channels, H >> (k + 1), W >> (k + 1)):
+        elif k + 1 < d and ops.convt_slots_ok(N, up.in_channels, up.out_channels, H >> (k + 1), W >> (k + 1), parts=_parts()):
             out["convt"][unames[k]] = "slots"
         else:
             out["convt"][unames[k]] = "fp32->slots"
@@ -199,13 +213,20 @@ def _bound(conv, save, t):
     return ops.conv3x3_act_bound(conv.weight, save, s1, s2, ch)
 
 
-def _wq(conv):
-    return conv.packed().get_pack("split")[0]
+def _wq(conv, parts=2):
+    return conv.packed().get_pack("split" if parts == 2 else "plain16")[0]
 
 
 def _fused_unit(conv, bn, t, keep_fp32=False):
     """Conv-BatchNorm-ReLU in one launch, output as slots (+ fp32 when another reader needs it)"""
     save = _coeffs(bn)
+    if t.P.shape[3] == 1:             # plain bf16: unscaled, nothing to bound or record
+        B, _, H, _, W, _ = t.P.shape
+        a = torch.empty((B, conv.out_channels, H, W), dtype=torch.float32, device=t.P.device) if keep_fp32 else None
+        aP = ops.conv3x3_plain16_pre_act(t.P, _wq(conv, 1), conv.out_channels, save, a=a)
+        if aP is None:
+            raise RuntimeError("onet_amd: the fused eval kernel refused a shape ops.eval_layer_ok_bf16 accepted")
+        return _T(aP, a)
     scale = _bound(conv, save, t)
     B, _, H, _, W, _ = t.P.shape
     amax = ops.new_amax(t.P.device)
@@ -218,6 +239,8 @@ def _fused_unit(conv, bn, t, keep_fp32=False):
 
 
 def _plain_conv(conv, t):
+    if t.P.shape[3] == 1:
+        return ops.conv3x3_split_pre(t.P, _wq(conv, 1), conv.out_channels)
     s1, s2, ch = ops._slots3(t.scale)
     return ops.conv3x3_split_pre(t.P, _wq(conv), conv.out_channels, slots=s1, slots2=s2, split_ch=ch)
 
@@ -227,15 +250,16 @@ def _pooled_unit(conv, bn, t, skipP, want_L, pooled_slots):
     into the concat buffer, the pooled tensor (slots, or fp32 for a fall-back level) and -- level 0 -- the fp32 tensor the caller
     receives.  -> (skip, pooled, L | None)"""
     save = _coeffs(bn)
-    scale = _bound(conv, save, t)
+    parts = t.P.shape[3]
+    scale = _bound(conv, save, t) if parts == 2 else None
     z = _plain_conv(conv, t)
     B, C, H, W = z.shape
     L = torch.empty_like(z) if want_L else None
-    yP = ops.p16_empty(B, C, H // 2, W // 2, z.device, parts=2) if pooled_slots else None
+    yP = ops.p16_empty(B, C, H // 2, W // 2, z.device, parts=parts) if pooled_slots else None
     yF = None if pooled_slots else torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=z.device)
     if not ops.bn_relu_apply_pool_split(z, save, skipP, L, yP, yF, slots=scale):
         raise RuntimeError("onet_amd: the BatchNorm + pooling pass refused a shape ops.eval_layer_ok accepted")
-    if yF is not None:
+    if yF is not None and scale is not None:
         ops.tag_amax(yF, scale)           # (max-pooling keeps the bound: the in-staging kernel below takes it as its range guard)
     return _T(skipP, None, scale, scale), _T(yP, yF, scale, scale), L
 
@@ -243,6 +267,16 @@ def _pooled_unit(conv, bn, t, skipP, want_L, pooled_slots):
 def _conv_t(up, t, catP, C2):
     """ConvTranspose2d(k=2, s=2) + bias into the up-sampled channel groups of the pre-split concat buffer -> their magnitude slots"""
     Ct = up.out_channels
+    if catP.shape[3] == 1:            # plain bf16: the one-part weight pack, no magnitude slots on either side
+        dst = catP[:, C2 // 8:]
+        packed = up.packed()
+        if t.P is not None and ops.convT2x2_fwd_slots(t.P, packed.slots(1), up.bias, dst, Ct, kind="convt_slot_fwd_kernel"):
+            return None
+        if t.F is None:
+            raise RuntimeError("onet_amd: the slot-operand ConvTranspose2d refused a shape ops.convt_slots_ok accepted")
+        if not ops.convT2x2_fwd_p(t.F, packed[0], up.bias, dst, Ct, 0, 0):
+            raise RuntimeError("onet_amd: the ConvTranspose2d GEMM refused the fp32 input of a fused level")
+        return None
     x_amax = t.amax if t.amax is not None else ops.absmax_slots(t.F)
     s_up = ops.convT2x2_out_bound(up.weight, up.bias, x_amax)
     dst = catP[:, C2 // 8:]
@@ -273,11 +307,11 @@ def _unet_pass(unet, x, d):
     dev = x.device
     # stem: the existing direct kernel, then one BatchNorm + ReLU pass that writes slots
     c1, b1, c2, b2 = _units(enc[0])
+    P = _parts()
     z0 = ops.conv3x3_auto(x, c1.packed(), 0)
     save0 = _coeffs(b1)
-    xin = _T(None, x, None, ops.absmax_slots(x))
-    scale0 = _bound(c1, save0, xin)
-    a0 = ops.p16_empty(N, c1.out_channels, H, W, dev, parts=2)
+    scale0 = _bound(c1, save0, _T(None, x, None, ops.absmax_slots(x))) if P == 2 else None
+    a0 = ops.p16_empty(N, c1.out_channels, H, W, dev, parts=P)
     ops.bn_relu_apply_split(z0, save0, a0, slots=scale0)
     del z0
     t = _note("inc.c1", _T(a0, None, scale0, scale0))
@@ -289,30 +323,32 @@ def _unet_pass(unet, x, d):
             t = _note(names[k] + ".c1", _fused_unit(c1, b1, t))
         if k == 4:
             up = ups[3].up
-            t = _note("down4.c2", _fused_unit(c2, b2, t, keep_fp32=not ops.convt_slots_ok(N, up.in_channels, up.out_channels, H >> 4, W >> 4)))
+            t = _note("down4.c2", _fused_unit(c2, b2, t, keep_fp32=not ops.convt_slots_ok(N, up.in_channels, up.out_channels, H >> 4, W >> 4, parts=P)))
             break
         C = c2.out_channels
-        catP[k] = ops.p16_empty(N, C + ups[k].up.out_channels, H >> k, W >> k, dev, parts=2)
+        catP[k] = ops.p16_empty(N, C + ups[k].up.out_channels, H >> k, W >> k, dev, parts=P)
         skips[k], t, Lk = _pooled_unit(c2, b2, t, catP[k][:, :C // 8], k == 0, k + 1 < d)
         _note(names[k] + ".c2", skips[k])
+        if P == 1 and t.P is not None:
+            _note(names[k] + ".pool", t)          # (the one-part plan's trace is complete: every convolution's exact input can be rebuilt)
         if k == 0:
             L = Lk
     if d < 5:
         # the levels below: existing eval kernels on fp32 tensors, from the pooled tensor of level d - 1
         t = _T(None, _tail(unet, d, enc[d](t.F)), None, None)
-        t.amax = ops.amax_of(t.F)
+        t.amax = ops.amax_of(t.F) if P == 2 else None
     z = save = None
     for k in range(min(d, 4) - 1, -1, -1):
         C = _units(enc[k])[2].out_channels
         s_up = _conv_t(ups[k].up, t, catP[k], C)
-        cat = _T(catP[k], None, (skips[k].scale, s_up, C), (skips[k].amax, s_up, C))
+        cat = _T(catP[k], None, (skips[k].scale, s_up, C), (skips[k].amax, s_up, C)) if P == 2 else _T(catP[k])
         c1, b1, c2, b2 = _units(ups[k].conv)
         _note(unames[k] + ".up", _T(catP[k][:, C // 8:], None, s_up, s_up))
         t = _note(unames[k] + ".c1", _fused_unit(c1, b1, cat))
         catP[k] = None
         if k > 0:
             up = ups[k - 1].up
-            t = _note(unames[k] + ".c2", _fused_unit(c2, b2, t, keep_fp32=not ops.convt_slots_ok(N, up.in_channels, up.out_channels, H >> k, W >> k)))
+            t = _note(unames[k] + ".c2", _fused_unit(c2, b2, t, keep_fp32=not ops.convt_slots_ok(N, up.in_channels, up.out_channels, H >> k, W >> k, parts=P)))
         else:
             z, save = _plain_conv(c2, t), _coeffs(b2)
     return L, z, save

@@ -60,7 +60,11 @@ class Settings:
       presplit      the split kernels' operands are written pre-split (fp16 hi | mid slots) by their producers     (default PRESPLIT)
       z_bf16        under conv == "bf16" with pre-split operands: the convolution outputs z are STORED as bf16          (default Z_BF16)
       fused_eval    eval-mode forward under no_grad as a straight-line plan on the pre-split kernels: BatchNorm(eval) + ReLU in
-                    the convolution's epilogue, activations kept as slots (onet_amd/inference.py); opt-in                (default FUSED_EVAL)"""
+                    the convolution's epilogue, activations kept as slots (onet_amd/inference.py); opt-in                (default FUSED_EVAL)
+                    True: fp16 (hi | mid) slots, fp32-level results (needs the fp16-split convolution path: under conv == "bf16" the
+                    forward falls back to the default path); "bf16": ONE part of plain bf16 per slot -- the arithmetic conv == "bf16"
+                    trains with, a third of the matrix instructions and half the slot bytes -- under any conv with pre-split storage
+                    (fused_eval_operands())"""
     __slots__ = ("conv", "twin", "convt_bf16", "lazy_nan", "split", "bn_on_load", "split_f16", "grad_f16", "split_dgrad",
                  "stem_fused", "sync_bn", "presplit", "z_bf16", "fused_eval")
 
@@ -157,11 +161,21 @@ def presplit():
     return split_enabled() and conv_algo() in ("auto", "split") and split_f16() and split_dgrad()
 
 
-FUSED_EVAL = _flag("FUSED_EVAL", False)     # 1: eval forwards under no_grad take the fused inference plan (Settings.fused_eval)
+# 1: eval forwards under no_grad take the fused inference plan (Settings.fused_eval); bf16: its one-part plain-bf16 form
+FUSED_EVAL = "bf16" if _FLAGS.get("FUSED_EVAL") == "bf16" else _flag("FUSED_EVAL", False)
 
 
 def fused_eval():
     return bool(_setting("fused_eval", FUSED_EVAL))
+
+
+def fused_eval_operands():
+    """The slot format of the fused eval plan: "fp16x2" (Settings.fused_eval = True: fp16 hi | mid parts), "bf16" (= "bf16": one part
+    of plain bf16), None (off)."""
+    v = _setting("fused_eval", FUSED_EVAL)
+    if not v:
+        return None
+    return "bf16" if v == "bf16" else "fp16x2"
 
 
 Z_BF16 = _flag("Z_BF16", True)       # BASELINE configs[2] (conv == "bf16", pre-split operands): conv outputs stored as bf16 (Settings.z_bf16)
@@ -504,11 +518,12 @@ def conv3x3_split_dgrad_pre_slots(dzP, wq, Cout, ch0, daP_slots, slots=None, alw
 CONVT_SLOTS = _flag("CONVT_SLOTS", True)     # 0: the ConvTranspose2d forward reads the fp32 activation (round 4's kernels)
 
 
-def convt_slots_ok(B, Cin, Ct, h, w):
+def convt_slots_ok(B, Cin, Ct, h, w, parts=None):
     """Does the slot-operand ConvTranspose2d forward take this layer (onet_convT2x2_fwd_slots' predicate)?  The block below then writes
-    its output pre-split for it (UNet._forward)."""
-    return bool(CONVT_SLOTS and presplit() and (p16_parts() == 2 or CONVT_BF16) and Cin % 32 == 0 and Cin >= 128 and Ct % 32 == 0 and (h * w) % 128 == 0 and w % 2 == 0
-                and Cin * h * w * 2 * p16_parts() < 2 ** 31)
+    its output pre-split for it (UNet._forward).  parts: parts per slot operand (None: p16_parts(), what the active `conv` trains with)."""
+    parts = p16_parts() if parts is None else parts
+    return bool(CONVT_SLOTS and presplit() and (parts == 2 or CONVT_BF16) and Cin % 32 == 0 and Cin >= 128 and Ct % 32 == 0 and (h * w) % 128 == 0 and w % 2 == 0
+                and Cin * h * w * 2 * parts < 2 ** 31)
 
 
 CONVT_BWD_SLOTS = _flag("CONVT_BWD_SLOTS", True)     # 0: the ConvTranspose2d backward GEMMs read fp32 operands (round 4's kernels)
@@ -1188,6 +1203,45 @@ def eval_layer_ok(B, Cin, Cout, H, W):
     if Cin % 16 or Cout % 64 or W < 32 or W % 32 or H % 16 or H * W >= 2 ** 24:
         return False
     return conv3x3_algo(B, Cin, Cout, H, W) == "split"
+
+
+def eval_layer_ok_bf16(B, Cin, Cout, H, W):
+    """eval_layer_ok for the one-part plan (Settings.fused_eval = "bf16"): the domain of onet_conv3x3_plain16_fwd_pre_act -- maps made of
+    full 16 x 32 tiles, Cin % 32 == 0, Cout % 64 == 0 -- inside the buffer-resource range, with pre-split storage on.  Under conv in
+    ("bf16", "split") every such layer is taken, as those settings take every legal layer of their own kernels; otherwise conv3x3_algo's
+    fill rule decides (tiles >= 3/4 of the compute units; smaller layers stay on the existing eval kernels).  A function of shapes,
+    settings and n_cu()."""
+    if not presplit():
+        return False
+    if Cin % 32 or Cout % 64 or W < 32 or W % 32 or H % 16 or H * W >= 2 ** 24 or not _in_buffer_range(Cin, Cout, H, W):
+        return False
+    if conv_algo() in ("bf16", "split"):
+        return True
+    return B * (H // 16) * (W // 32) * (Cout // 64) >= (n_cu() * 3) // 4
+
+
+def conv3x3_plain16_pre_act(xs, wq, Cout, save, out=None, a_amax=None, a=None):
+    """aP = relu(bn(conv3x3(xs))) on PLAIN bf16 operands (xs [B, Cin/8, H, 1, W, 8] bf16, wq the plain16 forward pack), written as one
+    part of bf16 slots, BatchNorm with the fixed coefficients `save` [4, Cout] (bn_eval_coeffs) in the convolution's epilogue:
+    conv3x3_split_pre (fp32 z) followed by bn_relu_apply_split, bit for bit, without the tensor z.  Unscaled: no magnitude slots.
+    a_amax: slots that receive the exact max a; a: optional fp32 destination.  -> aP, or None where the kernel does not take the shape
+    (nothing launched)."""
+    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
+        raise TypeError("conv3x3_plain16_pre_act: xs and wq must be one-part bf16 packs on the GPU")
+    B, C8, H, _, W, _ = xs.shape
+    Cin = C8 * 8
+    if W < 32 or W % 32 or H % 16 or Cin % 32 or Cout % 64:
+        return None
+    if out is None:
+        out = p16_empty(B, Cout, H, W, xs.device, parts=1)
+    e0 = _prof_begin("conv3x3_pre16_act_kernel")
+    rc = _lib.load().onet_conv3x3_plain16_fwd_pre_act(_p(xs), _pbs(xs), _p(wq), _p(save), _p(out), _pbs(out), _p(a_amax), _p(a),
+                                                      0 if a is None else (a.stride(0) if B > 1 else Cout * H * W), B, Cin, Cout, H, W, _stream())
+    _prof_end("conv3x3_pre16_act_kernel", 2.0 * B * H * W * Cin * Cout * 9 if rc == 0 else 0.0, e0,
+              (B * H * W * (2.0 * Cin + (2.0 + 4.0 * (a is not None)) * Cout) + 2.0 * 9 * Cin * Cout) if rc == 0 else 0.0)
+    if rc < 0:
+        raise _lib.OnetHipError(f"onet_conv3x3_plain16_fwd_pre_act failed ({rc}): {_lib.last_error()}")
+    return out if rc == 0 else None
 
 
 def conv3x3_act_bound(weight, save, x_amax, x_amax2=None, split_ch=0):

@@ -1,12 +1,15 @@
-"""Eval-mode forward time: the default path against the fused plan (Settings.fused_eval), in ONE process.
+"""Eval-mode forward time: the default path against the fused plans (Settings.fused_eval), in ONE process.
 
     python tools/time_eval.py [--rounds 5] [--seconds 1.0] [--shapes 32x1x256x256,2x1x256x256,1x3x512x512] [--json out.json]
-    python tools/time_eval.py --profile-run 32x1x256x256      # fused forwards only: the workload of a rocprofv3 --kernel-trace run
+    python tools/time_eval.py --profile-run 32x1x256x256 [--path fused]     # one path's forwards only: the workload of a kernel-trace run
 
-Per shape: both paths are warmed up, the number of forwards that fills `--seconds` is measured, then `--rounds` interleaved rounds
-(default, fused, default, fused, ...) of that many forwards each are timed with device events under no_grad.  Reported: ms per
-forward (median over rounds), images/s, the round-to-round spread (max - min over rounds) and torch.cuda.max_memory_allocated of
-each path.  The verdict per shape compares the difference of the medians with the SUM of the two spreads."""
+Paths: "default" (Settings()), "fused" (fused_eval=True: fp16 hi | mid slots), "bf16" (fused_eval="bf16" under conv == "auto": one-part
+bf16 slots, depth by the fill rule) and "bf16/bf16" (the same under conv == "bf16": every legal level).
+Per shape: every path is warmed up, the number of forwards that fills `--seconds` is measured, then `--rounds` interleaved rounds
+(default, fused, bf16, bf16/bf16, default, ...) of that many forwards each are timed with device events under no_grad.  Reported: ms
+per forward (median over rounds), images/s, the round-to-round spread (max - min over rounds) and torch.cuda.max_memory_allocated of
+each path.  A verdict compares the difference of two medians with the SUM of the two spreads: every fused path against the default
+path, and the one-part plans against the fp16 plan."""
 import argparse
 import json
 import os
@@ -34,16 +37,32 @@ def _timed(m, X, n):
     return e0.elapsed_time(e1) / n
 
 
+def _settings():
+    from onet_amd import ops
+    return {"default": ops.Settings(), "fused": ops.Settings(fused_eval=True), "bf16": ops.Settings(fused_eval="bf16"),
+            "bf16/bf16": ops.Settings(conv="bf16", fused_eval="bf16")}
+
+
+def _verdict(base, other):
+    """-> (gain of `other` over `base` in ms, noise, verdict): the difference of the medians against the sum of the spreads"""
+    gain = base["ms"] - other["ms"]
+    noise = base["spread_ms"] + other["spread_ms"]
+    return gain, noise, "faster" if gain > noise else ("slower" if -gain > noise else "within spread")
+
+
 def time_shape(shape, rounds, seconds, dev):
     import onet_amd
-    from onet_amd import ops
     B, C, H, W = shape
     m = _model(C, dev)
     X = torch.rand((B, C, H, W), device=dev)
-    sets = {"default": ops.Settings(), "fused": ops.Settings(fused_eval=True)}
-    m.settings = sets["fused"]
-    plan = onet_amd.fused_eval_plan(m, X.shape)
-    res = {"shape": list(shape), "plan_fused": plan["fused"], "depth": plan["depth"], "reason": plan["reason"]}
+    sets = _settings()
+    res = {"shape": list(shape), "plans": {}}
+    for name, st in sets.items():
+        if name != "default":
+            m.settings = st
+            plan = onet_amd.fused_eval_plan(m, X.shape)
+            res["plans"][name] = {"fused": plan["fused"], "depth": plan["depth"], "operands": plan["operands"], "reason": plan["reason"]}
+    res["plan_fused"], res["depth"], res["reason"] = (res["plans"]["fused"][k] for k in ("fused", "depth", "reason"))
     with torch.no_grad():
         n = {}
         for name, st in sets.items():
@@ -66,10 +85,11 @@ def time_shape(shape, rounds, seconds, dev):
         med = v[len(v) // 2]
         res[name] = {"ms": med, "img_s": 1e3 * B / med, "spread_ms": v[-1] - v[0], "rounds_ms": ms[name], "forwards_per_round": n[name],
                      "max_mem_MiB": mem[name] / 2 ** 20}
-    gain = res["default"]["ms"] - res["fused"]["ms"]
-    noise = res["default"]["spread_ms"] + res["fused"]["spread_ms"]
-    res["gain_ms"], res["noise_ms"] = gain, noise
-    res["verdict"] = "faster" if gain > noise else ("slower" if -gain > noise else "within spread")
+    res["gain_ms"], res["noise_ms"], res["verdict"] = _verdict(res["default"], res["fused"])
+    res["versus"] = {}
+    for base, other in (("default", "fused"), ("default", "bf16"), ("default", "bf16/bf16"), ("fused", "bf16"), ("fused", "bf16/bf16")):
+        g, nz, v = _verdict(res[base], res[other])
+        res["versus"][f"{other} vs {base}"] = {"gain_ms": g, "noise_ms": nz, "verdict": v}
     return res
 
 
@@ -79,14 +99,14 @@ def main():
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--shapes", default="32x1x256x256,2x1x256x256,1x3x512x512")
     ap.add_argument("--json", default=None)
-    ap.add_argument("--profile-run", default=None, help="BxCxHxW: run 3 warm-up + 10 fused forwards and exit")
+    ap.add_argument("--profile-run", default=None, help="BxCxHxW: run 3 warm-up + 10 forwards of --path and exit")
+    ap.add_argument("--path", default="fused", choices=["default", "fused", "bf16", "bf16/bf16"])
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.profile_run:
-        from onet_amd import ops
         B, C, H, W = (int(v) for v in a.profile_run.split("x"))
         m = _model(C, dev)
-        m.settings = ops.Settings(fused_eval=True)
+        m.settings = _settings()[a.path]
         X = torch.rand((B, C, H, W), device=dev)
         with torch.no_grad():
             for _ in range(13):
@@ -98,10 +118,14 @@ def main():
         shape = tuple(int(v) for v in s.split("x"))
         r = time_shape(shape, max(5, a.rounds), a.seconds, dev)
         out.append(r)
-        print("%s  depth %d  default %.3f ms (%.0f img/s, spread %.3f, %.0f MiB)  fused %.3f ms (%.0f img/s, spread %.3f, %.0f MiB)  gain %.3f ms "
-              "vs noise %.3f: %s" % ("x".join(map(str, shape)), r["depth"], r["default"]["ms"], r["default"]["img_s"], r["default"]["spread_ms"],
-                                     r["default"]["max_mem_MiB"], r["fused"]["ms"], r["fused"]["img_s"], r["fused"]["spread_ms"],
-                                     r["fused"]["max_mem_MiB"], r["gain_ms"], r["noise_ms"], r["verdict"]), flush=True)
+        print("x".join(map(str, shape)), flush=True)
+        for name in ("default", "fused", "bf16", "bf16/bf16"):
+            p = r["plans"].get(name)
+            print("  %-10s %s %8.3f ms (%6.0f img/s, spread %.3f, %5.0f MiB)" % (
+                name, "depth %d" % p["depth"] if p else "       ", r[name]["ms"], r[name]["img_s"], r[name]["spread_ms"], r[name]["max_mem_MiB"]),
+                flush=True)
+        for k, v in r["versus"].items():
+            print("  %-22s gain %7.3f ms vs noise %.3f: %s" % (k, v["gain_ms"], v["noise_ms"], v["verdict"]), flush=True)
     if a.json:
         with open(a.json, "w") as f:
             json.dump(out, f, indent=1)
