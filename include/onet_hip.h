@@ -253,6 +253,23 @@ int onet_conv3x3_act_bound(const float* w, int Cout, int Cin, const float* save,
  * launched) elsewhere. */
 int onet_conv3x3_plain16_fwd_pre_act(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs, void* a_amax,
                                      float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream);
+/* Round 9 -- labels-only inference (onet_amd.scores, onet_amd.segment(head="fused")): the model's LAST Conv-BatchNorm-ReLU unit with the
+ * head's channel product (OV:176,182) in the convolution's epilogue.  The convolution of the two _act entries above on the same operands;
+ * the epilogue forms h = max(0, fma(z - mean, sc, sh)) from save [4][Cout] on the accumulators -- onet_head_softmax_fwd's h_save form --
+ * and writes V [B][H][W] = sum_c L[c] h[c] (L: fp32 NCHW, batch stride L_bs; both 16-byte aligned, L_bs % 4 == 0) and NOTHING else:
+ * neither the fp32 pre-activation z (the largest tensor of the forward) nor h is stored, and the head kernel's read of both is gone.
+ * The sum runs in-lane over the four 16-channel tiles and by four DPP steps over a row's 16 lanes: a fixed order (deterministic), not
+ * the head kernel's channel order -- V agrees with it to the rounding of a 64-term fp32 dot product.  Maps made of full 16 x 32 tiles,
+ * Cin % 32 == 0 (_plain16_) or % 16 == 0 (_split_), Cout == 64 (one channel tile holds every output channel of a pixel): returns 1
+ * (nothing launched, nothing written) elsewhere.
+ * onet_softmax2_labels: S [B][2][HW] = softmax([Vt, Vd]) by onet_head_softmax_fwd's expressions and / or Y [B][HW] = its argmax by
+ * onet_argmax2's rule (ties -> 0) from Vt, Vd [B][HW]; S or Y may be NULL (not both). */
+int onet_conv3x3_plain16_fwd_pre_head(const void* xs, int64_t xs_bs, const void* wq, const float* save, const float* L, int64_t L_bs, float* V,
+                                      int B, int Cin, int Cout, int H, int W, void* stream);
+int onet_conv3x3_split_fwd_pre_head(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
+                                    const void* wq, const float* save, const float* L, int64_t L_bs, float* V, int B, int Cin, int Cout, int H,
+                                    int W, void* stream);
+int onet_softmax2_labels(const float* Vt, const float* Vd, float* S, int64_t* Y, int B, int HW, void* stream);
 /* Weight gradient (OV:47,51 backward) from pre-split x and dz (both in the slot layout, same 16-bit type): fragments by the gfx950
  * transposing LDS read, staging by LDS-DMA; the producers' power-of-two scales (x_amax: guard rule, dz_amax: always; NULL:
  * unscaled) are undone on the slabs; deterministic split-K through ws

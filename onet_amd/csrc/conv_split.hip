@@ -672,6 +672,12 @@ struct SpPreArgs {
     unsigned* act_amax = nullptr;
     float* act_a = nullptr;
     int64_t act_a_bs = 0;
+    // conv3x3_pre16_kernel<false, PM, false, false, false, HEAD = true> (labels-only inference, Cout == 64: one channel tile holds every
+    // output channel of a pixel): the epilogue forms h = max(0, fma(z - mean, sc, sh)) with act_save as above and reduces it against
+    // hd_L [B][Cout][H][W] fp32 (batch stride hd_L_bs) over the channels: hd_V [B][H][W] = sum_c L[c] h[c] is ALL the launch writes
+    const float* hd_L = nullptr;
+    int64_t hd_L_bs = 0;
+    float* hd_V = nullptr;
 };
 
 // PM: 0 = bf16 (hi | mid) parts, 1 = fp16 (hi | mid) parts -- three MFMAs per term on 16-channel chunks; 2 = PLAIN bf16 operands
@@ -1095,10 +1101,19 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
 // ACT (eval-mode inference on plain bf16 operands): conv3x3_split_pre_kernel's activation epilogue in this lane layout -- the fixed
 // BatchNorm + ReLU of SpPreArgs::act_* on the accumulators, every channel out through the one-part slot store (zP, zP_ch0 = 0, unscaled:
 // bf16 has fp32's exponent range, there is no guard), z never written.
-template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false>
+//
+// HEAD (labels-only inference, the model's last unit: Cout == 64, so a block's one channel tile holds every output channel of its
+// pixels): the same activation on the accumulators, then the head's product with L (SpPreArgs::hd_*) summed over the channels --
+// in-lane over the four channel tiles, four DPP steps over the 16 channel lanes of a row -- and V [B][H][W] as the ONLY store: neither
+// z nor an activation leaves the kernel.  No LDS traffic beyond the coefficients, no atomics, a fixed order: deterministic.
+template <int CTRL> __device__ __forceinline__ float dpp_add(float x) {     // x + (x of the lane DPP control CTRL selects)
+    return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
+}
+template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     constexpr bool F16 = PM == 1;
     static_assert(!ACT || (PM == 2 && !ST && !W16 && !RD), "conv3x3_pre16_kernel: the activation epilogue goes with the one-part bf16 slot store");
+    static_assert(!HEAD || (PM != 0 && !ST && !W16 && !RD && !ACT), "conv3x3_pre16_kernel: the head epilogue replaces every store of a plain forward launch");
     using C = SpPreCfg<W16>;
     static_assert(C::NW == 8 && C::NT == 2, "conv3x3_pre16_kernel: 8 waves of 2 rows");
     constexpr int NT = 2, IN_COLS = C::IN_COLS, NWI = C::NWI, CO_T = C::CO_T, NPIXP = C::NPIXP;
@@ -1210,9 +1225,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
             cf_next = a.act_save[(int64_t)(k + (k > 0)) * a.Cout + sp_tile(t, a.coTiles, a.tilesX, a.tilesY).co0 + (tid & 63)];
         }
     };
-    if constexpr (ACT) act_fetch(t_first);
+    if constexpr (ACT || HEAD) act_fetch(t_first);
     for (int tile = t_first; tile < t_end; tile += t_stride) {
-        if constexpr (ACT) {
+        if constexpr (ACT || HEAD) {
             cf_par ^= 1;
             if (tid < 192) act_cf[cf_par * 192 + tid] = cf_next;
             act_fetch(tile + t_stride);
@@ -1388,6 +1403,61 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
                 if (lane == 0 && vmax == vmax)
                     atomicMax(a.act_amax + ((tile * 8 + wn) & (AMAX_SLOTS - 1)) * AMAX_STRIDE, __builtin_bit_cast(unsigned, vmax));
             }
+        }
+        if constexpr (HEAD) {
+            // The L tile in the accumulator layout (RD's z loads: the lane's channel 16 ct + r16 at pixels 4 lq .. + 3 of both 16-pixel
+            // halves of its two rows) goes into registers first; the main loop's fragment registers are dead here
+            f32x4s lr[4][NT][2];
+            const float* Lb = a.hd_L + (int64_t)b * a.hd_L_bs;
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+                for (int n = 0; n < NT; ++n)
+#pragma unroll
+                    for (int ch = 0; ch < 2; ++ch) {
+                        const int co = co0 + ct * 16 + r16, yo = y0 + wn * NT + n, xo = x0 + 16 * ch + 4 * lq;
+                        f32x4s ll = {0.f, 0.f, 0.f, 0.f};
+                        if (co < a.Cout && yo < a.H && xo < a.W) ll = *reinterpret_cast<const f32x4s*>(Lb + (int64_t)co * HW + (int64_t)yo * a.W + xo);
+                        lr[ct][n][ch] = ll;
+                    }
+            __builtin_amdgcn_sched_barrier(0);
+            // h = relu(bn(acc)) by head_softmax_fwd_kernel's expression, v += L h: the channel tiles in order, one fmaf chain per pixel
+            const float* cf = act_cf + cf_par * 192;
+            f32x4s v[NT][2];
+#pragma unroll
+            for (int n = 0; n < NT; ++n)
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch) v[n][ch] = f32x4s{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct) {
+                const float mean = cf[ct * 16 + r16], sc = cf[64 + ct * 16 + r16], sh = cf[128 + ct * 16 + r16];
+#pragma unroll
+                for (int n = 0; n < NT; ++n)
+#pragma unroll
+                    for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            v[n][ch][r] = fmaf(lr[ct][n][ch][r], fmaxf(fmaf(acc[ct][n][ch][r] - mean, sc, sh), 0.f), v[n][ch][r]);
+            }
+            // the 16 channel lanes r16 of a DPP row: lane ^ 1, lane ^ 2 (quad permutes), then the quads of a half and the halves of the
+            // row by the mirror modes -- below each step the sums are equal in the lanes it pairs, so every lane ends with the same bits
+#pragma unroll
+            for (int n = 0; n < NT; ++n)
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        v[n][ch][r] = dpp_add<0x140>(dpp_add<0x141>(dpp_add<0x4E>(dpp_add<0xB1>(v[n][ch][r]))));   // quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror
+            // one lane per (row, half, pixel quad) stores: lane r16 = 2 n + ch, so the wave's 16 float4s leave as four 64-byte runs
+            float* Vb = a.hd_V + (int64_t)b * HW;
+#pragma unroll
+            for (int n = 0; n < NT; ++n)
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch) {
+                    const int yo = y0 + wn * NT + n, xo = x0 + 16 * ch + 4 * lq;
+                    if (r16 == 2 * n + ch && yo < a.H && xo < a.W) *reinterpret_cast<f32x4s*>(Vb + (int64_t)yo * a.W + xo) = v[n][ch];
+                }
+            continue;
         }
         // RD, part 1: the z tile of the unit below goes into registers FIRST (16 loads in flight; the fragment registers of the main loop
         // are dead here), the da stores below run while they travel, and the sums are taken after the stores
@@ -1573,10 +1643,10 @@ int sp_launch_persistent(void (*kern)(Args), PerDeviceOnce& once, int lds_bytes,
     return check_launch(name);
 }
 
-template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false>
+template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false>
 int launch_split_pre(SpPreArgs a, hipStream_t st) {
     using C = SpPreCfg<W16>;
-    const int LDS_BYTES = C::LDS_BYTES + (ST ? C::NW * 64 * 2 * 4 : 0) + (ACT ? 2 * 3 * 64 * 4 : 0);
+    const int LDS_BYTES = C::LDS_BYTES + (ST ? C::NW * 64 * 2 * 4 : 0) + (ACT || HEAD ? 2 * 3 * 64 * 4 : 0);
     a.tilesX = W16 ? 1 : cdiv(a.W, C::TW);
     a.tilesY = cdiv(a.H, C::ROWS);
     a.coTiles = cdiv(a.Cout, C::CO_T);
@@ -1586,14 +1656,16 @@ int launch_split_pre(SpPreArgs a, hipStream_t st) {
     // which launches take the 16x16x32 kernel (profiles/r05_mfma_shape_ab.md): plain bf16 operands (K = 32 channels: no packing) always; the
     // (hi | mid) forward WITH the statistics epilogue and the input gradients that carry the fused reduce (the lane layout's cheap
     // epilogues: -5 %); the plain (hi | mid) input gradient keeps the 32x32x16 kernel (equal speed), and so does the (hi | mid) 16-pixel
-    // level (that instance of the new kernel exceeds the register budget).
-    constexpr bool P16 = RD || PM == 2 || (ST && !W16);
+    // level (that instance of the new kernel exceeds the register budget).  The head epilogue exists on the 16x16x32 kernel alone.
+    constexpr bool P16 = RD || PM == 2 || (ST && !W16) || HEAD;
     void (*kern)(SpPreArgs);
-    if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD, ACT>;      // (constexpr: the instances not dispatched are not built)
+    if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD, ACT, HEAD>;      // (constexpr: the instances not dispatched are not built)
     else kern = conv3x3_split_pre_kernel<ST, PM, W16, ACT>;
     static PerDeviceOnce attr_once;
     return sp_launch_persistent(kern, attr_once, LDS_BYTES, tiles, C::NW * 64,
-                                ACT ? (PM == 2 ? "conv3x3_pre16_act_kernel" : "conv3x3_split_pre_act_kernel") : "conv3x3_split_pre_kernel", a, st);
+                                HEAD  ? (PM == 2 ? "conv3x3_pre16_head_kernel" : "conv3x3_split_pre_head_kernel")
+                                : ACT ? (PM == 2 ? "conv3x3_pre16_act_kernel" : "conv3x3_split_pre_act_kernel")
+                                      : "conv3x3_split_pre_kernel", a, st);
 }
 
 int split_nparts(int B, int H, int W) {
@@ -2564,6 +2636,43 @@ int onet_conv3x3_plain16_fwd_pre_act(const void* xs, int64_t xs_bs, const void* 
     p.act_a = a;
     p.act_a_bs = a_bs;
     return launch_split_pre<false, 2, false, false, true>(p, as_stream(stream));
+}
+
+// Labels-only inference: the model's LAST unit with the head in the convolution's epilogue (SpPreArgs::hd_*).  The two entries below run
+// the forward convolution of the _act entries above on the same operands, form h = max(0, fma(z - mean, sc, sh)) from save [4][Cout] on
+// the accumulators and write V [B][H][W] = sum_c L[c] h[c] (L: fp32 NCHW, batch stride L_bs) -- nothing else: neither z nor h is stored.
+// Returns 1 (nothing launched, nothing written) outside maps made of full 16 x 32 tiles, Cin % 32 (plain bf16) / % 16 (fp16), Cout == 64.
+static int pre_head_impl(const char* entry, int wq_f16, const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2,
+                         int split_ch, const void* wq, const float* save, const float* L, int64_t L_bs, float* V, int B, int Cin, int Cout,
+                         int H, int W, void* stream) {
+    ONET_REQUIRE(xs && wq && save && L && V, "%s: null pointer", entry);
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
+    if (W < 32 || (W % 32) || (H % 16) || (Cin % (wq_f16 == 2 ? 32 : 16)) || Cout != 64) return 1;
+    ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
+    ONET_REQUIRE((L_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(L) & 15) == 0 && (reinterpret_cast<uintptr_t>(V) & 15) == 0,
+                 "%s: 16-byte aligned rows required", entry);
+    if (const int rc = pre_operand_checks(entry, xs, xs_bs, wq_f16, Cin, Cout, H, W)) return rc;
+    ONET_REQUIRE(L_bs >= (int64_t)Cout * H * W, "%s: batch stride too small", entry);
+    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)x_amax, scale_always,
+                (const unsigned*)x_amax2, split_ch};
+    p.act_save = save;
+    p.hd_L = L;
+    p.hd_L_bs = L_bs;
+    p.hd_V = V;
+    if (wq_f16 == 2) return launch_split_pre<false, 2, false, false, false, true>(p, as_stream(stream));
+    return launch_split_pre<false, 1, false, false, false, true>(p, as_stream(stream));
+}
+
+int onet_conv3x3_plain16_fwd_pre_head(const void* xs, int64_t xs_bs, const void* wq, const float* save, const float* L, int64_t L_bs, float* V,
+                                      int B, int Cin, int Cout, int H, int W, void* stream) {
+    return pre_head_impl("conv3x3_plain16_fwd_pre_head", 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, L, L_bs, V, B, Cin, Cout, H, W, stream);
+}
+
+int onet_conv3x3_split_fwd_pre_head(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
+                                    const void* wq, const float* save, const float* L, int64_t L_bs, float* V, int B, int Cin, int Cout, int H,
+                                    int W, void* stream) {
+    return pre_head_impl("conv3x3_split_fwd_pre_head", 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, L, L_bs, V, B, Cin, Cout,
+                         H, W, stream);
 }
 
 // a[co] = relu(sc (z - mean) + sh) with |z[co]| <= sum_ci |w[co][ci][.]| max |x[ci]|:  |a[co]| <= |sc| (S1 max1 + S2 max2) + |sh - mean sc|,

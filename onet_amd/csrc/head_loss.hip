@@ -226,6 +226,27 @@ __global__ void argmax2_kernel(const float* __restrict__ S, int64_t* __restrict_
     }
 }
 
+// Labels-only inference: the head's softmax over (Vt, Vd) [B][HW] and / or its argmax, one thread per pixel.  S by
+// head_softmax_fwd_kernel's expressions, Y by argmax2_kernel's rule on that S (ties -> 0); either output may be NULL
+__global__ __launch_bounds__(256) void softmax2_labels_kernel(const float* __restrict__ Vt, const float* __restrict__ Vd, float* __restrict__ S,
+                                                              int64_t* __restrict__ Y, int B, int HW) {
+    const int64_t n = (int64_t)B * HW;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int b = (int)(i / HW);
+        const int p = (int)(i % HW);
+        const float vt = Vt[i], vd = Vd[i];
+        const float m = fmaxf(vt, vd);
+        const float et = expf(vt - m), ed = expf(vd - m);
+        const float den = et + ed;
+        const float s0 = et / den, s1 = ed / den;
+        if (S) {
+            S[((int64_t)b * 2 + 0) * HW + p] = s0;
+            S[((int64_t)b * 2 + 1) * HW + p] = s1;
+        }
+        if (Y) Y[i] = s1 > s0 ? 1 : 0;
+    }
+}
+
 static inline unsigned grid_px(int64_t n) {
     int64_t b = (n + 255) / 256;
     if (b > 8192) b = 8192;
@@ -301,6 +322,14 @@ int onet_argmax2(const float* S, int64_t* Y, int B, int HW, void* stream) {
     ONET_REQUIRE(S && Y && B > 0 && HW > 0, "argmax2: bad args");
     hipLaunchKernelGGL(argmax2_kernel, dim3(grid_px((int64_t)B * HW)), dim3(256), 0, as_stream(stream), S, Y, B, HW);
     return check_launch("argmax2_kernel");
+}
+
+int onet_softmax2_labels(const float* Vt, const float* Vd, float* S, int64_t* Y, int B, int HW, void* stream) {
+    ONET_REQUIRE(Vt && Vd, "softmax2_labels: null pointer");
+    ONET_REQUIRE(S || Y, "softmax2_labels: no output (S and Y are both null)");
+    ONET_REQUIRE(B > 0 && HW > 0, "softmax2_labels: bad shape");
+    hipLaunchKernelGGL(softmax2_labels_kernel, dim3(grid_px((int64_t)B * HW)), dim3(256), 0, as_stream(stream), Vt, Vd, S, Y, B, HW);
+    return check_launch("softmax2_labels_kernel");
 }
 
 }  // extern "C"

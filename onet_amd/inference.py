@@ -20,7 +20,13 @@ d - 1 is written as fp32 going down, ops.convT2x2_fwd_p writes slots coming back
 
 Settings.fused_eval = "bf16" runs the same plan on ONE part of plain bf16 per slot (ops.conv3x3_plain16_pre_act; layer predicate
 ops.eval_layer_ok_bf16): the operands conv == "bf16" trains with, one MFMA per product term instead of three and 2-byte slot elements.
-bf16 has fp32's exponent range, so that plan carries no magnitude slots at all: scale = amax = None on every tensor, no bound launches."""
+bf16 has fp32's exponent range, so that plan carries no magnitude slots at all: scale = amax = None on every tensor, no bound launches.
+
+Labels-only calls (scores, segment(head="fused")): the same plan on either slot format, ending in ONE launch for the last unit and the
+head's channel product (ops.conv3x3_plain16_pre_head / conv3x3_split_pre_head: relu(bn(.)) on the accumulators, times L, summed over
+the unit's 64 channels, V the only store) followed by ops.softmax2_labels.  The last unit's fp32 pre-activation -- the largest tensor
+of the forward -- is never written, the head kernel does not run, and segment does not materialise S.  Onet.forward does not take this
+route: under every setting it launches what it launched before these calls existed."""
 from __future__ import annotations
 
 import torch
@@ -101,11 +107,21 @@ def _depth(unet, N, H, W):
     return 5, None
 
 
-def unet_plan(unet, shape, device=None):
+def _head_ok(unet):
+    """Does the last unit fit the convolution with the head epilogue (ops.conv3x3_*_pre_head: one 64-channel tile per pixel)?"""
+    return _units(_blocks(unet)[2][0].conv)[2].out_channels == 64
+
+
+def unet_plan(unet, shape, device=None, head=None):
     """What the fused plan does with a U-Net pass over an input of `shape` = (N, C, H, W): a pure query, nothing is launched.
     -> {"fused": bool, "reason": why not | None, "depth": d, "batch": N, "layers": {name: "stem" | "fused" | "two-pass" | "plain+head"
-    | "fallback"}, "convt": {name: "slots" | "fp32->slots" | "fallback"}, "fallback_reason": why level d is not fused | None,
-    "operands": the slot format the settings select, "fp16x2" | "bf16" (None: Settings.fused_eval is off)}"""
+    | "fused+head" | "fallback"}, "convt": {name: "slots" | "fp32->slots" | "fallback"}, "fallback_reason": why level d is not fused |
+    None, "operands": the slot format the settings select, "fp16x2" | "bf16" (None: Settings.fused_eval is off)}
+    head = "fused": the plan of the labels-only calls (scores, segment(head="fused")) -- "fused+head" where the last unit runs with the
+    head in its epilogue; a last unit outside that kernel's domain (Cout != 64) sends those calls to the ordinary forward, whose plan
+    this then is ("plain+head")."""
+    if head not in (None, "fused"):
+        raise ValueError(f"onet_amd: head must be None or 'fused', not {head!r}")
     out = {"fused": False, "reason": None, "depth": 0, "batch": int(shape[0]) if len(shape) == 4 else 0, "layers": {}, "convt": {},
            "fallback_reason": None, "operands": ops.fused_eval_operands()}
     if len(shape) != 4:
@@ -141,7 +157,7 @@ def unet_plan(unet, shape, device=None):
             if k >= d:
                 kind = "fallback"
             elif name == "up4.c2":
-                kind = "plain+head"
+                kind = "fused+head" if head == "fused" and _head_ok(unet) else "plain+head"
             elif name.endswith(".c2") and name[:2] != "up" and k < 4:
                 kind = "two-pass"             # pooled units: plain convolution + BatchNorm / ReLU / pooling pass writing slots
             else:
@@ -158,12 +174,16 @@ def unet_plan(unet, shape, device=None):
     return out
 
 
-def fused_eval_plan(model, shape):
+def fused_eval_plan(model, shape, head=None):
     """What `model(X)` does with an input of `shape` (B, C, H, W) under its settings: see unet_plan.  For an Onet the batch through
     each U-Net is 2 B when the weights are shared and the twin batch is on ("twin": True), B otherwise (two passes).
+    head = "fused": what scores(model, X) / segment(model, X, head="fused") do instead ("fused+head" for up4.c2 where the fused launch
+    runs; both U-Nets of an unshared model must qualify).
     The answer holds for the model's device: ops.eval_layer_ok follows the convolution dispatch, which asks for enough tiles to fill
     that device's compute units, so the fused depth of a small batch can differ between devices."""
     from .modules import Onet
+    if head not in (None, "fused"):
+        raise ValueError(f"onet_amd: head must be None or 'fused', not {head!r}")
     if not isinstance(model, Onet):
         return unet_plan(model, tuple(shape))
     with ops.using(model.settings):
@@ -171,10 +191,12 @@ def fused_eval_plan(model, shape):
         shp = tuple(shape)
         if len(shp) == 4 and twin:
             shp = (2 * shp[0],) + shp[1:]
-        plan = unet_plan(model.topu, shp)
+        if head == "fused" and not (_head_ok(model.topu) and _head_ok(model.dwnu)):
+            head = None
+        plan = unet_plan(model.topu, shp, head=head)
         plan["twin"] = bool(twin)
         if plan["fused"] and model.dwnu is not model.topu:
-            other = unet_plan(model.dwnu, shp)
+            other = unet_plan(model.dwnu, shp, head=head)
             if not other["fused"]:
                 plan.update(fused=False, reason="dwnu: " + str(other["reason"]), depth=0)
         return plan
@@ -300,8 +322,23 @@ def _tail(unet, k, xk):
     return ups[k](_tail(unet, k + 1, downs[k](xk)), xk)
 
 
-def _unet_pass(unet, x, d):
-    """-> (L = inc's output fp32, z = the last unit's pre-activation, save = its coefficients): the head forms relu(bn(z)) on load"""
+def _head_unit(conv, bn, t, L):
+    """The last Conv-BatchNorm-ReLU unit with the head's channel product in the epilogue -> V [N, 1, H, W]"""
+    save = _coeffs(bn)
+    if t.P.shape[3] == 1:
+        V = ops.conv3x3_plain16_pre_head(t.P, _wq(conv, 1), conv.out_channels, save, L)
+    else:
+        s1, s2, ch = ops._slots3(t.scale)
+        V = ops.conv3x3_split_pre_head(t.P, _wq(conv), conv.out_channels, save, L, slots=s1, slots2=s2, split_ch=ch)
+    if V is None:
+        raise RuntimeError("onet_amd: the fused head kernel refused a shape the plan accepted")
+    return V
+
+
+def _unet_pass(unet, x, d, head=False):
+    """-> (L = inc's output fp32, z = the last unit's pre-activation, save = its coefficients): the head forms relu(bn(z)) on load.
+    head=True (labels-only calls; the caller has checked _head_ok): the last unit ends in the fused launch -> V [N, 1, H, W] =
+    sum_c L[c] relu(bn(z))[c]; z is never written and L is dropped with the pass."""
     enc, downs, ups = _blocks(unet)
     N, _, H, W = x.shape
     dev = x.device
@@ -349,6 +386,8 @@ def _unet_pass(unet, x, d):
         if k > 0:
             up = ups[k - 1].up
             t = _note(unames[k] + ".c2", _fused_unit(c2, b2, t, keep_fp32=not ops.convt_slots_ok(N, up.in_channels, up.out_channels, H >> k, W >> k, parts=P)))
+        elif head:
+            return _head_unit(c2, b2, t, L)
         else:
             z, save = _plain_conv(c2, t), _coeffs(b2)
     return L, z, save
@@ -395,9 +434,58 @@ def onet_forward(onet, X):
     return Lt, Vt, Ld, Vd, S
 
 
-def segment(onet, X):
-    """int64 [B, H, W] labels of `X`: predict_label of the forward under no_grad (the fused plan when `onet.settings.fused_eval` is on
-    and the model qualifies), without keeping the five outputs alive."""
+def _head_scores(onet, X):
+    """(Vt, Vd) [B, 1, H, W] by the fused plan ending in the head-epilogue launch, or None where that does not apply (the caller runs
+    the ordinary forward).  Called with the model's settings active, under no_grad."""
+    if not (ops.fused_eval() and not onet.training and not torch.is_grad_enabled() and _input_ok(X)):
+        return None
+    shared = onet.dwnu is onet.topu
+    twin = shared and ops.twin_enabled()
+    B, C, H, W = X.shape
+    N = 2 * B if twin else B
+    for u in ((onet.topu,) if shared else (onet.topu, onet.dwnu)):
+        if _static_reason(u) is not None or C != u.inc.double_conv[0].in_channels or _depth(u, N, H, W)[0] == 0 or not _head_ok(u):
+            return None
+    X = X.contiguous()
+    ops.amax_arena_reset(X.device)
+    if twin:
+        XX = ops.twin_materialize(src=(X, float(onet.bias)))
+        V = _unet_pass(onet.topu, XX, _depth(onet.topu, N, H, W)[0], head=True)
+        return V[:B], V[B:]
+    Vt = _unet_pass(onet.topu, X, _depth(onet.topu, N, H, W)[0], head=True)
+    Xd = ops.complement_clip(X, float(onet.bias))
+    Vd = _unet_pass(onet.dwnu, Xd, _depth(onet.dwnu, N, H, W)[0], head=True)
+    return Vt, Vd
+
+
+def scores(onet, X):
+    """(Vt, Vd, S) of `X` -- the forward's outputs 1, 3 and 4, same shapes and dtypes -- under no_grad.  Where the fused plan applies
+    (`onet.settings.fused_eval` on, eval mode, a last unit of 64 channels) the last convolution carries the head in its epilogue
+    (ops.conv3x3_*_pre_head): the fp32 pre-activation of the last unit, the forward's largest tensor, is never written and the head
+    kernel's read of it is gone; Vt / Vd then agree with the forward's to the rounding of a 64-term dot product (another, fixed,
+    summation order).  Elsewhere: the ordinary forward's tensors, bit for bit."""
     with torch.no_grad():
+        with ops.using(onet.settings):
+            VV = _head_scores(onet, X)
+            if VV is not None:
+                S, _ = ops.softmax2_labels(VV[0], VV[1], want_S=True, want_labels=False)
+                return VV[0], VV[1], S
+        out = onet(X)
+        return out[1], out[3], out[4]
+
+
+def segment(onet, X, head=None):
+    """int64 [B, H, W] labels of `X`: predict_label of the forward under no_grad (the fused plan when `onet.settings.fused_eval` is on
+    and the model qualifies), without keeping the five outputs alive.
+    head = "fused": the labels of scores(onet, X) -- the last convolution with the head in its epilogue, then one streaming launch that
+    writes the labels alone: neither the last pre-activation nor S is materialised.  Where that plan does not apply: as head=None."""
+    if head not in (None, "fused"):
+        raise ValueError(f"onet_amd.segment: head must be None or 'fused', not {head!r}")
+    with torch.no_grad():
+        if head == "fused":
+            with ops.using(onet.settings):
+                VV = _head_scores(onet, X)
+                if VV is not None:
+                    return ops.softmax2_labels(VV[0], VV[1], want_S=False, want_labels=True)[1]
         S = onet(X)[4]
         return onet.predict_label(S)

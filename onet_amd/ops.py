@@ -1279,6 +1279,48 @@ def conv3x3_split_pre_act(xs, wq, Cout, save, aP_slots, out=None, slots=None, sl
     return out if rc == 0 else None
 
 
+def _pre_head(entry, kind, two, xs, wq, Cout, save, L, out, extra):
+    name = entry[len("onet_"):]
+    B, C8, H, _, W, _ = xs.shape
+    Cin = C8 * 8
+    if tuple(L.shape) != (B, Cout, H, W) or L.dtype != F32:
+        raise ValueError(f"{name}: L must be an fp32 [B, Cout, H, W] tensor of the convolution's output shape")
+    L, lbs = plane(L)
+    if out is None:
+        out = torch.empty((B, 1, H, W), dtype=F32, device=xs.device)
+    elif tuple(out.shape) != (B, 1, H, W) or out.dtype != F32 or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous fp32 [B, 1, H, W] tensor")
+    e0 = _prof_begin(kind)
+    rc = getattr(_lib.load(), entry)(_p(xs), _pbs(xs), *extra, _p(wq), _p(save), _p(L), lbs, _p(out), B, Cin, Cout, H, W, _stream())
+    _prof_end(kind, 2.0 * B * H * W * Cin * Cout * 9 if rc == 0 else 0.0, e0,
+              (B * H * W * (2.0 * two * Cin + 4.0 * Cout + 4.0) + 2.0 * two * 9 * Cin * Cout) if rc == 0 else 0.0)
+    if rc < 0:
+        raise _lib.OnetHipError(f"{entry} failed ({rc}): {_lib.last_error()}")
+    return out if rc == 0 else None
+
+
+def conv3x3_plain16_pre_head(xs, wq, Cout, save, L, out=None):
+    """V [B, 1, H, W] = sum_c L[c] relu(bn(conv3x3(xs)))[c] on PLAIN bf16 operands (conv3x3_plain16_pre_act's), the model's last unit
+    with the head's channel product in the convolution's epilogue: neither the pre-activation nor the activation is written.  `save`
+    [4, Cout] (bn_eval_coeffs); L: fp32 [B, Cout, H, W], a batch slice of a larger tensor qualifies; out: optional contiguous
+    destination.  The accumulators are those of conv3x3_split_pre's launch bit for bit; the channel sum runs in the kernel's own fixed
+    order.  -> V, or None where the kernel does not take the shape (Cout != 64, maps not made of full 16 x 32 tiles, Cin % 32: nothing
+    launched, nothing written)."""
+    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
+        raise TypeError("conv3x3_plain16_pre_head: xs and wq must be one-part bf16 packs on the GPU")
+    return _pre_head("onet_conv3x3_plain16_fwd_pre_head", "conv3x3_pre16_head_kernel", 1, xs, wq, Cout, save, L, out, ())
+
+
+def conv3x3_split_pre_head(xs, wq, Cout, save, L, out=None, slots=None, slots2=None, split_ch=0):
+    """conv3x3_plain16_pre_head on fp16 (hi | mid) parts (conv3x3_split_pre_act's operands; slots / slots2 / split_ch: the magnitude
+    slots the producers scaled xs by).  The convolution runs on the 16x16x32 kernel: its accumulators agree with conv3x3_split_pre's
+    (the 32x32x16 kernel) to fp32 accumulation order.  -> V, or None (Cout != 64, maps not made of full tiles, Cin % 16)."""
+    if wq is None or not wq.is_cuda or wq.dtype != torch.float16 or xs.dtype != torch.float16 or xs.shape[3] != 2:
+        raise TypeError("conv3x3_split_pre_head: xs and wq must be fp16 (hi | mid) split packs on the GPU")
+    return _pre_head("onet_conv3x3_split_fwd_pre_head", "conv3x3_split_pre_head_kernel", 2, xs, wq, Cout, save, L, out,
+                     (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)))
+
+
 FUSE_DGRAD_REDUCE = _flag("FUSE_DGRAD_REDUCE", True)      # False (tests / A-B): the first unit of a DoubleConv runs its own BatchNorm-backward reduce pass
 
 
@@ -2221,6 +2263,23 @@ def argmax2(S):
     Y = torch.empty((B, H, W), dtype=torch.int64, device=S.device)
     _lib.call("onet_argmax2", _p(S), _p(Y), B, H * W, _stream())
     return Y
+
+
+def softmax2_labels(Vt, Vd, want_S=True, want_labels=True):
+    """-> (S [B, 2, H, W] | None, Y int64 [B, H, W] | None) from the head's Vt, Vd [B, 1, H, W]: S by head_softmax_fwd's expressions,
+    Y = argmax2(S) (ties -> 0), in one streaming launch; an output that is not wanted is neither allocated nor written."""
+    require_gpu(Vt, Vd)
+    if Vt.shape != Vd.shape or Vt.dim() != 4 or Vt.shape[1] != 1 or Vt.dtype != F32 or Vd.dtype != F32:
+        raise ValueError("softmax2_labels: Vt and Vd must be fp32 [B, 1, H, W] tensors of one shape")
+    if not (want_S or want_labels):
+        raise ValueError("softmax2_labels: nothing asked for")
+    Vt, Vd = Vt.contiguous(), Vd.contiguous()
+    B, _, H, W = Vt.shape
+    S = torch.empty((B, 2, H, W), dtype=F32, device=Vt.device) if want_S else None
+    Y = torch.empty((B, H, W), dtype=torch.int64, device=Vt.device) if want_labels else None
+    _lib.call("onet_softmax2_labels", _p(Vt), _p(Vd), _p(S), _p(Y), B, H * W, _stream(),
+              nbytes=4.0 * B * H * W * (2 + 2 * want_S + 2 * want_labels))
+    return S, Y
 
 
 # ----------------------------------------------------------------------------- optimizer
