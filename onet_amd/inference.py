@@ -26,12 +26,22 @@ Labels-only calls (scores, segment(head="fused")): the same plan on either slot 
 head's channel product (ops.conv3x3_plain16_pre_head / conv3x3_split_pre_head: relu(bn(.)) on the accumulators, times L, summed over
 the unit's 64 channels, V the only store) followed by ops.softmax2_labels.  The last unit's fp32 pre-activation -- the largest tensor
 of the forward -- is never written, the head kernel does not run, and segment does not materialise S.  Onet.forward does not take this
-route: under every setting it launches what it launched before these calls existed."""
+route: under every setting it launches what it launched before these calls existed.
+
+Every decision about what runs where is taken once per U-Net pass, by _build_plan: the query (unet_plan, fused_eval_plan) prints its
+record, the executor (_unet_pass) follows it, and _gate is the one place that says whether the plan runs at all and on which passes.
+The slot format is chosen once per plan (_format); the units below take it from there."""
 from __future__ import annotations
+
+from collections import namedtuple
 
 import torch
 
 from . import ops
+
+
+_ENC = ("inc", "down1", "down2", "down3", "down4")        # the encoder block of level k
+_DEC = ("up4", "up3", "up2", "up1")                       # the Up block of level k (up4: the full-size level's, the last one applied)
 
 
 def _blocks(unet):
@@ -46,7 +56,21 @@ def _units(blk):
     return s[0], s[1], s[3], s[4]
 
 
-def _static_reason(unet):
+# The slot format of a plan: parts per slot, the weight pack, the layer predicate, the two launches, whether tensors carry magnitude
+# slots (without them: scale = amax = None everywhere, no bound launches) and whether the pooled tensors are traced
+_Format = namedtuple("_Format", "operands parts pack layer_ok act head magnitude trace_pool")
+
+
+def _format():
+    """The format Settings.fused_eval selects: fp16 (hi | mid) parts, or one part of plain bf16 ("bf16")"""
+    name = ops.fused_eval_operands()
+    if name == "bf16":
+        # (trace_pool: the one-part plan's trace is complete -- every convolution's exact input can be rebuilt)
+        return _Format(name, 1, "plain16", ops.eval_layer_ok_bf16, ops.conv3x3_plain16_pre_act, ops.conv3x3_plain16_pre_head, False, True)
+    return _Format(name, 2, "split", ops.eval_layer_ok, ops.conv3x3_split_pre_act, ops.conv3x3_split_pre_head, True, False)
+
+
+def _static_reason(unet, fmt):
     """Why the plan cannot run on this U-Net whatever the input (None: it can)."""
     from .modules import ConvT2x2, _hooked
     if unet.training:
@@ -58,7 +82,7 @@ def _static_reason(unet):
             return "a BatchNorm without running statistics (or in training mode)"
     if _hooked(unet):
         return "a forward hook watches a block"
-    if _parts() == 1:
+    if fmt.parts == 1:
         if not ops.presplit():
             return "pre-split storage is off under the effective convolution algorithm"
     elif not (ops.presplit() and ops.p16_parts() == 2):
@@ -66,43 +90,35 @@ def _static_reason(unet):
     return None
 
 
-def _parts():
-    """Parts per slot of the active plan: 2 = fp16 (hi | mid), 1 = plain bf16 (Settings.fused_eval = "bf16")"""
-    return 1 if ops.fused_eval_operands() == "bf16" else 2
+def _level_units(unet):
+    """-> [level] -> (encoder units, decoder units) of that level's maps, each [(name, conv, bn)] in execution order, of the 3x3
+    convolutions the plan runs on pre-split operands (all but the stem)"""
+    def named(name, blk):
+        c1, b1, c2, b2 = _units(blk)
+        return [(name + ".c1", c1, b1), (name + ".c2", c2, b2)]
+    enc, _, ups = _blocks(unet)
+    out = [(named(_ENC[k], enc[k]), named(_DEC[k], ups[k].conv) if k < 4 else []) for k in range(5)]
+    out[0] = (out[0][0][1:], out[0][1])
+    return out
 
 
 def _level_layers(unet):
     """-> [level] -> [(name, conv)] of the 3x3 convolutions on that level's maps that the plan runs on pre-split operands"""
-    enc, _, ups = _blocks(unet)
-    names = ("inc", "down1", "down2", "down3", "down4")
-    unames = ("up4", "up3", "up2", "up1")
-    out = []
-    for k in range(5):
-        c1, _, c2, _ = _units(enc[k])
-        lv = [(names[k] + ".c2", c2)] if k == 0 else [(names[k] + ".c1", c1), (names[k] + ".c2", c2)]
-        if k < 4:
-            d1, _, d2, _ = _units(ups[k].conv)
-            lv += [(unames[k] + ".c1", d1), (unames[k] + ".c2", d2)]
-        out.append(lv)
-    return out
+    return [[(name, conv) for name, conv, _ in e + d] for e, d in _level_units(unet)]
 
 
-def _depth(unet, N, H, W):
+def _depth(units, ups, layer_ok, N, H, W):
     """-> (d, why level d is not fused | None): levels 0 .. d - 1 are fused"""
-    enc, _, ups = _blocks(unet)
-    levels = _level_layers(unet)
-    layer_ok = ops.eval_layer_ok_bf16 if _parts() == 1 else ops.eval_layer_ok
-    for k in range(5):
+    for k, (e, d) in enumerate(units):
         if (H % (1 << k)) or (W % (1 << k)):
             return k, f"level {k}: the input size is not a multiple of {1 << k}"
         h, w = H >> k, W >> k
-        for name, conv in levels[k]:
+        for name, conv, _ in e + d:
             if not layer_ok(N, conv.in_channels, conv.out_channels, h, w):
                 return k, f"level {k}: {name} ({conv.in_channels} -> {conv.out_channels} on {N} maps of {h} x {w}) is outside ops.{layer_ok.__name__}"
         if k < 4:
-            C = _units(enc[k])[2].out_channels
-            d1 = _units(ups[k].conv)[0]
-            if C % 32 or d1.in_channels != C + ups[k].up.out_channels or ups[k].up.out_channels % 8:
+            C, up = e[-1][1].out_channels, ups[k].up
+            if C % 32 or d[0][1].in_channels != C + up.out_channels or up.out_channels % 8:
                 return k, f"level {k}: the concat buffer's channel groups do not fit the slot layout"
     return 5, None
 
@@ -110,6 +126,88 @@ def _depth(unet, N, H, W):
 def _head_ok(unet):
     """Does the last unit fit the convolution with the head epilogue (ops.conv3x3_*_pre_head: one 64-channel tile per pixel)?"""
     return _units(_blocks(unet)[2][0].conv)[2].out_channels == 64
+
+
+def _check_head(head):
+    if head not in (None, "fused"):
+        raise ValueError(f"onet_amd: head must be None or 'fused', not {head!r}")
+
+
+# ----------------------------------------------------------------------------- the plan record
+# One unit (Conv-BatchNorm-ReLU) of a pass.  kind: what unet_plan prints; keep_fp32: a unit that writes slots also writes fp32, for a
+# ConvTranspose2d that reads it as "fp32->slots"
+_Unit = namedtuple("_Unit", "name conv bn kind keep_fp32")
+# One level: its encoder and decoder units in execution order, the ConvTranspose2d that fills its concat buffer with its kind ("slots":
+# from the slots of the level below; "fp32->slots": from an fp32 tensor; level 4 has none), and whether the pooled tensor leaves as
+# slots (fp32: for the fall-back levels)
+_Level = namedtuple("_Level", "enc dec up convt pooled_slots")
+# One U-Net pass.  reason: why the plan does not run (None: it runs); static: the part of it that holds whatever the input;
+# levels 0 .. depth - 1 are fused, fallback_reason says why level `depth` is not; head: the last unit ends in the head-epilogue launch
+_Plan = namedtuple("_Plan", "fmt batch reason static depth fallback_reason unet levels head", defaults=(None, 0, None, None, (), False))
+
+_WHY_CHANNELS = "the input's channels do not match the stem"
+
+
+def _build_plan(unet, shape, head=None):
+    """The record of a pass of `unet` over an input of `shape` = (N, C, H, W) under the active settings -- every decision the query
+    announces and the executor follows, taken here and nowhere else.  Built per call (training flags, hooks, settings and running
+    statistics may change between calls); touches no device beyond ops.n_cu()."""
+    N, C, H, W = shape
+    fmt = _format()
+    why = _static_reason(unet, fmt)
+    if why is not None:
+        return _Plan(fmt, N, why, why)
+    if C != unet.inc.double_conv[0].in_channels:
+        return _Plan(fmt, N, _WHY_CHANNELS)
+    units, ups = _level_units(unet), _blocks(unet)[2]
+    d, why_d = _depth(units, ups, fmt.layer_ok, N, H, W)
+    if d == 0:
+        return _Plan(fmt, N, why_d, None, 0, why_d)
+    # the ConvTranspose2d of level k reads the output of level k + 1: slots where that level is fused and the slot-operand kernel takes
+    # the map, else the fp32 tensor its producer -- the last unit of level k + 1, or the fall-back levels -- leaves
+    convt = ["fallback" if k >= d else
+             "slots" if k + 1 < d and ops.convt_slots_ok(N, up.up.in_channels, up.up.out_channels, H >> (k + 1), W >> (k + 1), parts=fmt.parts) else
+             "fp32->slots" for k, up in enumerate(ups)]
+    with_head = head == "fused" and _head_ok(unet)
+    levels = []
+    for k, (e, dec) in enumerate(units):
+        kind = dict.fromkeys((name for name, _, _ in e + dec), "fused" if k < d else "fallback")
+        if k < min(d, 4):
+            kind[e[-1][0]] = "two-pass"           # pooled units: plain convolution + BatchNorm / ReLU / pooling pass writing slots
+        if k == 0:
+            e = [("inc.c1",) + _units(unet.inc)[:2]] + e
+            kind["inc.c1"], kind[dec[-1][0]] = "stem", ("fused+head" if with_head else "plain+head")
+        keep = {(dec or e)[-1][0]} if 0 < k < d and convt[k - 1] == "fp32->slots" else ()
+        enc_u, dec_u = ([_Unit(name, conv, bn, kind[name], name in keep) for name, conv, bn in us] for us in (e, dec))
+        levels.append(_Level(enc_u, dec_u, ups[k].up if k < 4 else None, convt[k] if k < 4 else None, k + 1 < d))
+    return _Plan(fmt, N, None, None, d, why_d, unet, tuple(levels), with_head)
+
+
+def _query(unet, shape, head=None, device=None):
+    """_build_plan for a caller that has a shape and no tensor: behind the checks the executors make on the input itself"""
+    fmt, shape = _format(), tuple(shape)
+    if len(shape) != 4:
+        return _Plan(fmt, 0, "the input is not 4-D")
+    N, C, H, W = (int(v) for v in shape)
+    if N <= 0:
+        C = None        # (an empty batch is announced as a channel mismatch; the executors leave its refusal to the kernels)
+    dev = device if device is not None else next(unet.parameters()).device
+    if dev.type != "cuda":
+        return _Plan(fmt, N, "the model is not on a GPU")
+    if not ops.fused_eval():
+        return _Plan(fmt, N, "Settings.fused_eval is off")
+    with torch.cuda.device(dev):
+        return _build_plan(unet, (N, C, H, W), head)
+
+
+def _plan_dict(plan):
+    out = {"fused": plan.reason is None, "reason": plan.reason, "depth": plan.depth, "batch": plan.batch, "layers": {}, "convt": {},
+           "fallback_reason": plan.fallback_reason, "operands": plan.fmt.operands}
+    for k, lv in enumerate(plan.levels):
+        out["layers"].update((u.name, u.kind) for u in lv.enc + lv.dec)
+        if lv.up is not None:
+            out["convt"][_DEC[k]] = lv.convt
+    return out
 
 
 def unet_plan(unet, shape, device=None, head=None):
@@ -120,58 +218,35 @@ def unet_plan(unet, shape, device=None, head=None):
     head = "fused": the plan of the labels-only calls (scores, segment(head="fused")) -- "fused+head" where the last unit runs with the
     head in its epilogue; a last unit outside that kernel's domain (Cout != 64) sends those calls to the ordinary forward, whose plan
     this then is ("plain+head")."""
-    if head not in (None, "fused"):
-        raise ValueError(f"onet_amd: head must be None or 'fused', not {head!r}")
-    out = {"fused": False, "reason": None, "depth": 0, "batch": int(shape[0]) if len(shape) == 4 else 0, "layers": {}, "convt": {},
-           "fallback_reason": None, "operands": ops.fused_eval_operands()}
-    if len(shape) != 4:
-        out["reason"] = "the input is not 4-D"
-        return out
-    dev = device if device is not None else next(unet.parameters()).device
-    if dev.type != "cuda":
-        out["reason"] = "the model is not on a GPU"
-        return out
-    if not ops.fused_eval():
-        out["reason"] = "Settings.fused_eval is off"
-        return out
-    why = _static_reason(unet)
-    if why is not None:
-        out["reason"] = why
-        return out
-    N, C, H, W = (int(v) for v in shape)
-    if C != unet.inc.double_conv[0].in_channels or N <= 0:
-        out["reason"] = "the input's channels do not match the stem"
-        return out
-    with torch.cuda.device(dev):
-        d, why_d = _depth(unet, N, H, W)
-    out["depth"], out["fallback_reason"] = d, why_d
-    if d == 0:
-        out["reason"] = why_d
-        return out
-    out["fused"] = True
-    _, _, ups = _blocks(unet)
-    unames = ("up4", "up3", "up2", "up1")
-    out["layers"]["inc.c1"] = "stem"
-    for k, lv in enumerate(_level_layers(unet)):
-        for name, _ in lv:
-            if k >= d:
-                kind = "fallback"
-            elif name == "up4.c2":
-                kind = "fused+head" if head == "fused" and _head_ok(unet) else "plain+head"
-            elif name.endswith(".c2") and name[:2] != "up" and k < 4:
-                kind = "two-pass"             # pooled units: plain convolution + BatchNorm / ReLU / pooling pass writing slots
-            else:
-                kind = "fused"
-            out["layers"][name] = kind
-    for k in range(4):
-        up = ups[k].up
-        if k >= d:
-            out["convt"][unames[k]] = "fallback"
-        elif k + 1 < d and ops.convt_slots_ok(N, up.in_channels, up.out_channels, H >> (k + 1), W >> (k + 1), parts=_parts()):
-            out["convt"][unames[k]] = "slots"
-        else:
-            out["convt"][unames[k]] = "fp32->slots"
-    return out
+    _check_head(head)
+    return _plan_dict(_query(unet, shape, head, device))
+
+
+def _gate(model, shape, head=None, x=None):
+    """Does the plan run for `model` (an Onet or a UNet) on an input of `shape`, and with which passes?  -> ([(unet, plan)], twin): one
+    pass per U-Net, over a batch of 2 B where the twin batch is on; the plan runs where every record's reason is None (_runs).
+    x: the input itself, for the executors (`shape` is then its own) -- an input or a mode the plan never takes gives no passes at all;
+    None: a query by shape.
+    head = "fused" holds only where the last unit of every U-Net fits the head-epilogue launch."""
+    if x is not None:
+        if not (ops.fused_eval() and not model.training and not torch.is_grad_enabled() and _input_ok(x)):
+            return [], False
+        shape = x.shape
+    from .modules import Onet
+    unets, twin, shape = (model,), False, tuple(shape)
+    if isinstance(model, Onet):
+        shared = model.dwnu is model.topu
+        unets, twin = ((model.topu,) if shared else (model.topu, model.dwnu)), bool(shared and ops.twin_enabled())
+    if twin and len(shape) == 4:
+        shape = (2 * shape[0],) + shape[1:]
+    if head == "fused" and not all(_head_ok(u) for u in unets):
+        head = None
+    build = _query if x is None else _build_plan
+    return [(u, build(u, shape, head)) for u in unets], twin
+
+
+def _runs(passes):
+    return bool(passes) and all(plan.reason is None for _, plan in passes)
 
 
 def fused_eval_plan(model, shape, head=None):
@@ -182,23 +257,16 @@ def fused_eval_plan(model, shape, head=None):
     The answer holds for the model's device: ops.eval_layer_ok follows the convolution dispatch, which asks for enough tiles to fill
     that device's compute units, so the fused depth of a small batch can differ between devices."""
     from .modules import Onet
-    if head not in (None, "fused"):
-        raise ValueError(f"onet_amd: head must be None or 'fused', not {head!r}")
+    _check_head(head)
     if not isinstance(model, Onet):
         return unet_plan(model, tuple(shape))
     with ops.using(model.settings):
-        twin = model.dwnu is model.topu and ops.twin_enabled()
-        shp = tuple(shape)
-        if len(shp) == 4 and twin:
-            shp = (2 * shp[0],) + shp[1:]
-        if head == "fused" and not (_head_ok(model.topu) and _head_ok(model.dwnu)):
-            head = None
-        plan = unet_plan(model.topu, shp, head=head)
-        plan["twin"] = bool(twin)
-        if plan["fused"] and model.dwnu is not model.topu:
-            other = unet_plan(model.dwnu, shp, head=head)
-            if not other["fused"]:
-                plan.update(fused=False, reason="dwnu: " + str(other["reason"]), depth=0)
+        passes, twin = _gate(model, shape, head)
+        plan = _plan_dict(passes[0][1])
+        plan["twin"] = twin
+        for _, other in passes[1:]:
+            if plan["fused"] and other.reason is not None:
+                plan.update(fused=False, reason="dwnu: " + str(other.reason), depth=0)
         return plan
 
 
@@ -230,80 +298,87 @@ def _coeffs(bn):
     return ops.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
 
 
-def _bound(conv, save, t):
-    s1, s2, ch = ops._slots3(t.amax)
+def _amax(t):
+    return t.amax if t.amax is not None else ops.absmax_slots(t.F)
+
+
+def _bound(fmt, conv, save, t):
+    """The scale slots of relu(bn(conv(t))), from the magnitude of `t` (None on a format without magnitude slots)"""
+    if not fmt.magnitude:
+        return None
+    s1, s2, ch = ops._slots3(_amax(t))
     return ops.conv3x3_act_bound(conv.weight, save, s1, s2, ch)
 
 
-def _wq(conv, parts=2):
-    return conv.packed().get_pack("split" if parts == 2 else "plain16")[0]
+def _wq(fmt, conv):
+    return conv.packed().get_pack(fmt.pack)[0]
 
 
-def _fused_unit(conv, bn, t, keep_fp32=False):
-    """Conv-BatchNorm-ReLU in one launch, output as slots (+ fp32 when another reader needs it)"""
-    save = _coeffs(bn)
-    if t.P.shape[3] == 1:             # plain bf16: unscaled, nothing to bound or record
-        B, _, H, _, W, _ = t.P.shape
-        a = torch.empty((B, conv.out_channels, H, W), dtype=torch.float32, device=t.P.device) if keep_fp32 else None
-        aP = ops.conv3x3_plain16_pre_act(t.P, _wq(conv, 1), conv.out_channels, save, a=a)
-        if aP is None:
-            raise RuntimeError("onet_amd: the fused eval kernel refused a shape ops.eval_layer_ok_bf16 accepted")
-        return _T(aP, a)
-    scale = _bound(conv, save, t)
-    B, _, H, _, W, _ = t.P.shape
-    amax = ops.new_amax(t.P.device)
-    a = torch.empty((B, conv.out_channels, H, W), dtype=torch.float32, device=t.P.device) if keep_fp32 else None
+def _slot_kw(fmt, t, **out):
+    """The magnitude-slot arguments of a convolution launch on operand `t` (out: those of its output) -- none on a format without"""
+    if not fmt.magnitude:
+        return {}
     s1, s2, ch = ops._slots3(t.scale)
-    aP = ops.conv3x3_split_pre_act(t.P, _wq(conv), conv.out_channels, save, scale, slots=s1, slots2=s2, split_ch=ch, a_amax=amax, a=a)
+    return dict(out, slots=s1, slots2=s2, split_ch=ch)
+
+
+def _stem_unit(fmt, u, x):
+    """The stem: the existing direct kernel, then one BatchNorm + ReLU pass that writes slots"""
+    N, _, H, W = x.shape
+    z0 = ops.conv3x3_auto(x, u.conv.packed(), 0)
+    save0 = _coeffs(u.bn)
+    scale0 = _bound(fmt, u.conv, save0, _T(None, x))
+    a0 = ops.p16_empty(N, u.conv.out_channels, H, W, x.device, parts=fmt.parts)
+    ops.bn_relu_apply_split(z0, save0, a0, slots=scale0)
+    return _T(a0, None, scale0, scale0)
+
+
+def _fused_unit(fmt, u, t):
+    """Conv-BatchNorm-ReLU in one launch, output as slots (+ fp32 when another reader needs it)"""
+    conv = u.conv
+    save = _coeffs(u.bn)
+    scale = _bound(fmt, conv, save, t)
+    B, _, H, _, W, _ = t.P.shape
+    amax = ops.new_amax(t.P.device) if fmt.magnitude else None
+    a = torch.empty((B, conv.out_channels, H, W), dtype=torch.float32, device=t.P.device) if u.keep_fp32 else None
+    aP = fmt.act(t.P, _wq(fmt, conv), conv.out_channels, save, a=a, **_slot_kw(fmt, t, aP_slots=scale, a_amax=amax))
     if aP is None:
-        raise RuntimeError("onet_amd: the fused eval kernel refused a shape ops.eval_layer_ok accepted")
+        raise RuntimeError(f"onet_amd: the fused eval kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
     return _T(aP, a, scale, amax)
 
 
-def _plain_conv(conv, t):
-    if t.P.shape[3] == 1:
-        return ops.conv3x3_split_pre(t.P, _wq(conv, 1), conv.out_channels)
-    s1, s2, ch = ops._slots3(t.scale)
-    return ops.conv3x3_split_pre(t.P, _wq(conv), conv.out_channels, slots=s1, slots2=s2, split_ch=ch)
+def _plain_conv(fmt, conv, t):
+    return ops.conv3x3_split_pre(t.P, _wq(fmt, conv), conv.out_channels, **_slot_kw(fmt, t))
 
 
-def _pooled_unit(conv, bn, t, skipP, want_L, pooled_slots):
+def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots):
     """An encoder block's second unit: plain convolution, then ONE BatchNorm + ReLU + 2 x 2 max-pooling pass that writes the skip slots
     into the concat buffer, the pooled tensor (slots, or fp32 for a fall-back level) and -- level 0 -- the fp32 tensor the caller
     receives.  -> (skip, pooled, L | None)"""
-    save = _coeffs(bn)
-    parts = t.P.shape[3]
-    scale = _bound(conv, save, t) if parts == 2 else None
-    z = _plain_conv(conv, t)
+    save = _coeffs(u.bn)
+    scale = _bound(fmt, u.conv, save, t)
+    z = _plain_conv(fmt, u.conv, t)
     B, C, H, W = z.shape
     L = torch.empty_like(z) if want_L else None
-    yP = ops.p16_empty(B, C, H // 2, W // 2, z.device, parts=parts) if pooled_slots else None
+    yP = ops.p16_empty(B, C, H // 2, W // 2, z.device, parts=fmt.parts) if pooled_slots else None
     yF = None if pooled_slots else torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=z.device)
     if not ops.bn_relu_apply_pool_split(z, save, skipP, L, yP, yF, slots=scale):
         raise RuntimeError("onet_amd: the BatchNorm + pooling pass refused a shape ops.eval_layer_ok accepted")
-    if yF is not None and scale is not None:
+    if yF is not None and fmt.magnitude:
         ops.tag_amax(yF, scale)           # (max-pooling keeps the bound: the in-staging kernel below takes it as its range guard)
     return _T(skipP, None, scale, scale), _T(yP, yF, scale, scale), L
 
 
-def _conv_t(up, t, catP, C2):
-    """ConvTranspose2d(k=2, s=2) + bias into the up-sampled channel groups of the pre-split concat buffer -> their magnitude slots"""
+def _conv_t(fmt, up, t, catP, C2):
+    """ConvTranspose2d(k=2, s=2) + bias into the up-sampled channel groups of the pre-split concat buffer -> their magnitude slots
+    (None on a format without: the weight pack of that many parts, no slots on either side)"""
     Ct = up.out_channels
-    if catP.shape[3] == 1:            # plain bf16: the one-part weight pack, no magnitude slots on either side
-        dst = catP[:, C2 // 8:]
-        packed = up.packed()
-        if t.P is not None and ops.convT2x2_fwd_slots(t.P, packed.slots(1), up.bias, dst, Ct, kind="convt_slot_fwd_kernel"):
-            return None
-        if t.F is None:
-            raise RuntimeError("onet_amd: the slot-operand ConvTranspose2d refused a shape ops.convt_slots_ok accepted")
-        if not ops.convT2x2_fwd_p(t.F, packed[0], up.bias, dst, Ct, 0, 0):
-            raise RuntimeError("onet_amd: the ConvTranspose2d GEMM refused the fp32 input of a fused level")
-        return None
-    x_amax = t.amax if t.amax is not None else ops.absmax_slots(t.F)
-    s_up = ops.convT2x2_out_bound(up.weight, up.bias, x_amax)
+    s_up = None
+    if fmt.magnitude:
+        s_up = ops.convT2x2_out_bound(up.weight, up.bias, _amax(t))
     dst = catP[:, C2 // 8:]
     packed = up.packed()
-    if t.P is not None and ops.convT2x2_fwd_slots(t.P, packed.slots(2), up.bias, dst, Ct, x_slots=t.scale, slots=s_up,
+    if t.P is not None and ops.convT2x2_fwd_slots(t.P, packed.slots(fmt.parts), up.bias, dst, Ct, x_slots=t.scale, slots=s_up,
                                                    kind="convt_slot_fwd_kernel"):
         return s_up
     if t.F is None:
@@ -322,114 +397,103 @@ def _tail(unet, k, xk):
     return ups[k](_tail(unet, k + 1, downs[k](xk)), xk)
 
 
-def _head_unit(conv, bn, t, L):
+def _head_unit(fmt, u, t, L):
     """The last Conv-BatchNorm-ReLU unit with the head's channel product in the epilogue -> V [N, 1, H, W]"""
-    save = _coeffs(bn)
-    if t.P.shape[3] == 1:
-        V = ops.conv3x3_plain16_pre_head(t.P, _wq(conv, 1), conv.out_channels, save, L)
-    else:
-        s1, s2, ch = ops._slots3(t.scale)
-        V = ops.conv3x3_split_pre_head(t.P, _wq(conv), conv.out_channels, save, L, slots=s1, slots2=s2, split_ch=ch)
+    V = fmt.head(t.P, _wq(fmt, u.conv), u.conv.out_channels, _coeffs(u.bn), L, **_slot_kw(fmt, t))
     if V is None:
         raise RuntimeError("onet_amd: the fused head kernel refused a shape the plan accepted")
     return V
 
 
-def _unet_pass(unet, x, d, head=False):
-    """-> (L = inc's output fp32, z = the last unit's pre-activation, save = its coefficients): the head forms relu(bn(z)) on load.
-    head=True (labels-only calls; the caller has checked _head_ok): the last unit ends in the fused launch -> V [N, 1, H, W] =
-    sum_c L[c] relu(bn(z))[c]; z is never written and L is dropped with the pass."""
-    enc, downs, ups = _blocks(unet)
+def _unet_pass(plan, x):
+    """One pass as `plan` (_build_plan; its reason is None) says -> (L = inc's output fp32, z = the last unit's pre-activation, save =
+    its coefficients): the head forms relu(bn(z)) on load.
+    plan.head (labels-only calls): the last unit ends in the fused launch -> V [N, 1, H, W] = sum_c L[c] relu(bn(z))[c]; z is never
+    written and L is dropped with the pass."""
+    fmt, fused = plan.fmt, plan.levels[:plan.depth]
     N, _, H, W = x.shape
-    dev = x.device
-    # stem: the existing direct kernel, then one BatchNorm + ReLU pass that writes slots
-    c1, b1, c2, b2 = _units(enc[0])
-    P = _parts()
-    z0 = ops.conv3x3_auto(x, c1.packed(), 0)
-    save0 = _coeffs(b1)
-    scale0 = _bound(c1, save0, _T(None, x, None, ops.absmax_slots(x))) if P == 2 else None
-    a0 = ops.p16_empty(N, c1.out_channels, H, W, dev, parts=P)
-    ops.bn_relu_apply_split(z0, save0, a0, slots=scale0)
-    del z0
-    t = _note("inc.c1", _T(a0, None, scale0, scale0))
-    names, unames = ("inc", "down1", "down2", "down3", "down4"), ("up4", "up3", "up2", "up1")
     catP, skips, L = [None] * 4, [None] * 4, None
-    for k in range(d):
-        c1, b1, c2, b2 = _units(enc[k])
-        if k > 0:
-            t = _note(names[k] + ".c1", _fused_unit(c1, b1, t))
-        if k == 4:
-            up = ups[3].up
-            t = _note("down4.c2", _fused_unit(c2, b2, t, keep_fp32=not ops.convt_slots_ok(N, up.in_channels, up.out_channels, H >> 4, W >> 4, parts=P)))
-            break
-        C = c2.out_channels
-        catP[k] = ops.p16_empty(N, C + ups[k].up.out_channels, H >> k, W >> k, dev, parts=P)
-        skips[k], t, Lk = _pooled_unit(c2, b2, t, catP[k][:, :C // 8], k == 0, k + 1 < d)
-        _note(names[k] + ".c2", skips[k])
-        if P == 1 and t.P is not None:
-            _note(names[k] + ".pool", t)          # (the one-part plan's trace is complete: every convolution's exact input can be rebuilt)
-        if k == 0:
-            L = Lk
-    if d < 5:
+    for k, lv in enumerate(fused):
+        for u in lv.enc:
+            if u.kind == "stem":
+                t = _note(u.name, _stem_unit(fmt, u, x))
+            elif u.kind == "fused":
+                t = _note(u.name, _fused_unit(fmt, u, t))
+            else:
+                C = u.conv.out_channels
+                catP[k] = ops.p16_empty(N, C + lv.up.out_channels, H >> k, W >> k, x.device, parts=fmt.parts)
+                skips[k], t, Lk = _pooled_unit(fmt, u, t, catP[k][:, :C // 8], k == 0, lv.pooled_slots)
+                _note(u.name, skips[k])
+                if fmt.trace_pool and lv.pooled_slots:
+                    _note(_ENC[k] + ".pool", t)
+                if k == 0:
+                    L = Lk
+    if plan.depth < 5:
         # the levels below: existing eval kernels on fp32 tensors, from the pooled tensor of level d - 1
-        t = _T(None, _tail(unet, d, enc[d](t.F)), None, None)
-        t.amax = ops.amax_of(t.F) if P == 2 else None
+        t = _T(None, _tail(plan.unet, plan.depth, _blocks(plan.unet)[0][plan.depth](t.F)), None, None)
+        t.amax = ops.amax_of(t.F) if fmt.magnitude else None
     z = save = None
-    for k in range(min(d, 4) - 1, -1, -1):
-        C = _units(enc[k])[2].out_channels
-        s_up = _conv_t(ups[k].up, t, catP[k], C)
-        cat = _T(catP[k], None, (skips[k].scale, s_up, C), (skips[k].amax, s_up, C)) if P == 2 else _T(catP[k])
-        c1, b1, c2, b2 = _units(ups[k].conv)
-        _note(unames[k] + ".up", _T(catP[k][:, C // 8:], None, s_up, s_up))
-        t = _note(unames[k] + ".c1", _fused_unit(c1, b1, cat))
+    for k in range(len(fused) - 1, -1, -1):
+        lv = fused[k]
+        if not lv.dec:
+            continue
+        u1, u2 = lv.dec
+        C = lv.enc[-1].conv.out_channels
+        s_up = _conv_t(fmt, lv.up, t, catP[k], C)
+        cat = _T(catP[k], None, (skips[k].scale, s_up, C), (skips[k].amax, s_up, C)) if fmt.magnitude else _T(catP[k])
+        _note(_DEC[k] + ".up", _T(catP[k][:, C // 8:], None, s_up, s_up))
+        t = _note(u1.name, _fused_unit(fmt, u1, cat))
         catP[k] = None
-        if k > 0:
-            up = ups[k - 1].up
-            t = _note(unames[k] + ".c2", _fused_unit(c2, b2, t, keep_fp32=not ops.convt_slots_ok(N, up.in_channels, up.out_channels, H >> k, W >> k, parts=P)))
-        elif head:
-            return _head_unit(c2, b2, t, L)
+        if u2.kind == "fused":
+            t = _note(u2.name, _fused_unit(fmt, u2, t))
+        elif u2.kind == "fused+head":
+            return _head_unit(fmt, u2, t, L)
         else:
-            z, save = _plain_conv(c2, t), _coeffs(b2)
+            z, save = _plain_conv(fmt, u2.conv, t), _coeffs(u2.bn)
     return L, z, save
+
+
+def _run(passes, twin, X, bias=None):
+    """The passes of a gated call (_gate, _runs) -> [_unet_pass's result per pass].  bias None: a U-Net alone, one pass over X; an Onet:
+    one pass over the twin batch [X ; clip(1 - X + bias)] (shared weights: in eval both halves take the same coefficients), or one
+    over X and one over the complement."""
+    X = X.contiguous()
+    ops.amax_arena_reset(X.device)
+    if bias is None:
+        return [_unet_pass(passes[0][1], X)]
+    if twin:
+        return [_unet_pass(passes[0][1], ops.twin_materialize(src=(X, bias)))]
+    first = _unet_pass(passes[0][1], X)
+    return [first, _unet_pass(passes[-1][1], ops.complement_clip(X, bias))]
 
 
 def unet_forward(unet, x):
     """UNet.forward's (x1, y1) by the fused plan, or None where the plan does not apply (the caller runs the existing path)."""
-    if not (ops.fused_eval() and not torch.is_grad_enabled() and _input_ok(x)) or _static_reason(unet) is not None:
+    passes, twin = _gate(unet, None, x=x)
+    if not _runs(passes):
         return None
-    if x.shape[1] != unet.inc.double_conv[0].in_channels:
-        return None
-    d, _ = _depth(unet, x.shape[0], x.shape[2], x.shape[3])
-    if d == 0:
-        return None
-    x = x.contiguous()
-    ops.amax_arena_reset(x.device)
-    L, z, save = _unet_pass(unet, x, d)
+    (L, z, save), = _run(passes, twin, x)
     return L, ops.bn_relu_apply(z, save)
+
+
+def _onet_halves(onet, X, head, cut):
+    """-> [_unet_pass's result for X, for its complement] by the fused plan (head = "fused": the one that ends in the head-epilogue
+    launch), or None where it does not apply.  cut(result, slice): a batch slice of a result, for the halves of the twin batch.
+    Called with the model's settings active."""
+    passes, twin = _gate(onet, None, head, x=X)
+    if not _runs(passes) or (head == "fused" and not passes[0][1].head):
+        return None
+    res = _run(passes, twin, X, float(onet.bias))
+    B = X.shape[0]
+    return [cut(res[0], slice(0, B)), cut(res[0], slice(B, 2 * B))] if twin else res
 
 
 def onet_forward(onet, X):
     """Onet.forward's (Lt, Vt, Ld, Vd, S) by the fused plan, or None where it does not apply.  Called with the model's settings active."""
-    if not (ops.fused_eval() and not onet.training and not torch.is_grad_enabled() and _input_ok(X)):
+    res = _onet_halves(onet, X, None, lambda r, s: (r[0][s], r[1][s], r[2]))
+    if res is None:
         return None
-    shared = onet.dwnu is onet.topu
-    twin = shared and ops.twin_enabled()
-    B, C, H, W = X.shape
-    N = 2 * B if twin else B
-    for u in ((onet.topu,) if shared else (onet.topu, onet.dwnu)):
-        if _static_reason(u) is not None or C != u.inc.double_conv[0].in_channels or _depth(u, N, H, W)[0] == 0:
-            return None
-    X = X.contiguous()
-    ops.amax_arena_reset(X.device)
-    if twin:
-        # shared weights: [X ; clip(1 - X + bias)] as one batch of 2B -- in eval both halves take the same coefficients
-        XX = ops.twin_materialize(src=(X, float(onet.bias)))
-        L, z, save = _unet_pass(onet.topu, XX, _depth(onet.topu, N, H, W)[0])
-        Vt, Vd, S = ops.head_softmax_fwd(L[:B], z[:B], L[B:], z[B:], h_norm=(save, save))
-        return L[:B], Vt, L[B:], Vd, S
-    Lt, zt, st = _unet_pass(onet.topu, X, _depth(onet.topu, N, H, W)[0])
-    Xd = ops.complement_clip(X, float(onet.bias))
-    Ld, zd, sd = _unet_pass(onet.dwnu, Xd, _depth(onet.dwnu, N, H, W)[0])
+    (Lt, zt, st), (Ld, zd, sd) = res
     Vt, Vd, S = ops.head_softmax_fwd(Lt, zt, Ld, zd, h_norm=(st, sd))
     return Lt, Vt, Ld, Vd, S
 
@@ -437,25 +501,7 @@ def onet_forward(onet, X):
 def _head_scores(onet, X):
     """(Vt, Vd) [B, 1, H, W] by the fused plan ending in the head-epilogue launch, or None where that does not apply (the caller runs
     the ordinary forward).  Called with the model's settings active, under no_grad."""
-    if not (ops.fused_eval() and not onet.training and not torch.is_grad_enabled() and _input_ok(X)):
-        return None
-    shared = onet.dwnu is onet.topu
-    twin = shared and ops.twin_enabled()
-    B, C, H, W = X.shape
-    N = 2 * B if twin else B
-    for u in ((onet.topu,) if shared else (onet.topu, onet.dwnu)):
-        if _static_reason(u) is not None or C != u.inc.double_conv[0].in_channels or _depth(u, N, H, W)[0] == 0 or not _head_ok(u):
-            return None
-    X = X.contiguous()
-    ops.amax_arena_reset(X.device)
-    if twin:
-        XX = ops.twin_materialize(src=(X, float(onet.bias)))
-        V = _unet_pass(onet.topu, XX, _depth(onet.topu, N, H, W)[0], head=True)
-        return V[:B], V[B:]
-    Vt = _unet_pass(onet.topu, X, _depth(onet.topu, N, H, W)[0], head=True)
-    Xd = ops.complement_clip(X, float(onet.bias))
-    Vd = _unet_pass(onet.dwnu, Xd, _depth(onet.dwnu, N, H, W)[0], head=True)
-    return Vt, Vd
+    return _onet_halves(onet, X, "fused", lambda V, s: V[s])
 
 
 def scores(onet, X):
@@ -479,8 +525,7 @@ def segment(onet, X, head=None):
     and the model qualifies), without keeping the five outputs alive.
     head = "fused": the labels of scores(onet, X) -- the last convolution with the head in its epilogue, then one streaming launch that
     writes the labels alone: neither the last pre-activation nor S is materialised.  Where that plan does not apply: as head=None."""
-    if head not in (None, "fused"):
-        raise ValueError(f"onet_amd.segment: head must be None or 'fused', not {head!r}")
+    _check_head(head)
     with torch.no_grad():
         if head == "fused":
             with ops.using(onet.settings):

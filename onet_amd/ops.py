@@ -1220,6 +1220,23 @@ def eval_layer_ok_bf16(B, Cin, Cout, H, W):
     return B * (H // 16) * (W // 32) * (Cout // 64) >= (n_cu() * 3) // 4
 
 
+def _pre_act(entry, kind, two, cin_mult, xs, wq, Cout, save, out, a_amax, a, extra_in, extra_out):
+    B, C8, H, _, W, _ = xs.shape
+    Cin = C8 * 8
+    if W < 32 or W % 32 or H % 16 or Cin % cin_mult or Cout % 64:
+        return None
+    if out is None:
+        out = p16_empty(B, Cout, H, W, xs.device, parts=two)
+    e0 = _prof_begin(kind)
+    rc = getattr(_lib.load(), entry)(_p(xs), _pbs(xs), *extra_in, _p(wq), _p(save), _p(out), _pbs(out), *extra_out, _p(a_amax), _p(a),
+                                     0 if a is None else (a.stride(0) if B > 1 else Cout * H * W), B, Cin, Cout, H, W, _stream())
+    _prof_end(kind, 2.0 * B * H * W * Cin * Cout * 9 if rc == 0 else 0.0, e0,
+              (B * H * W * (2.0 * two * Cin + (2.0 * two + 4.0 * (a is not None)) * Cout) + 2.0 * two * 9 * Cin * Cout) if rc == 0 else 0.0)
+    if rc < 0:
+        raise _lib.OnetHipError(f"{entry} failed ({rc}): {_lib.last_error()}")
+    return out if rc == 0 else None
+
+
 def conv3x3_plain16_pre_act(xs, wq, Cout, save, out=None, a_amax=None, a=None):
     """aP = relu(bn(conv3x3(xs))) on PLAIN bf16 operands (xs [B, Cin/8, H, 1, W, 8] bf16, wq the plain16 forward pack), written as one
     part of bf16 slots, BatchNorm with the fixed coefficients `save` [4, Cout] (bn_eval_coeffs) in the convolution's epilogue:
@@ -1228,20 +1245,7 @@ def conv3x3_plain16_pre_act(xs, wq, Cout, save, out=None, a_amax=None, a=None):
     (nothing launched)."""
     if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
         raise TypeError("conv3x3_plain16_pre_act: xs and wq must be one-part bf16 packs on the GPU")
-    B, C8, H, _, W, _ = xs.shape
-    Cin = C8 * 8
-    if W < 32 or W % 32 or H % 16 or Cin % 32 or Cout % 64:
-        return None
-    if out is None:
-        out = p16_empty(B, Cout, H, W, xs.device, parts=1)
-    e0 = _prof_begin("conv3x3_pre16_act_kernel")
-    rc = _lib.load().onet_conv3x3_plain16_fwd_pre_act(_p(xs), _pbs(xs), _p(wq), _p(save), _p(out), _pbs(out), _p(a_amax), _p(a),
-                                                      0 if a is None else (a.stride(0) if B > 1 else Cout * H * W), B, Cin, Cout, H, W, _stream())
-    _prof_end("conv3x3_pre16_act_kernel", 2.0 * B * H * W * Cin * Cout * 9 if rc == 0 else 0.0, e0,
-              (B * H * W * (2.0 * Cin + (2.0 + 4.0 * (a is not None)) * Cout) + 2.0 * 9 * Cin * Cout) if rc == 0 else 0.0)
-    if rc < 0:
-        raise _lib.OnetHipError(f"onet_conv3x3_plain16_fwd_pre_act failed ({rc}): {_lib.last_error()}")
-    return out if rc == 0 else None
+    return _pre_act("onet_conv3x3_plain16_fwd_pre_act", "conv3x3_pre16_act_kernel", 1, 32, xs, wq, Cout, save, out, a_amax, a, (), ())
 
 
 def conv3x3_act_bound(weight, save, x_amax, x_amax2=None, split_ch=0):
@@ -1262,21 +1266,8 @@ def conv3x3_split_pre_act(xs, wq, Cout, save, aP_slots, out=None, slots=None, sl
     a: optional fp32 destination.  -> aP, or None where the kernel does not take the shape (nothing launched)."""
     if wq is None or not wq.is_cuda or wq.dtype != torch.float16 or xs.dtype != torch.float16 or xs.shape[3] != 2:
         raise TypeError("conv3x3_split_pre_act: xs and wq must be fp16 (hi | mid) split packs on the GPU")
-    B, C8, H, _, W, _ = xs.shape
-    Cin = C8 * 8
-    if W < 32 or W % 32 or H % 16 or Cin % 16 or Cout % 64:
-        return None
-    if out is None:
-        out = p16_empty(B, Cout, H, W, xs.device, parts=2)
-    e0 = _prof_begin("conv3x3_split_pre_act_kernel")
-    rc = _lib.load().onet_conv3x3_split_fwd_pre_act(_p(xs), _pbs(xs), _p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0),
-                                                    _p(wq), _p(save), _p(out), _pbs(out), _p(aP_slots), _p(a_amax), _p(a),
-                                                    0 if a is None else (a.stride(0) if B > 1 else Cout * H * W), B, Cin, Cout, H, W, _stream())
-    _prof_end("conv3x3_split_pre_act_kernel", 2.0 * B * H * W * Cin * Cout * 9 if rc == 0 else 0.0, e0,
-              (B * H * W * (4.0 * Cin + (4.0 + 4.0 * (a is not None)) * Cout) + 4.0 * 9 * Cin * Cout) if rc == 0 else 0.0)
-    if rc < 0:
-        raise _lib.OnetHipError(f"onet_conv3x3_split_fwd_pre_act failed ({rc}): {_lib.last_error()}")
-    return out if rc == 0 else None
+    return _pre_act("onet_conv3x3_split_fwd_pre_act", "conv3x3_split_pre_act_kernel", 2, 16, xs, wq, Cout, save, out, a_amax, a,
+                    (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)), (_p(aP_slots),))
 
 
 def _pre_head(entry, kind, two, xs, wq, Cout, save, L, out, extra):

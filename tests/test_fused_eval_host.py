@@ -76,3 +76,29 @@ def test_plan_on_cpu_model_reports_the_reason_without_a_device():
         assert "GPU" in str(e)
     else:
         raise AssertionError("a CPU forward did not raise")
+
+
+def test_plan_query_table_matches_the_recorded_one():
+    """inference.unet_plan over settings x shapes x heads on CPU models, compute units stubbed to 256 (tests/golden/make_plan_table.py):
+    every dictionary -- keys, values, reason strings, key order -- equals the recorded table."""
+    import importlib.util
+    import json
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_plan_table.py")
+    spec = importlib.util.spec_from_file_location("make_plan_table", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    with open(mod.PATH) as f:
+        want = json.load(f)
+    got = mod.table()
+    assert list(got) == list(want)
+    depths, convt, kinds = set(), set(), set()
+    for key, plan in want.items():
+        assert got[key] == plan, (key, got[key], plan)
+        assert list(got[key]) == list(plan) and list(got[key]["layers"]) == list(plan["layers"]) and \
+            list(got[key]["convt"]) == list(plan["convt"]), key
+        depths.add(plan["depth"])
+        convt.update(plan["convt"].values())
+        kinds.update(plan["layers"].values())
+    # the table covers what it is there to pin
+    assert depths == {0, 1, 2, 3, 4, 5} and convt == {"slots", "fp32->slots", "fallback"}, (depths, convt)
+    assert kinds == {"stem", "fused", "two-pass", "plain+head", "fused+head", "fallback"}, kinds

@@ -531,3 +531,66 @@ def test_f7_default_settings_keep_the_eval_path(dev):
     # 32- and 16-pixel levels on the direct kernel (11), the 256- and 128-pixel levels on the in-staging split kernel (7), the four
     # ConvTranspose2d GEMMs -- and nothing else
     assert ka == {"conv_fwd_kernel": 11, "conv3x3_split_kernel": 7, "convt_gemm_kernel": 4}, ka
+
+
+def _slot_writers(plan):
+    """The names inference.TRACE must list for one pass, in execution order, from the plan dictionary alone: going down, every unit of a
+    fused level that writes slots (on the one-part plan also `<block>.pool` where the pooled tensor leaves as slots, i.e. where the
+    next level is fused); coming back up, deepest fused Up block first, the ConvTranspose2d's channel groups, c1, and c2 where it is a
+    fused launch (the last unit writes no slots)."""
+    layers, convt = plan["layers"], plan["convt"]
+    enc = [n for n in layers if n.split(".")[0] not in convt]
+    names = []
+    for i, n in enumerate(enc):
+        if layers[n] == "fallback":
+            break
+        names.append(n)
+        if layers[n] == "two-pass" and plan["operands"] == "bf16" and i + 1 < len(enc) and layers[enc[i + 1]] != "fallback":
+            names.append(n.split(".")[0] + ".pool")
+    for u in reversed([u for u, kind in convt.items() if kind != "fallback"]):
+        names += [u + ".up", u + ".c1"] + ([u + ".c2"] if layers[u + ".c2"] == "fused" else [])
+    return names
+
+
+@pytest.mark.parametrize("conv,fused_eval", [("split", True), ("bf16", "bf16"), (None, True)])
+def test_f9_trace_and_launches_follow_the_plan_dictionary(dev, conv, fused_eval):
+    """The executor does what the query announces, on the smallest input whose level-4 map is one full 16 x 32 tile (B = 1, 1 x 256 x
+    512, shared: a twin batch of 2): conv = "split" / "bf16" fuse every level with every ConvTranspose2d on slot operands on a
+    256-compute-unit device, the default dispatch leaves a fall-back tail.  Every expected value comes from the dictionary:
+    inference.TRACE lists, per pass and in order, the slot-writing units the dictionary lists; the launch records of m(X) and of
+    segment(m, X, head="fused") match it (_assert_plan_matches' rule on either format's kinds), with exactly one head-epilogue launch
+    per pass and no plain launch for the last unit where it says "fused+head"."""
+    import onet_amd
+    from onet_amd import inference, ops
+    m = _onet(_prefixed(orc.det_state_dict(1, 1981)), 1, True, dev)
+    m.settings = ops.Settings(fused_eval=fused_eval) if conv is None else ops.Settings(conv=conv, fused_eval=fused_eval)
+    X = orc.det_input(1, 1, 256, 512, seed=131).to(dev)
+    act, head_kind = {"fp16x2": ("conv3x3_split_pre_act_kernel", "conv3x3_split_pre_head_kernel"),
+                      "bf16": ("conv3x3_pre16_act_kernel", "conv3x3_pre16_head_kernel")}[onet_amd.fused_eval_plan(m, X.shape)["operands"]]
+    for head in (None, "fused"):
+        plan = onet_amd.fused_eval_plan(m, X.shape, head=head)
+        assert plan["fused"] and plan["depth"] >= 1, plan
+        passes = 1 if plan["twin"] else 2
+        n = {k: sum(1 for v in plan["layers"].values() if v == k) for k in ("fused", "two-pass", "plain+head", "fused+head")}
+        assert n["plain+head"] + n["fused+head"] == 1 and (n["fused+head"] == 1) == (head == "fused"), plan
+        inference.TRACE = []
+        ops.profile_start(everything=False)
+        try:
+            with torch.no_grad():
+                if head is None:
+                    m(X)
+                else:
+                    onet_amd.segment(m, X, head="fused")
+            torch.cuda.synchronize()
+            traced = [name for name, _ in inference.TRACE]
+        finally:
+            kinds = {k: len(v) for k, v in ops.profile_stop()[0].items()}
+            inference.TRACE = None
+        what = (conv, fused_eval, head, plan["depth"])
+        assert traced == _slot_writers(plan) * passes, (what, traced, _slot_writers(plan))
+        assert kinds.get(act, 0) == passes * n["fused"], (what, kinds, plan)
+        assert kinds.get("conv3x3_split_pre_kernel", 0) == passes * (n["two-pass"] + n["plain+head"]), (what, kinds, plan)
+        assert kinds.get("convt_slot_fwd_kernel", 0) == passes * sum(1 for v in plan["convt"].values() if v == "slots"), (what, kinds, plan)
+        assert kinds.get(head_kind, 0) == passes * n["fused+head"], (what, kinds, plan)
+        other = {"conv3x3_split_pre_act_kernel", "conv3x3_pre16_act_kernel", "conv3x3_split_pre_head_kernel", "conv3x3_pre16_head_kernel"}
+        assert not (other - {act, head_kind}) & set(kinds), (what, kinds)
