@@ -270,6 +270,22 @@ int onet_conv3x3_split_fwd_pre_head(const void* xs, int64_t xs_bs, const void* x
                                     const void* wq, const float* save, const float* L, int64_t L_bs, float* V, int B, int Cin, int Cout, int H,
                                     int W, void* stream);
 int onet_softmax2_labels(const float* Vt, const float* Vd, float* S, int64_t* Y, int B, int HW, void* stream);
+/* Round 11 -- eval-mode inference, the Conv-BatchNorm-ReLU unit in front of a 2 x 2 max-pool in ONE launch (Settings.fused_eval =
+ * "fp16x2+pool" | "bf16+pool").  The two _act entries of rounds 7 and 8 on the same operands, with everything they write written as they
+ * write it -- aP (the leading channel groups of a concat buffer: the skip connection), a (may be NULL), a_amax (may be NULL) -- and, from
+ * the same accumulators, the pooled tensor m = fmaxf over each 2 x 2 window of a: as slots yP [B][Cout/8][H/2][W/2][8] bf16 (_plain16_) or
+ * [B][Cout/8][H/2][2][W/2][8] fp16 parts of 2^k m with the k of aP (_split_), batch stride yP_bs in 4-byte units, 16-byte aligned; as
+ * fp32 y [B][Cout][H/2][W/2], batch stride y_bs (16-byte aligned, y_bs % 4 == 0); or both -- at least one, the other NULL.  Bit for bit
+ * what the plain launch (fp32 z) + onet_bn_relu_apply_pool_split write; z is never stored.  A 16 x 32 tile starts on even rows and
+ * columns and a wave owns two adjacent rows: no window leaves a wave.  The _act entries' domain (maps made of full 16 x 32 tiles,
+ * Cin % 32 == 0 / % 16 == 0, Cout % 64 == 0): returns 1 (nothing launched, nothing written) elsewhere. */
+int onet_conv3x3_plain16_fwd_pre_act_pool(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs, void* a_amax,
+                                          float* a, int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin, int Cout, int H,
+                                          int W, void* stream);
+int onet_conv3x3_split_fwd_pre_act_pool(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
+                                        const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
+                                        int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin, int Cout, int H, int W,
+                                        void* stream);
 /* Weight gradient (OV:47,51 backward) from pre-split x and dz (both in the slot layout, same 16-bit type): fragments by the gfx950
  * transposing LDS read, staging by LDS-DMA; the producers' power-of-two scales (x_amax: guard rule, dz_amax: always; NULL:
  * unscaled) are undone on the slabs; deterministic split-K through ws

@@ -647,7 +647,7 @@ struct SpPreArgs {
     // coefficients [G][4][Cout] (groups of rd_gimg images; 0: one group), rd_rec [tiles][Cout][4] receives (sum dy, 0, sum dy xhat, 0)
     // per tile (bn_relu_bwd_reduce_kernel's record format), rd_amax (may be NULL) the magnitude slots of da.
     const float* rd_z = nullptr;
-    int64_t rd_z_bs = 0;
+    union { int64_t rd_z_bs = 0; int64_t pl_y_bs; };
     const float* rd_save = nullptr;
     int rd_gimg = 0;
     float* rd_rec = nullptr;
@@ -675,9 +675,16 @@ struct SpPreArgs {
     // conv3x3_pre16_kernel<false, PM, false, false, false, HEAD = true> (labels-only inference, Cout == 64: one channel tile holds every
     // output channel of a pixel): the epilogue forms h = max(0, fma(z - mean, sc, sh)) with act_save as above and reduces it against
     // hd_L [B][Cout][H][W] fp32 (batch stride hd_L_bs) over the channels: hd_V [B][H][W] = sum_c L[c] h[c] is ALL the launch writes
-    const float* hd_L = nullptr;
-    int64_t hd_L_bs = 0;
-    float* hd_V = nullptr;
+    union { const float* hd_L = nullptr; void* pl_P; };
+    union { int64_t hd_L_bs = 0; int64_t pl_P_bs; };
+    union { float* hd_V = nullptr; float* pl_y; };
+    // POOL (on top of ACT: an encoder block's second unit, the one in front of a max-pool): besides every store of ACT the epilogue forms
+    // m = the maximum of each 2 x 2 window of a (fmaxf; a tile starts on even rows and columns and a wave owns two adjacent rows, so no
+    // window leaves a wave) and writes it as slots -- pl_P [B][Cout/8][H/2][parts][W/2][8], the parts of 2^k m with zP's k, batch stride
+    // pl_P_bs in 4-byte units -- and / or as fp32 NCHW -- pl_y [B][Cout][H/2][W/2], batch stride pl_y_bs: what
+    // bn_relu_apply_pool_split_kernel writes from a stored z, bit for bit.  The four fields share the storage of hd_L, hd_L_bs, hd_V and
+    // rd_z_bs above -- epilogues POOL excludes (HEAD, RD) -- so that the kernel-argument block, and with it the code of every other
+    // instance, keeps its size and layout
 };
 
 // PM: 0 = bf16 (hi | mid) parts, 1 = fp16 (hi | mid) parts -- three MFMAs per term on 16-channel chunks; 2 = PLAIN bf16 operands
@@ -698,10 +705,14 @@ template <bool W16> struct SpPreCfg {
     static constexpr int LAST_TAP = 4;                                  // the next chunk's DMA pieces go out during taps 0 .. LAST_TAP
     static_assert(CO_T == SpCfg::CO_T && ROWS == SpCfg::ROWS && TW == SpCfg::TW, "sp_tile: one tile shape for every kernel of the family");
 };
-template <bool ST, int PM, bool W16, bool ACT = false>
+template <int CTRL> __device__ __forceinline__ float dpp_max(float x) {     // max(x, x of the lane DPP control CTRL selects)
+    return fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false)));
+}
+template <bool ST, int PM, bool W16, bool ACT = false, bool POOL = false>
 __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void conv3x3_split_pre_kernel(SpPreArgs a) {
     constexpr bool F16 = PM == 1;
     static_assert(!ACT || (PM == 1 && !ST && !W16), "conv3x3_split_pre_kernel: the activation epilogue goes with the fp16 slot store");
+    static_assert(!POOL || ACT, "conv3x3_split_pre_kernel: the pooled stores ride on the activation epilogue");
     using C = SpPreCfg<W16>;
     constexpr int NT = C::NT, IN_COLS = C::IN_COLS, NWI = C::NWI, CO_T = C::CO_T, NPIXP = C::NPIXP, NB = C::NB;
     constexpr int BUF = C::BUF_SLOTS, W_PART = C::W_PART, IN_PART = C::IN_PART;
@@ -1058,6 +1069,53 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
                             }
                         }
                     }
+                if constexpr (POOL) {
+                    // 2 x 2 max-pooling of the activation tile (SpPreArgs::pl_*): the window of pooled pixel (y0 / 2 + wn, (x0 + l31) / 2)
+                    // is the lane's two rows n at its own pixel column and at the lane ^ 1 neighbour's -- an in-lane fmaxf, one quad-permute
+                    // DPP step, and both lanes of a pair hold the maximum.  The slot form is the full-resolution one (permlane32 swap: all
+                    // 8 channels of the pixel in one lane, the same 2^k); the even lanes store, 256 contiguous bytes per half-wave
+                    const int Hp = a.H >> 1, Wp = a.W >> 1, yp = (y0 >> 1) + wn, xp = (x0 + l31) >> 1;
+                    const bool pst = (l31 & 1) == 0 && yp < Hp && xp < Wp;
+                    u32x4s* const yP = reinterpret_cast<u32x4s*>(reinterpret_cast<unsigned*>(a.pl_P) + (int64_t)b * a.pl_P_bs);
+                    float* const yF = a.pl_y + (int64_t)b * a.pl_y_bs;
+#pragma unroll
+                    for (int m = 0; m < 2; ++m)
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) {
+                            float v[8];
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) {
+                                const float t0 = acc[m][0][8 * e + j], u0 = acc[m][1][8 * e + j];                 // group 2 e: rows 0, 1
+                                const float t1 = acc[m][0][8 * e + 4 + j], u1 = acc[m][1][8 * e + 4 + j];         // group 2 e + 1
+                                const float f0 = dpp_max<0xB1>(fmaxf(t0, u0)), f1 = dpp_max<0xB1>(fmaxf(t1, u1)); // quad_perm [1,0,3,2]
+                                if (a.pl_y && pst) {
+                                    const int co = co0 + m * 32 + 16 * e + 4 * kh + j;
+                                    yF[((int64_t)co * Hp + yp) * Wp + xp] = f0;
+                                    yF[((int64_t)(co + 8) * Hp + yp) * Wp + xp] = f1;
+                                }
+                                const unsigned d0 = __builtin_bit_cast(unsigned, f0);
+                                const unsigned d1 = __builtin_bit_cast(unsigned, f1);
+                                const auto sw = __builtin_amdgcn_permlane32_swap(d0, d1, false, false);
+                                const unsigned lo = sw[0], hi4 = sw[1];
+                                v[j] = __builtin_bit_cast(float, lo);
+                                v[4 + j] = __builtin_bit_cast(float, hi4);
+                            }
+                            u32x4s hi, mid;
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                unsigned hh, mm;
+                                split2h_s(v[2 * k], v[2 * k + 1], zs, hh, mm);
+                                hi[k] = hh;
+                                mid[k] = mm;
+                            }
+                            if (a.pl_P && pst) {
+                                const int c8 = ((co0 + m * 32) >> 3) + 2 * e + kh;
+                                u32x4s* d = yP + ((int64_t)(c8 * Hp + yp) * 2) * Wp + xp;
+                                d[0] = hi;
+                                d[Wp] = mid;
+                            }
+                        }
+                }
                 continue;
             }
         }
@@ -1109,9 +1167,31 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
 template <int CTRL> __device__ __forceinline__ float dpp_add(float x) {     // x + (x of the lane DPP control CTRL selects)
     return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
 }
-template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false>
+// The one-part bf16 slot form of conv3x3_pre16_kernel's accumulator layout: the eight lanes c8 = 0 .. 7 of a group hold 8 channels x 4
+// pixels of channel group A (d1: the lane's channel c8 of A at four pixels) and of group B (d2).  Three butterfly exchanges (lane ^ 1,
+// ^ 2, ^ 4) transpose them: afterwards lane c8 owns one whole 16-byte slot -- the 8 channels of group (c8 >> 2 ? B : A) at pixel c8 & 3.
+__device__ __forceinline__ u32x4s pre16_slot_transpose(const f32x4s& d1, const f32x4s& d2, int c8) {
+    const unsigned a0 = pack2bf(d1[0], d1[1]), a1 = pack2bf(d1[2], d1[3]);
+    const unsigned b0 = pack2bf(d2[0], d2[1]), b1 = pack2bf(d2[2], d2[3]);
+    const bool o1 = (c8 & 1) != 0, o2 = (c8 & 2) != 0, o4 = (c8 & 4) != 0;
+    // stage 1: (pixel pair of one channel) x 2 lanes -> (channel pair) of pixel (c8 & 1) [and + 2]
+    auto st1 = [&](unsigned x) {
+        const unsigned y = (unsigned)__shfl_xor((int)x, 1, 64);
+        return o1 ? ((y >> 16) | (x & 0xffff0000u)) : ((x & 0xffffu) | (y << 16));
+    };
+    const unsigned A0 = st1(a0), A1 = st1(a1), B0 = st1(b0), B1 = st1(b1);
+    // stage 2: -> the channel quad (c8 >> 2) of pixel c8 & 3: lanes with bit 1 clear keep pixel (c8 & 1), the others + 2
+    const unsigned ra = (unsigned)__shfl_xor((int)(o2 ? A0 : A1), 2, 64), rb = (unsigned)__shfl_xor((int)(o2 ? B0 : B1), 2, 64);
+    const unsigned ka = o2 ? A1 : A0, kb = o2 ? B1 : B0;
+    const unsigned Alo = o2 ? ra : ka, Ahi = o2 ? ka : ra, Blo = o2 ? rb : kb, Bhi = o2 ? kb : rb;
+    // stage 3: lanes with bit 2 clear collect group A (their quad = channels 0 .. 3, the partner's 4 .. 7), the others B
+    const unsigned r0 = (unsigned)__shfl_xor((int)(o4 ? Alo : Blo), 4, 64), r1 = (unsigned)__shfl_xor((int)(o4 ? Ahi : Bhi), 4, 64);
+    return o4 ? u32x4s{r0, r1, Blo, Bhi} : u32x4s{Alo, Ahi, r0, r1};
+}
+template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false, bool POOL = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     constexpr bool F16 = PM == 1;
+    static_assert(!POOL || ACT, "conv3x3_pre16_kernel: the pooled stores ride on the activation epilogue");
     static_assert(!ACT || (PM == 2 && !ST && !W16 && !RD), "conv3x3_pre16_kernel: the activation epilogue goes with the one-part bf16 slot store");
     static_assert(!HEAD || (PM != 0 && !ST && !W16 && !RD && !ACT), "conv3x3_pre16_kernel: the head epilogue replaces every store of a plain forward launch");
     using C = SpPreCfg<W16>;
@@ -1520,26 +1600,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
                             }
                         }
                         if (ACT || (a.zP && co0 >= a.zP_ch0)) {
-                            // Pre-split output, plain bf16 (SpPreArgs::zP, one part): the eight lanes c8 = 0 .. 7 of a (pixel quad, tile half)
-                            // hold 8 channels x 4 pixels of channel group A (d1: channels 16 ct + c8) and of group B (d2: + 8).  Three
-                            // butterfly exchanges (lane ^ 1, ^ 2, ^ 4) transpose them: afterwards lane c8 owns one whole slot -- the 8
-                            // channels of group (c8 >> 2 ? B : A) at pixel c8 & 3 of the quad.
-                            const unsigned a0 = pack2bf(d1[0], d1[1]), a1 = pack2bf(d1[2], d1[3]);
-                            const unsigned b0 = pack2bf(d2[0], d2[1]), b1 = pack2bf(d2[2], d2[3]);
-                            const bool o1 = (c8 & 1) != 0, o2 = (c8 & 2) != 0, o4 = (c8 & 4) != 0;
-                            // stage 1: (pixel pair of one channel) x 2 lanes -> (channel pair) of pixel (c8 & 1) [and + 2]
-                            auto st1 = [&](unsigned x) {
-                                const unsigned y = (unsigned)__shfl_xor((int)x, 1, 64);
-                                return o1 ? ((y >> 16) | (x & 0xffff0000u)) : ((x & 0xffffu) | (y << 16));
-                            };
-                            const unsigned A0 = st1(a0), A1 = st1(a1), B0 = st1(b0), B1 = st1(b1);
-                            // stage 2: -> the channel quad (c8 >> 2) of pixel c8 & 3: lanes with bit 1 clear keep pixel (c8 & 1), the others + 2
-                            const unsigned ra = (unsigned)__shfl_xor((int)(o2 ? A0 : A1), 2, 64), rb = (unsigned)__shfl_xor((int)(o2 ? B0 : B1), 2, 64);
-                            const unsigned ka = o2 ? A1 : A0, kb = o2 ? B1 : B0;
-                            const unsigned Alo = o2 ? ra : ka, Ahi = o2 ? ka : ra, Blo = o2 ? rb : kb, Bhi = o2 ? kb : rb;
-                            // stage 3: lanes with bit 2 clear collect group A (their quad = channels 0 .. 3, the partner's 4 .. 7), the others B
-                            const unsigned r0 = (unsigned)__shfl_xor((int)(o4 ? Alo : Blo), 4, 64), r1 = (unsigned)__shfl_xor((int)(o4 ? Ahi : Bhi), 4, 64);
-                            const u32x4s slot = o4 ? u32x4s{r0, r1, Blo, Bhi} : u32x4s{Alo, Ahi, r0, r1};
+                            // Pre-split output, plain bf16 (SpPreArgs::zP, one part): channel group A = d1 (channels 16 ct + c8), group B =
+                            // d2 (+ 8) through pre16_slot_transpose -- lane c8 then owns the slot of group (c8 >> 2 ? B : A) at pixel c8 & 3
+                            const bool o4 = (c8 & 4) != 0;
+                            const u32x4s slot = pre16_slot_transpose(d1, d2, c8);
                             const int xs = x0 + 16 * half + 4 * lq + (c8 & 3);
                             if (yo < a.H && xs < a.W) {
                                 const int g8 = ((co0 - a.zP_ch0) >> 3) + 2 * ct + (o4 ? 1 : 0);
@@ -1564,6 +1628,44 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
                             if (co + 8 < a.Cout) *reinterpret_cast<f32x4s*>(o + (int64_t)8 * HW) = d2;
                         }
                     }
+                }
+            }
+        }
+        if constexpr (POOL) {
+            // 2 x 2 max-pooling of the activation tile (SpPreArgs::pl_*).  The lane holds channel 16 ct + r16 at pixels 4 lq .. + 3 of both
+            // 16-pixel halves of its two rows: two windows per half, all in the lane -- pooled pixels 2 lq, 2 lq + 1 and 8 + 2 lq, 8 + 2 lq + 1
+            // of the tile's 16, row y0 / 2 + wn.  Slots: the butterfly of the full-resolution store with channel tiles 2 p and 2 p + 1 as
+            // its groups A and B -- lane c8 of a half (r16 >> 3: channels + 8) then owns all 8 channels of one pooled pixel, and two
+            // store instructions per wave and tile write whole 16-byte slots, 256 contiguous bytes per channel group
+            const int Hp = a.H >> 1, Wp = a.W >> 1, yp = (y0 >> 1) + wn, xp0 = (x0 >> 1) + 2 * lq;
+            f32x4s pm[4];
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch) {
+                    const f32x4s t = acc[ct][0][ch], u = acc[ct][1][ch];
+                    pm[ct][2 * ch] = fmaxf(fmaxf(t[0], t[1]), fmaxf(u[0], u[1]));
+                    pm[ct][2 * ch + 1] = fmaxf(fmaxf(t[2], t[3]), fmaxf(u[2], u[3]));
+                }
+            if (a.pl_y && yp < Hp && xp0 + 9 < Wp) {
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct) {
+                    const int co = co0 + ct * 16 + r16;
+                    float* o = a.pl_y + (int64_t)b * a.pl_y_bs + ((int64_t)co * Hp + yp) * Wp + xp0;
+                    if (co < a.Cout) {
+                        *reinterpret_cast<float2*>(o) = make_float2(pm[ct][0], pm[ct][1]);
+                        *reinterpret_cast<float2*>(o + 8) = make_float2(pm[ct][2], pm[ct][3]);
+                    }
+                }
+            }
+            if (a.pl_P) {
+                const int c8 = r16 & 7, xs = xp0 + (c8 & 2 ? 8 : 0) + (c8 & 1);
+                u32x4s* yP = reinterpret_cast<u32x4s*>(reinterpret_cast<unsigned*>(a.pl_P) + (int64_t)b * a.pl_P_bs);
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    const u32x4s slot = pre16_slot_transpose(pm[2 * p], pm[2 * p + 1], c8);
+                    const int g8 = (co0 >> 3) + 2 * (2 * p + (c8 >> 2)) + (r16 >> 3);
+                    if (yp < Hp && xs < Wp) yP[((int64_t)g8 * Hp + yp) * Wp + xs] = slot;
                 }
             }
         }
@@ -1643,7 +1745,7 @@ int sp_launch_persistent(void (*kern)(Args), PerDeviceOnce& once, int lds_bytes,
     return check_launch(name);
 }
 
-template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false>
+template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false, bool POOL = false>
 int launch_split_pre(SpPreArgs a, hipStream_t st) {
     using C = SpPreCfg<W16>;
     const int LDS_BYTES = C::LDS_BYTES + (ST ? C::NW * 64 * 2 * 4 : 0) + (ACT || HEAD ? 2 * 3 * 64 * 4 : 0);
@@ -1659,12 +1761,13 @@ int launch_split_pre(SpPreArgs a, hipStream_t st) {
     // level (that instance of the new kernel exceeds the register budget).  The head epilogue exists on the 16x16x32 kernel alone.
     constexpr bool P16 = RD || PM == 2 || (ST && !W16) || HEAD;
     void (*kern)(SpPreArgs);
-    if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD, ACT, HEAD>;      // (constexpr: the instances not dispatched are not built)
-    else kern = conv3x3_split_pre_kernel<ST, PM, W16, ACT>;
+    if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD, ACT, HEAD, POOL>;      // (constexpr: the instances not dispatched are not built)
+    else kern = conv3x3_split_pre_kernel<ST, PM, W16, ACT, POOL>;
     static PerDeviceOnce attr_once;
     return sp_launch_persistent(kern, attr_once, LDS_BYTES, tiles, C::NW * 64,
-                                HEAD  ? (PM == 2 ? "conv3x3_pre16_head_kernel" : "conv3x3_split_pre_head_kernel")
-                                : ACT ? (PM == 2 ? "conv3x3_pre16_act_kernel" : "conv3x3_split_pre_act_kernel")
+                                HEAD   ? (PM == 2 ? "conv3x3_pre16_head_kernel" : "conv3x3_split_pre_head_kernel")
+                                : POOL ? (PM == 2 ? "conv3x3_pre16_act_pool_kernel" : "conv3x3_split_pre_act_pool_kernel")
+                                : ACT  ? (PM == 2 ? "conv3x3_pre16_act_kernel" : "conv3x3_split_pre_act_kernel")
                                       : "conv3x3_split_pre_kernel", a, st);
 }
 
@@ -2636,6 +2739,60 @@ int onet_conv3x3_plain16_fwd_pre_act(const void* xs, int64_t xs_bs, const void* 
     p.act_a = a;
     p.act_a_bs = a_bs;
     return launch_split_pre<false, 2, false, false, true>(p, as_stream(stream));
+}
+
+// Eval-mode inference, an encoder block's second unit: the _act entries above with the 2 x 2 max-pooling of the activation in the same
+// epilogue (SpPreArgs::pl_*).  Everything the _act entry writes is written as it writes it -- aP (the leading channel groups of a concat
+// buffer qualify), a, a_amax -- plus the pooled tensor m = max over each 2 x 2 window of relu(bn(z)): as slots yP [B][Cout/8][H/2][parts]
+// [W/2][8] (fp16: the parts of 2^k m with aP's k; plain bf16: one part, unscaled; batch stride yP_bs in 4-byte units), as fp32 y
+// [B][Cout][H/2][W/2] (batch stride y_bs), or both; at least one.  Bit for bit what the plain launch followed by
+// onet_bn_relu_apply_pool_split writes.  Returns 1 (nothing launched) outside the _act entry's domain.
+static int pre_act_pool_impl(const char* entry, int wq_f16, const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2,
+                             int split_ch, const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
+                             int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    ONET_REQUIRE(xs && wq && save && aP && (aP_slots || wq_f16 == 2), "%s: null pointer", entry);
+    ONET_REQUIRE(yP || y, "%s: a pooled destination is required (yP, y or both)", entry);
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
+    if (W < 32 || (W % 32) || (H % 16) || (Cin % (wq_f16 == 2 ? 32 : 16)) || (Cout % 64)) return 1;
+    ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
+    if (const int rc = pre_operand_checks(entry, xs, xs_bs, wq_f16, Cin, Cout, H, W)) return rc;
+    const int64_t n = (int64_t)Cout * H * W, per = wq_f16 == 2 ? 2 : 1;       // slot elements per 4-byte unit: one bf16 part / two fp16 parts
+    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0 && (!yP || ((yP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(yP) & 15) == 0)),
+                 "%s: 16-byte aligned slots required", entry);
+    ONET_REQUIRE((!a || ((a_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0)) && (!y || ((y_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0)),
+                 "%s: 16-byte aligned rows required", entry);
+    ONET_REQUIRE(aP_bs >= n / per && (!a || a_bs >= n) && (!yP || yP_bs >= n / 4 / per) && (!y || y_bs >= n / 4), "%s: batch stride too small", entry);
+    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)x_amax, scale_always,
+                (const unsigned*)x_amax2, split_ch};
+    p.zP = aP;
+    p.zP_bs = aP_bs;
+    p.zP_ch0 = 0;
+    p.zP_slots = (const unsigned*)aP_slots;
+    p.act_save = save;
+    p.act_amax = (unsigned*)a_amax;
+    p.act_a = a;
+    p.act_a_bs = a_bs;
+    p.pl_P = yP;
+    p.pl_P_bs = yP_bs;
+    p.pl_y = y;
+    p.pl_y_bs = y_bs;
+    if (wq_f16 == 2) return launch_split_pre<false, 2, false, false, true, false, true>(p, as_stream(stream));
+    return launch_split_pre<false, 1, false, false, true, false, true>(p, as_stream(stream));
+}
+
+int onet_conv3x3_plain16_fwd_pre_act_pool(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs, void* a_amax,
+                                          float* a, int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin, int Cout, int H,
+                                          int W, void* stream) {
+    return pre_act_pool_impl("conv3x3_plain16_fwd_pre_act_pool", 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, aP, aP_bs, nullptr, a_amax, a, a_bs,
+                             yP, yP_bs, y, y_bs, B, Cin, Cout, H, W, stream);
+}
+
+int onet_conv3x3_split_fwd_pre_act_pool(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
+                                        const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
+                                        int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin, int Cout, int H, int W,
+                                        void* stream) {
+    return pre_act_pool_impl("conv3x3_split_fwd_pre_act_pool", 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, aP, aP_bs, aP_slots,
+                             a_amax, a, a_bs, yP, yP_bs, y, y_bs, B, Cin, Cout, H, W, stream);
 }
 
 // Labels-only inference: the model's LAST unit with the head in the convolution's epilogue (SpPreArgs::hd_*).  The two entries below run

@@ -28,6 +28,12 @@ the unit's 64 channels, V the only store) followed by ops.softmax2_labels.  The 
 of the forward -- is never written, the head kernel does not run, and segment does not materialise S.  Onet.forward does not take this
 route: under every setting it launches what it launched before these calls existed.
 
+Settings.fused_eval = "fp16x2+pool" | "bf16+pool" (ops.fused_eval_pool()): the plan of True / "bf16" with each of the four units in front
+of a max-pool -- inc.c2, down1.c2, down2.c2, down3.c2: otherwise a plain convolution writing the fp32 pre-activation and one BatchNorm +
+ReLU + pooling pass reading it back -- as ONE launch (ops.conv3x3_*_pre_act_pool: skip slots, L at level 0 and the 2 x 2 maximum from the
+same accumulators).  Those units keep handing on their bound as scale AND amax, so every launch behind them sees the magnitude slots of
+the two-pass form and the whole forward is bit-identical to the plan without "+pool".
+
 Every decision about what runs where is taken once per U-Net pass, by _build_plan: the query (unet_plan, fused_eval_plan) prints its
 record, the executor (_unet_pass) follows it, and _gate is the one place that says whether the plan runs at all and on which passes.
 The slot format is chosen once per plan (_format); the units below take it from there."""
@@ -56,9 +62,10 @@ def _units(blk):
     return s[0], s[1], s[3], s[4]
 
 
-# The slot format of a plan: parts per slot, the weight pack, the layer predicate, the two launches, whether tensors carry magnitude
-# slots (without them: scale = amax = None everywhere, no bound launches) and whether the pooled tensors are traced
-_Format = namedtuple("_Format", "operands parts pack layer_ok act head magnitude trace_pool")
+# The slot format of a plan: parts per slot, the weight pack, the layer predicate, the three launches (act_pool: the unit in front of a
+# max-pool in one launch, taken where ops.fused_eval_pool() holds), whether tensors carry magnitude slots (without them: scale = amax =
+# None everywhere, no bound launches) and whether the pooled tensors are traced
+_Format = namedtuple("_Format", "operands parts pack layer_ok act act_pool head magnitude trace_pool")
 
 
 def _format():
@@ -66,8 +73,10 @@ def _format():
     name = ops.fused_eval_operands()
     if name == "bf16":
         # (trace_pool: the one-part plan's trace is complete -- every convolution's exact input can be rebuilt)
-        return _Format(name, 1, "plain16", ops.eval_layer_ok_bf16, ops.conv3x3_plain16_pre_act, ops.conv3x3_plain16_pre_head, False, True)
-    return _Format(name, 2, "split", ops.eval_layer_ok, ops.conv3x3_split_pre_act, ops.conv3x3_split_pre_head, True, False)
+        return _Format(name, 1, "plain16", ops.eval_layer_ok_bf16, ops.conv3x3_plain16_pre_act, ops.conv3x3_plain16_pre_act_pool,
+                       ops.conv3x3_plain16_pre_head, False, True)
+    return _Format(name, 2, "split", ops.eval_layer_ok, ops.conv3x3_split_pre_act, ops.conv3x3_split_pre_act_pool, ops.conv3x3_split_pre_head,
+                   True, False)
 
 
 def _static_reason(unet, fmt):
@@ -169,11 +178,13 @@ def _build_plan(unet, shape, head=None):
              "slots" if k + 1 < d and ops.convt_slots_ok(N, up.up.in_channels, up.up.out_channels, H >> (k + 1), W >> (k + 1), parts=fmt.parts) else
              "fp32->slots" for k, up in enumerate(ups)]
     with_head = head == "fused" and _head_ok(unet)
+    # pooled units: plain convolution + BatchNorm / ReLU / pooling pass writing slots, or -- "+pool" -- all of it in the convolution's launch
+    pooled_kind = "fused+pool" if ops.fused_eval_pool() else "two-pass"
     levels = []
     for k, (e, dec) in enumerate(units):
         kind = dict.fromkeys((name for name, _, _ in e + dec), "fused" if k < d else "fallback")
         if k < min(d, 4):
-            kind[e[-1][0]] = "two-pass"           # pooled units: plain convolution + BatchNorm / ReLU / pooling pass writing slots
+            kind[e[-1][0]] = pooled_kind
         if k == 0:
             e = [("inc.c1",) + _units(unet.inc)[:2]] + e
             kind["inc.c1"], kind[dec[-1][0]] = "stem", ("fused+head" if with_head else "plain+head")
@@ -212,8 +223,8 @@ def _plan_dict(plan):
 
 def unet_plan(unet, shape, device=None, head=None):
     """What the fused plan does with a U-Net pass over an input of `shape` = (N, C, H, W): a pure query, nothing is launched.
-    -> {"fused": bool, "reason": why not | None, "depth": d, "batch": N, "layers": {name: "stem" | "fused" | "two-pass" | "plain+head"
-    | "fused+head" | "fallback"}, "convt": {name: "slots" | "fp32->slots" | "fallback"}, "fallback_reason": why level d is not fused |
+    -> {"fused": bool, "reason": why not | None, "depth": d, "batch": N, "layers": {name: "stem" | "fused" | "two-pass" | "fused+pool" |
+    "plain+head" | "fused+head" | "fallback"}, "convt": {name: "slots" | "fp32->slots" | "fallback"}, "fallback_reason": why level d is not fused |
     None, "operands": the slot format the settings select, "fp16x2" | "bf16" (None: Settings.fused_eval is off)}
     head = "fused": the plan of the labels-only calls (scores, segment(head="fused")) -- "fused+head" where the last unit runs with the
     head in its epilogue; a last unit outside that kernel's domain (Cout != 64) sends those calls to the ordinary forward, whose plan
@@ -352,17 +363,22 @@ def _plain_conv(fmt, conv, t):
 
 
 def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots):
-    """An encoder block's second unit: plain convolution, then ONE BatchNorm + ReLU + 2 x 2 max-pooling pass that writes the skip slots
-    into the concat buffer, the pooled tensor (slots, or fp32 for a fall-back level) and -- level 0 -- the fp32 tensor the caller
-    receives.  -> (skip, pooled, L | None)"""
+    """An encoder block's second unit, which writes the skip slots into the concat buffer, the pooled tensor (slots, or fp32 for a
+    fall-back level) and -- level 0 -- the fp32 tensor the caller receives.  "two-pass": plain convolution, then ONE BatchNorm + ReLU +
+    2 x 2 max-pooling pass; "fused+pool": all of it in the convolution's launch, the same bits (no exact maximum is taken from it: the
+    unit hands on its bound either way, so every later launch sees the same magnitude slots).  -> (skip, pooled, L | None)"""
     save = _coeffs(u.bn)
     scale = _bound(fmt, u.conv, save, t)
-    z = _plain_conv(fmt, u.conv, t)
-    B, C, H, W = z.shape
-    L = torch.empty_like(z) if want_L else None
-    yP = ops.p16_empty(B, C, H // 2, W // 2, z.device, parts=fmt.parts) if pooled_slots else None
-    yF = None if pooled_slots else torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=z.device)
-    if not ops.bn_relu_apply_pool_split(z, save, skipP, L, yP, yF, slots=scale):
+    B, _, H, _, W, _ = t.P.shape
+    C, dev = u.conv.out_channels, t.P.device
+    z = None if u.kind == "fused+pool" else _plain_conv(fmt, u.conv, t)
+    L = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if want_L else None
+    yP = ops.p16_empty(B, C, H // 2, W // 2, dev, parts=fmt.parts) if pooled_slots else None
+    yF = None if pooled_slots else torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=dev)
+    if z is None:
+        if fmt.act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, aP_slots=scale)) is None:
+            raise RuntimeError(f"onet_amd: the fused pooling kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
+    elif not ops.bn_relu_apply_pool_split(z, save, skipP, L, yP, yF, slots=scale):
         raise RuntimeError("onet_amd: the BatchNorm + pooling pass refused a shape ops.eval_layer_ok accepted")
     if yF is not None and fmt.magnitude:
         ops.tag_amax(yF, scale)           # (max-pooling keeps the bound: the in-staging kernel below takes it as its range guard)

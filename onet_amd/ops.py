@@ -64,7 +64,9 @@ class Settings:
                     True: fp16 (hi | mid) slots, fp32-level results (needs the fp16-split convolution path: under conv == "bf16" the
                     forward falls back to the default path); "bf16": ONE part of plain bf16 per slot -- the arithmetic conv == "bf16"
                     trains with, a third of the matrix instructions and half the slot bytes -- under any conv with pre-split storage
-                    (fused_eval_operands())"""
+                    (fused_eval_operands()); "fp16x2+pool" / "bf16+pool": the plan of True / "bf16" with the four encoder units in front
+                    of a max-pool in ONE launch each, the pooling in the convolution's epilogue (fused_eval_pool()) -- the same bits.
+                    Any other string is a ValueError where the setting is read"""
     __slots__ = ("conv", "twin", "convt_bf16", "lazy_nan", "split", "bn_on_load", "split_f16", "grad_f16", "split_dgrad",
                  "stem_fused", "sync_bn", "presplit", "z_bf16", "fused_eval")
 
@@ -161,21 +163,37 @@ def presplit():
     return split_enabled() and conv_algo() in ("auto", "split") and split_f16() and split_dgrad()
 
 
-# 1: eval forwards under no_grad take the fused inference plan (Settings.fused_eval); bf16: its one-part plain-bf16 form
-FUSED_EVAL = "bf16" if _FLAGS.get("FUSED_EVAL") == "bf16" else _flag("FUSED_EVAL", False)
+# The string values of Settings.fused_eval -> (slot format, pooled units in one launch); True is ("fp16x2", False)
+_FUSED_EVAL_VALUES = {"bf16": ("bf16", False), "fp16x2+pool": ("fp16x2", True), "bf16+pool": ("bf16", True)}
+# 1: eval forwards under no_grad take the fused inference plan (Settings.fused_eval); bf16: its one-part plain-bf16 form; either with
+# "+pool" ("fp16x2+pool", "bf16+pool"): the pooled units in one launch
+FUSED_EVAL = _FLAGS["FUSED_EVAL"] if _FLAGS.get("FUSED_EVAL") in _FUSED_EVAL_VALUES else _flag("FUSED_EVAL", False)
+
+
+def _fused_eval_value():
+    """-> (slot format | None: off, pooled units in one launch) of the active Settings.fused_eval"""
+    v = _setting("fused_eval", FUSED_EVAL)
+    if isinstance(v, str):
+        if v not in _FUSED_EVAL_VALUES:
+            raise ValueError(f"onet_amd: Settings.fused_eval must be None, a bool or one of {sorted(_FUSED_EVAL_VALUES)}, not {v!r}")
+        return _FUSED_EVAL_VALUES[v]
+    return ("fp16x2" if v else None), False
 
 
 def fused_eval():
-    return bool(_setting("fused_eval", FUSED_EVAL))
+    return _fused_eval_value()[0] is not None
 
 
 def fused_eval_operands():
-    """The slot format of the fused eval plan: "fp16x2" (Settings.fused_eval = True: fp16 hi | mid parts), "bf16" (= "bf16": one part
-    of plain bf16), None (off)."""
-    v = _setting("fused_eval", FUSED_EVAL)
-    if not v:
-        return None
-    return "bf16" if v == "bf16" else "fp16x2"
+    """The slot format of the fused eval plan: "fp16x2" (Settings.fused_eval = True or "fp16x2+pool": fp16 hi | mid parts), "bf16"
+    (= "bf16" or "bf16+pool": one part of plain bf16), None (off)."""
+    return _fused_eval_value()[0]
+
+
+def fused_eval_pool():
+    """Does the fused eval plan run a unit in front of a max-pool as ONE launch, the pooling in the convolution's epilogue
+    (Settings.fused_eval = "fp16x2+pool" | "bf16+pool": conv3x3_*_pre_act_pool)?"""
+    return _fused_eval_value()[1]
 
 
 Z_BF16 = _flag("Z_BF16", True)       # BASELINE configs[2] (conv == "bf16", pre-split operands): conv outputs stored as bf16 (Settings.z_bf16)
@@ -1220,18 +1238,27 @@ def eval_layer_ok_bf16(B, Cin, Cout, H, W):
     return B * (H // 16) * (W // 32) * (Cout // 64) >= (n_cu() * 3) // 4
 
 
-def _pre_act(entry, kind, two, cin_mult, xs, wq, Cout, save, out, a_amax, a, extra_in, extra_out):
+def _pre_act(entry, kind, two, cin_mult, xs, wq, Cout, save, out, a_amax, a, extra_in, extra_out, pooled=None):
+    """pooled: (yP, y) of the _pool entries -- the pooled slots and / or the pooled fp32 tensor, at least one"""
     B, C8, H, _, W, _ = xs.shape
     Cin = C8 * 8
+    if pooled is not None and pooled[0] is None and pooled[1] is None:
+        raise ValueError(f"{entry[len('onet_'):]}: a pooled destination is required (yP, y or both)")
     if W < 32 or W % 32 or H % 16 or Cin % cin_mult or Cout % 64:
         return None
     if out is None:
         out = p16_empty(B, Cout, H, W, xs.device, parts=two)
+    n = Cout * H * W
+    pool_args, pool_bytes = (), 0.0
+    if pooled is not None:
+        yP, y = pooled
+        pool_args = (_p(yP), 0 if yP is None else _pbs(yP), _p(y), 0 if y is None else (y.stride(0) if B > 1 else n // 4))
+        pool_bytes = 0.25 * (2.0 * two * (yP is not None) + 4.0 * (y is not None)) * Cout      # per pixel: a quarter as many pooled ones
     e0 = _prof_begin(kind)
     rc = getattr(_lib.load(), entry)(_p(xs), _pbs(xs), *extra_in, _p(wq), _p(save), _p(out), _pbs(out), *extra_out, _p(a_amax), _p(a),
-                                     0 if a is None else (a.stride(0) if B > 1 else Cout * H * W), B, Cin, Cout, H, W, _stream())
+                                     0 if a is None else (a.stride(0) if B > 1 else n), *pool_args, B, Cin, Cout, H, W, _stream())
     _prof_end(kind, 2.0 * B * H * W * Cin * Cout * 9 if rc == 0 else 0.0, e0,
-              (B * H * W * (2.0 * two * Cin + (2.0 * two + 4.0 * (a is not None)) * Cout) + 2.0 * two * 9 * Cin * Cout) if rc == 0 else 0.0)
+              (B * H * W * (2.0 * two * Cin + (2.0 * two + 4.0 * (a is not None)) * Cout + pool_bytes) + 2.0 * two * 9 * Cin * Cout) if rc == 0 else 0.0)
     if rc < 0:
         raise _lib.OnetHipError(f"{entry} failed ({rc}): {_lib.last_error()}")
     return out if rc == 0 else None
@@ -1246,6 +1273,29 @@ def conv3x3_plain16_pre_act(xs, wq, Cout, save, out=None, a_amax=None, a=None):
     if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
         raise TypeError("conv3x3_plain16_pre_act: xs and wq must be one-part bf16 packs on the GPU")
     return _pre_act("onet_conv3x3_plain16_fwd_pre_act", "conv3x3_pre16_act_kernel", 1, 32, xs, wq, Cout, save, out, a_amax, a, (), ())
+
+
+def conv3x3_plain16_pre_act_pool(xs, wq, Cout, save, out=None, a_amax=None, a=None, yP=None, y=None):
+    """conv3x3_plain16_pre_act with the 2 x 2 max-pooling of the activation in the same epilogue: besides aP (`out`: the skip groups of a
+    concat buffer qualify), `a` and `a_amax` the launch writes the pooled tensor as one-part bf16 slots (yP [B, Cout/8, H/2, 1, W/2, 8]),
+    as fp32 (y [B, Cout, H/2, W/2]) or both -- at least one.  conv3x3_split_pre (fp32 z) followed by bn_relu_apply_pool_split, bit for
+    bit, without the tensor z.  -> aP, or None where the kernel does not take the shape (nothing launched)."""
+    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
+        raise TypeError("conv3x3_plain16_pre_act_pool: xs and wq must be one-part bf16 packs on the GPU")
+    return _pre_act("onet_conv3x3_plain16_fwd_pre_act_pool", "conv3x3_pre16_act_pool_kernel", 1, 32, xs, wq, Cout, save, out, a_amax, a, (), (),
+                    pooled=(yP, y))
+
+
+def conv3x3_split_pre_act_pool(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None, yP=None,
+                               y=None):
+    """conv3x3_split_pre_act with the 2 x 2 max-pooling of the activation in the same epilogue (conv3x3_plain16_pre_act_pool on fp16
+    hi | mid parts): the pooled slots yP [B, Cout/8, H/2, 2, W/2, 8] are parts of 2^k m with the k of aP (aP_slots).  conv3x3_split_pre
+    followed by bn_relu_apply_pool_split(.., slots=aP_slots), bit for bit.  -> aP, or None (nothing launched)."""
+    if wq is None or not wq.is_cuda or wq.dtype != torch.float16 or xs.dtype != torch.float16 or xs.shape[3] != 2:
+        raise TypeError("conv3x3_split_pre_act_pool: xs and wq must be fp16 (hi | mid) split packs on the GPU")
+    return _pre_act("onet_conv3x3_split_fwd_pre_act_pool", "conv3x3_split_pre_act_pool_kernel", 2, 16, xs, wq, Cout, save, out, a_amax, a,
+                    (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)), (_p(aP_slots),),
+                    pooled=(yP, y))
 
 
 def conv3x3_act_bound(weight, save, x_amax, x_amax2=None, split_ch=0):

@@ -8,11 +8,14 @@ bf16 slots, depth by the fill rule) and "bf16/bf16" (the same under conv == "bf1
 Labels-only paths time a call that returns the labels alone: "fused:segment" and "bf16/bf16:segment" are `segment(m, X)` under the
 settings of "fused" / "bf16/bf16", "fused+head" and "bf16/bf16+head" are `segment(m, X, head="fused")` under the same settings (the
 head in the last convolution's epilogue).
+"+pool" paths -- "fused+pool", "bf16+pool", "bf16/bf16+pool" and the labels-only "fused+pool+head", "bf16/bf16+pool+head" -- are the paths
+of the same name without it under fused_eval = "fp16x2+pool" / "bf16+pool": the four units in front of a max-pool in one launch each.
 Per shape: every path is warmed up, the number of calls that fills `--seconds` is measured, then `--rounds` interleaved rounds
 (default, fused, bf16, bf16/bf16, fused:segment, fused+head, ..., default, ...) of that many calls each are timed with device events
-under no_grad.  Reported: ms per call (median over rounds), images/s, the round-to-round spread (max - min over rounds) and
+under no_grad (the "+pool" paths ride in the same rounds, so each is interleaved with its own baseline).  Reported: ms per call (median over rounds), images/s, the round-to-round spread (max - min over rounds) and
 torch.cuda.max_memory_allocated of each path.  A verdict compares the difference of two medians with the SUM of the two spreads: every
-fused path against the default path, the one-part plans against the fp16 plan, and each +head path against segment() of its plan."""
+fused path against the default path, the one-part plans against the fp16 plan, each +head path against segment() of its plan, and each
+"+pool" path against the path without it."""
 import argparse
 import json
 import os
@@ -44,10 +47,15 @@ def _timed(m, X, n, call=None):
 def _settings():
     from onet_amd import ops
     return {"default": ops.Settings(), "fused": ops.Settings(fused_eval=True), "bf16": ops.Settings(fused_eval="bf16"),
-            "bf16/bf16": ops.Settings(conv="bf16", fused_eval="bf16")}
+            "bf16/bf16": ops.Settings(conv="bf16", fused_eval="bf16"), "fused+pool": ops.Settings(fused_eval="fp16x2+pool"),
+            "bf16+pool": ops.Settings(fused_eval="bf16+pool"), "bf16/bf16+pool": ops.Settings(conv="bf16", fused_eval="bf16+pool")}
 
 
-PATHS = ("default", "fused", "bf16", "bf16/bf16", "fused:segment", "fused+head", "bf16/bf16:segment", "bf16/bf16+head")
+PATHS = ("default", "fused", "bf16", "bf16/bf16", "fused+pool", "bf16+pool", "bf16/bf16+pool", "fused:segment", "fused+head",
+         "fused+pool+head", "bf16/bf16:segment", "bf16/bf16+head", "bf16/bf16+pool+head")
+# each "+pool" path and the path it is held against
+POOL_PAIRS = (("fused", "fused+pool"), ("bf16", "bf16+pool"), ("bf16/bf16", "bf16/bf16+pool"), ("fused+head", "fused+pool+head"),
+              ("bf16/bf16+head", "bf16/bf16+pool+head"))
 
 
 def _paths(m):
@@ -58,6 +66,7 @@ def _paths(m):
     for name in ("fused", "bf16/bf16"):
         out[name + ":segment"] = (sets[name], lambda X: onet_amd.segment(m, X))
         out[name + "+head"] = (sets[name], lambda X: onet_amd.segment(m, X, head="fused"))
+        out[name + "+pool+head"] = (sets[name + "+pool"], lambda X: onet_amd.segment(m, X, head="fused"))
     assert tuple(out) == PATHS
     return out
 
@@ -81,7 +90,8 @@ def time_shape(shape, rounds, seconds, dev):
             m.settings = st
             plan = onet_amd.fused_eval_plan(m, X.shape, head="fused" if name.endswith("+head") else None)
             res["plans"][name] = {"fused": plan["fused"], "depth": plan["depth"], "operands": plan["operands"], "reason": plan["reason"],
-                                  "last_unit": plan["layers"].get("up4.c2")}
+                                  "last_unit": plan["layers"].get("up4.c2"),
+                                  "pooled_units": sorted(k for k, v in plan["layers"].items() if v == "fused+pool")}
     res["plan_fused"], res["depth"], res["reason"] = (res["plans"]["fused"][k] for k in ("fused", "depth", "reason"))
     with torch.no_grad():
         n = {}
@@ -108,7 +118,7 @@ def time_shape(shape, rounds, seconds, dev):
     res["gain_ms"], res["noise_ms"], res["verdict"] = _verdict(res["default"], res["fused"])
     res["versus"] = {}
     for base, other in (("default", "fused"), ("default", "bf16"), ("default", "bf16/bf16"), ("fused", "bf16"), ("fused", "bf16/bf16"),
-                        ("fused:segment", "fused+head"), ("bf16/bf16:segment", "bf16/bf16+head")):
+                        ("fused:segment", "fused+head"), ("bf16/bf16:segment", "bf16/bf16+head")) + POOL_PAIRS:
         g, nz, v = _verdict(res[base], res[other])
         res["versus"][f"{other} vs {base}"] = {"gain_ms": g, "noise_ms": nz, "verdict": v}
     return res
@@ -142,7 +152,7 @@ def main():
         print("x".join(map(str, shape)), flush=True)
         for name in PATHS:
             p = r["plans"].get(name)
-            print("  %-17s %s %8.3f ms (%6.0f img/s, spread %.3f, %5.0f MiB)" % (
+            print("  %-19s %s %8.3f ms (%6.0f img/s, spread %.3f, %5.0f MiB)" % (
                 name, "depth %d" % p["depth"] if p else "       ", r[name]["ms"], r[name]["img_s"], r[name]["spread_ms"], r[name]["max_mem_MiB"]),
                 flush=True)
         for k, v in r["versus"].items():
