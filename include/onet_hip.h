@@ -368,7 +368,9 @@ int64_t onet_conv_wgrad_ws_bytes(int B, int Cin, int Cout, int H, int W, int ks)
 /* ---- K2/K3: BatchNorm2d (+ReLU) ---------------------------------------- */
 /* Welford partials of z per channel: part [nparts][C][3] = (n_k, mean_k, M2_k = sum (z-mean_k)^2)
  * over nparts = B*chunks slices of the B*HW values (standalone statistics pass; the conv epilogue
- * can emit the same records instead).  Robust where E[z^2]-mean^2 is not (tiny counts, |mean|>>std). */
+ * can emit the same records instead).  Robust where E[z^2]-mean^2 is not (tiny counts, |mean|>>std).
+ * A plane is cut into chunks = nparts / B pieces of ceil(HW / chunks) rounded up to a multiple of 4 elements; a plan whose last
+ * piece would be empty (HW = 9 in 4 pieces) is refused with ONET_EINVAL, here and in onet_bn_relu_bwd_reduce. */
 int onet_bn_stats_partial(const float* z, int64_t z_bs, float* part, int nparts,
                           int B, int C, int HW, void* stream);
 /* train-mode finalize (OV:48,52 -> F.batch_norm(training=True)):

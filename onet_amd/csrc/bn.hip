@@ -959,12 +959,16 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const float* __r
     amax_commit(vmax, amax);
 }
 
-// nparts must be B * chunks with chunks = ceil(HW / chunk_len); we derive chunk_len from nparts
+// nparts must be B * chunks with chunks = ceil(HW / chunk_len); we derive chunk_len from nparts.
+// Every chunk must own at least one element: with chunk_len rounded up to a multiple of 4 a small plane cut into many chunks leaves
+// the last ones empty (HW = 9 in 4 chunks: chunk_len 4, the fourth chunk begins at 12) -- the kernels would read the pivot past the
+// plane and write a record with a negative count.
 static bool split_plan(int nparts, int B, int HW, int& chunks, int& chunk_len) {
     if (nparts <= 0 || nparts % B) return false;
     chunks = nparts / B;
     chunk_len = (HW + chunks - 1) / chunks;
     chunk_len = (chunk_len + 3) & ~3;
+    if ((int64_t)(chunks - 1) * chunk_len >= HW) return false;
     return (int64_t)chunks * chunk_len >= HW;
 }
 
@@ -974,7 +978,7 @@ int onet_bn_stats_partial(const float* z, int64_t z_bs, float* part, int nparts,
                           void* stream) {
     ONET_REQUIRE(z && part && B > 0 && C > 0 && HW > 0, "bn_stats_partial: bad args");
     int chunks, chunk_len;
-    ONET_REQUIRE(split_plan(nparts, B, HW, chunks, chunk_len), "bn_stats_partial: nparts=%d must be a multiple of B=%d", nparts, B);
+    ONET_REQUIRE(split_plan(nparts, B, HW, chunks, chunk_len), "bn_stats_partial: nparts=%d must be a multiple of B=%d that leaves no chunk of HW=%d empty", nparts, B, HW);
     hipLaunchKernelGGL(bn_stats_partial_kernel, dim3((unsigned)((int64_t)nparts * C)), dim3(256), 0,
                        as_stream(stream), z, z_bs, part, C, HW, chunks, chunk_len);
     return check_launch("bn_stats_partial_kernel");
@@ -1039,7 +1043,7 @@ int onet_bn_relu_bwd_reduce(const float* da, int64_t da_bs, const void* z, int z
                                  int nparts, void* da_amax, int group_images, int B, int C, int HW, void* stream) {
     ONET_REQUIRE(da && z && save && part2 && B > 0 && C > 0 && HW > 0 && group_images >= 0, "bn_relu_bwd_reduce: bad args");
     int chunks, chunk_len;
-    ONET_REQUIRE(split_plan(nparts, B, HW, chunks, chunk_len), "bn_relu_bwd_reduce: nparts=%d must be a multiple of B=%d", nparts, B);
+    ONET_REQUIRE(split_plan(nparts, B, HW, chunks, chunk_len), "bn_relu_bwd_reduce: nparts=%d must be a multiple of B=%d that leaves no chunk of HW=%d empty", nparts, B, HW);
     const dim3 grid((unsigned)((int64_t)nparts * C));
     if (z_bf16) {
         ONET_REQUIRE((reinterpret_cast<uintptr_t>(z) & 7) == 0, "bn_relu_bwd_reduce: 8-byte aligned bf16 rows required");
@@ -1127,7 +1131,7 @@ int onet_head_bwd_reduce(const float* L, int64_t L_bs, const float* z, int64_t z
     ONET_REQUIRE((HW & 3) == 0 && (L_bs & 3) == 0 && (z_bs & 3) == 0 && al(L) && al(z) && al(g) && al(gsLt) && al(gsLd) && al(dL),
                  "head_bwd_reduce: HW %% 4 == 0 and 16-byte aligned rows required");
     int chunks, chunk_len;
-    ONET_REQUIRE(split_plan(nparts, B, HW, chunks, chunk_len), "head_bwd_reduce: nparts=%d must be a multiple of B=%d", nparts, B);
+    ONET_REQUIRE(split_plan(nparts, B, HW, chunks, chunk_len), "head_bwd_reduce: nparts=%d must be a multiple of B=%d that leaves no chunk of HW=%d empty", nparts, B, HW);
     ONET_REQUIRE((int64_t)nparts * C < (1ll << 31), "head_bwd_reduce: grid too large");
     hipLaunchKernelGGL(head_bwd_reduce_kernel, dim3((unsigned)((int64_t)nparts * C)), dim3(256), 0, as_stream(stream), L, L_bs, z, z_bs, g, gsLt,
                        gsLd, save, dL, part2, C, HW, chunks, chunk_len, (unsigned*)da_amax, B / 2);
