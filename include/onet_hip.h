@@ -148,7 +148,7 @@ int onet_convT2x2_fwd_slots(const void* xP, int64_t xP_bs, const void* x_amax, c
  * 8 channels at one sub-pixel; same size and scale pair as the forward pack), dx fp32 [B][Cin][h][w].  Weight gradient: x pre-split as
  * for the forward; dw [Cin][Ct][2][2]; dbias (may be NULL) [Ct] = sum of dy over all pixels, taken in the same launch; ws: at least
  * onet_convT2x2_wgrad_slots_ws_bytes(...) (0: shape not taken).  Both return 1 (nothing done) outside Cin % 128 == 0, Ct % 32 == 0,
- * h w % 128 == 0 (weight gradient: w a power of two). */
+ * h w % 128 == 0, w even (weight gradient: w a power of two >= 2; the workspace query says 0 for exactly the shapes it refuses). */
 int onet_convT2x2_dgrad_slots(const void* dyP, int64_t dyP_bs, const void* dy_amax, const void* wdP, float* dx, int64_t dx_bs, int nparts, int B,
                               int Cin, int Ct, int h, int w, void* stream);
 int64_t onet_convT2x2_wgrad_slots_ws_bytes(int B, int Cin, int Ct, int h, int w);

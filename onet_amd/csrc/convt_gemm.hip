@@ -1363,7 +1363,7 @@ int onet_convT2x2_dgrad_slots(const void* dyP, int64_t dyP_bs, const void* dy_am
 }
 
 int64_t onet_convT2x2_wgrad_slots_ws_bytes(int B, int Cin, int Ct, int h, int w) {
-    if ((Cin % 128) || (Ct % 32) || (((int64_t)h * w) % 128) || (w & (w - 1))) return 0;
+    if ((Cin % 128) || (Ct % 32) || (((int64_t)h * w) % 128) || (w & (w - 1)) || w < 2) return 0;    // (as onet_convT2x2_wgrad_slots)
     int k, per;
     (void)wgrad_slots_plan(B, Cin, Ct, h, w, k, per);
     return (int64_t)k * ((int64_t)Cin * 4 * Ct + 4 * Ct) * 4;

@@ -716,8 +716,11 @@ def test_pool_backward_with_bn_reduce(dev, B, C, H, W, G):
 def test_up_convT_cat(dev, h, w, Ho, Wo, Cin, Ct):
     """ConvTranspose2d(k=2, s=2) + F.pad + cat through the fused shuffle-epilogue GEMM (odd pad offsets, a wide map,
     channel counts that do not fill the 64-row GEMM tile) and its backward (Ct % 64 == 0: the gather-fused dgrad / wgrad;
-    otherwise space-to-depth + plain 1x1 GEMMs).  Maps of 128 k pixels with Cin % 128 == 0, Ct % 32 == 0 and no F.pad take
-    the DMA-fed 128 x 128 GEMMs of convt_gemm.hip (16x16 and wider maps, several K chunks, split-K in the wgrad)."""
+    otherwise space-to-depth + plain 1x1 GEMMs).  Without F.pad and with an even w the DMA-fed 128 x 128 GEMMs of
+    convt_gemm.hip take: the forward at Cin % 16 == 0, Ct % 32 == 0, h w % 128 == 0; the input gradient at Cin % 128 == 0,
+    Ct % 4 == 0, h w % 128 == 0; the weight gradient at Cin % 128 == 0, Ct % 32 == 0, h w % 32 == 0 -- the two gradients
+    only where Ct % 64 == 0 lets the backward reach them (16x16 and wider maps, several K chunks, split-K in the wgrad;
+    edge shapes of each predicate: test_gpu_convt_kernels.py)."""
     from onet_amd import functional as Fn
     from onet_amd import ops
     B, C2 = 2, Ct
