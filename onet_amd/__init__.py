@@ -8,8 +8,8 @@ PyTorch-ROCm supplies device memory, streams, autograd orchestration and torch.d
 from .ops import set_sync_bn
 from .modules import (BatchNormReLU2d, BilinearUp2x, Conv3x3, ConvT2x2, DoubleConv, Down, MaxPool2, Onet, UNet,
                       Up, invalidate_packed)
-from .inference import fused_eval_plan, scores, segment
+from .inference import EvalCounts, fused_eval_plan, scores, segment, validate
 
 __all__ = ["Onet", "UNet", "Up", "Down", "DoubleConv", "Conv3x3", "ConvT2x2", "BatchNormReLU2d", "MaxPool2",
-           "BilinearUp2x", "invalidate_packed", "set_sync_bn", "fused_eval_plan", "scores", "segment"]
+           "BilinearUp2x", "invalidate_packed", "set_sync_bn", "fused_eval_plan", "scores", "segment", "validate", "EvalCounts"]
 __version__ = "0.1.0"

@@ -1,4 +1,4 @@
-"""ctypes binding of libonet_hip.so (C ABI: include/onet_hip.h).
+"""ctypes binding of libonet_hip.so (C ABI: include/onet_hip.h, and include/onet_hip_eval.h for the validation step).
 
 The prototypes are PARSED from the header, so the Python side cannot drift from
 the ABI.  There is no CPU fallback: if the library cannot be loaded (or built),
@@ -11,6 +11,8 @@ import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip.h")
+# the validation step's entry points: declared in a header of their own, bound by load() like the main header's
+EVAL_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_eval.h")
 # ONET_HIP_LIB: another build of the same library (onet_amd.build --variant ...) for same-box A/B runs
 LIBPATH = os.environ.get("ONET_HIP_LIB") or os.path.join(HERE, "libonet_hip.so")
 
@@ -69,14 +71,17 @@ def load(build_if_missing: bool = True):
         from . import build as _build
         _build.build()
     lib = ctypes.CDLL(LIBPATH)
-    _protos = parse_header()
-    for name, (restype, argtypes, _) in _protos.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:  # header/ABI drift must be loud
-            raise OnetHipError(f"libonet_hip.so does not export {name} declared in onet_hip.h") from e
-        fn.restype = restype
-        fn.argtypes = argtypes
+    _protos = {}
+    for header in (HEADER, EVAL_HEADER):
+        protos = parse_header(header)
+        for name, (restype, argtypes, _) in protos.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:  # header/ABI drift must be loud
+                raise OnetHipError(f"libonet_hip.so does not export {name} declared in {os.path.basename(header)}") from e
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _protos.update(protos)
     _lib = lib
     return lib
 

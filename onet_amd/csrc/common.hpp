@@ -81,6 +81,17 @@ __device__ __forceinline__ void block_sum_256(T (&v)[NV], T* smem /* >= 4*NV */)
     }
 }
 
+// The head's softmax over one pixel's (vt, vd) and its label: softmax2_labels_kernel's expressions (head_loss.hip), term for term, so
+// that a caller's s0, s1 and label are that kernel's bits.  The label is s1 > s0: ties and NaN give 0.
+__device__ __forceinline__ int softmax2_label(float vt, float vd, float& s0, float& s1) {
+    const float m = fmaxf(vt, vd);
+    const float et = expf(vt - m), ed = expf(vd - m);
+    const float den = et + ed;
+    s0 = et / den;
+    s1 = ed / den;
+    return s1 > s0 ? 1 : 0;
+}
+
 // ---- fp16 operand splitting with per-tensor power-of-two scales (conv_split.hip consumers, bn.hip producers)
 // Scaled fp16 split in FOUR VALU per value pair: hi = fp16(s v), mid = fp16(s v - hi) with v_fma_mixlo/mixhi_f16 -- the fma of
 // fp32 operands (and, for mid, the fp16 hi part read straight from its register half) rounded once to fp16 into the low / high

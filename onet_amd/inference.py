@@ -34,6 +34,11 @@ ReLU + pooling pass reading it back -- as ONE launch (ops.conv3x3_*_pre_act_pool
 same accumulators).  Those units keep handing on their bound as scale AND amax, so every launch behind them sees the magnitude slots of
 the two-pass form and the whole forward is bit-identical to the plan without "+pool".
 
+The validation step (validate, EvalCounts): the scores of a batch -- by the labels-only plan where it applies, the ordinary forward
+elsewhere -- then ONE launch (ops.score_counts) that forms the labels and adds each image's confusion counts against the ground truth
+into a device tensor; nothing synchronises, and metrics.epoch_metrics turns an epoch's rows into the reference's metrics on the host.
+A new call: the functions above launch and return what they did without it.
+
 Every decision about what runs where is taken once per U-Net pass, by _build_plan: the query (unet_plan, fused_eval_plan) prints its
 record, the executor (_unet_pass) follows it, and _gate is the one place that says whether the plan runs at all and on which passes.
 The slot format is chosen once per plan (_format); the units below take it from there."""
@@ -426,6 +431,13 @@ def _unet_pass(plan, x):
     its coefficients): the head forms relu(bn(z)) on load.
     plan.head (labels-only calls): the last unit ends in the fused launch -> V [N, 1, H, W] = sum_c L[c] relu(bn(z))[c]; z is never
     written and L is dropped with the pass."""
+    res = _unet_pass_L(plan, x)
+    return res[1] if plan.head else res
+
+
+def _unet_pass_L(plan, x):
+    """_unet_pass, the same launches, which on a plan.head pass hands back (L, V): inc's fp32 output, which the head launch has just
+    read, for a caller that goes on to the loss (validate(want_loss=True))"""
     fmt, fused = plan.fmt, plan.levels[:plan.depth]
     N, _, H, W = x.shape
     catP, skips, L = [None] * 4, [None] * 4, None
@@ -463,7 +475,7 @@ def _unet_pass(plan, x):
         if u2.kind == "fused":
             t = _note(u2.name, _fused_unit(fmt, u2, t))
         elif u2.kind == "fused+head":
-            return _head_unit(fmt, u2, t, L)
+            return L, _head_unit(fmt, u2, t, L)
         else:
             z, save = _plain_conv(fmt, u2.conv, t), _coeffs(u2.bn)
     return L, z, save
@@ -473,14 +485,19 @@ def _run(passes, twin, X, bias=None):
     """The passes of a gated call (_gate, _runs) -> [_unet_pass's result per pass].  bias None: a U-Net alone, one pass over X; an Onet:
     one pass over the twin batch [X ; clip(1 - X + bias)] (shared weights: in eval both halves take the same coefficients), or one
     over X and one over the complement."""
+    return _run_passes(_unet_pass, passes, twin, X, bias)
+
+
+def _run_passes(unet_pass, passes, twin, X, bias):
+    """_run with the pass function of the caller's choice (_unet_pass | _unet_pass_L)"""
     X = X.contiguous()
     ops.amax_arena_reset(X.device)
     if bias is None:
-        return [_unet_pass(passes[0][1], X)]
+        return [unet_pass(passes[0][1], X)]
     if twin:
-        return [_unet_pass(passes[0][1], ops.twin_materialize(src=(X, bias)))]
-    first = _unet_pass(passes[0][1], X)
-    return [first, _unet_pass(passes[-1][1], ops.complement_clip(X, bias))]
+        return [unet_pass(passes[0][1], ops.twin_materialize(src=(X, bias)))]
+    first = unet_pass(passes[0][1], X)
+    return [first, unet_pass(passes[-1][1], ops.complement_clip(X, bias))]
 
 
 def unet_forward(unet, x):
@@ -550,3 +567,94 @@ def segment(onet, X, head=None):
                     return ops.softmax2_labels(VV[0], VV[1], want_S=False, want_labels=True)[1]
         S = onet(X)[4]
         return onet.predict_label(S)
+
+
+# ----------------------------------------------------------------------------- the validation step
+def _head_scores_L(onet, X):
+    """_head_scores whose halves are (L, V): inc's fp32 output beside the scores, the same launches.  Called like _head_scores."""
+    passes, twin = _gate(onet, None, "fused", x=X)
+    if not _runs(passes) or not passes[0][1].head:
+        return None
+    res = _run_passes(_unet_pass_L, passes, twin, X, float(onet.bias))
+    B = X.shape[0]
+    return [tuple(t[:B] for t in res[0]), tuple(t[B:] for t in res[0])] if twin else res
+
+
+class EvalCounts:
+    """The confusion counts of a validation epoch, kept on the device: an int64 [capacity, 4] tensor of per-image (TP, FP, FN, TN),
+    zeroed once, that validate(..., into=self) adds each batch's images to, and the host-side list of the batch sizes appended so far.
+    rows() is the epoch's one device-to-host copy; metrics.epoch_metrics(rows, batch_sizes, protocol) does the rest on the host."""
+
+    def __init__(self, capacity, device):
+        self.counts = torch.zeros((int(capacity), 4), dtype=torch.int64, device=device)
+        self.batch_sizes = []
+
+    def __len__(self):
+        return sum(self.batch_sizes)
+
+    def reset(self):
+        self.counts.zero_()
+        self.batch_sizes = []
+
+    def reserve(self, B):
+        """-> the first of the B rows the next batch adds to"""
+        row = len(self)
+        if row + B > self.counts.shape[0]:
+            raise ValueError(f"onet_amd: EvalCounts of {self.counts.shape[0]} images cannot take {B} more after {row}")
+        self.batch_sizes.append(int(B))
+        return row
+
+    def rows(self):
+        """int64 [images so far, 4] on the host"""
+        return self.counts[:len(self)].cpu()
+
+
+Validation = namedtuple("Validation", "counts labels S Vt Vd loss")
+
+
+def _loss_value(Lt, St, Ld, Sd):
+    """The value of Onet.compute_loss(Lt, St, Ld, Sd), composed from the JSD forward launches it makes (on the channel sums where Lt, Ld
+    are the tagged halves of one twin forward, as there), without its NaN assertion: that would synchronise.  -> 1-element tensor"""
+    tag_t, tag_d = getattr(Lt, "_onet_twin", None), getattr(Ld, "_onet_twin", None)
+    if (tag_t is not None and tag_d is not None and tag_t[0] is tag_d[0] and tag_t[1] == 0 and tag_d[1] == 1
+            and tag_t[2] == Lt._version and tag_d[2] == Ld._version and tag_t[0][0].shape[0] == 2 * Lt.shape[0]):
+        top, _ = ops.jsd_fwd(None, St, Sd, sums=tag_t[0][1])
+        dwn, _ = ops.jsd_fwd(None, Sd, St, sums=tag_t[0][2])
+    else:
+        top, _ = ops.jsd_fwd(Lt, St, Sd)
+        dwn, _ = ops.jsd_fwd(Ld, Sd, St)
+    return (-(top + dwn) / 2).reshape(1)
+
+
+def validate(onet, X, gt, into=None, want_labels=False, want_S=False, want_loss=False):
+    """One validation step on the device: the scores of `X` (the labels-only plan of scores / segment(head="fused") where it applies,
+    the ordinary forward elsewhere), then ONE launch (ops.score_counts) that forms the labels and adds each image's confusion counts
+    (TP, FP, FN, TN) against `gt` ([B, H, W] or [B, 1, H, W] in its own dtype: uint8 / bool, int32, int64, float32; positive where
+    != 0) -- into rows of `into` (an EvalCounts) or, without one, of a fresh [B, 4] tensor.  Under no_grad, with the model's settings;
+    no host synchronisation: everything returned is a device tensor.
+    -> Validation(counts = the [B, 4] view of this batch's rows, labels int64 [B, H, W] | None, S [B, 2, H, W] | None, Vt, Vd, loss |
+    None).  labels / S: written by the same launch where asked for -- labels bit-equal to segment(onet, X, head="fused") on the
+    labels-only plan, to onet.predict_label(S) of the forward elsewhere.  want_loss: the value of onet.compute_loss(Lt, St, Ld, Sd) on
+    this call's own L and S as a 1-element tensor (the labels-only plan hands inc's output back beside V; the NaN assertion of
+    compute_loss, a synchronisation, is the caller's to make on the value)."""
+    with torch.no_grad():
+        B = X.shape[0]
+        Lt = Ld = S_fwd = None
+        with ops.using(onet.settings):
+            res = _head_scores_L(onet, X) if want_loss else _head_scores(onet, X)
+            if res is not None and want_loss:
+                (Lt, Vt), (Ld, Vd) = res
+            elif res is not None:
+                Vt, Vd = res
+        if res is None:
+            Lt, Vt, Ld, Vd, S_fwd = onet(X)
+        with ops.using(onet.settings):
+            if into is None:
+                counts, row = torch.zeros((B, 4), dtype=torch.int64, device=Vt.device), 0
+            else:
+                counts, row = into.counts, into.reserve(B)
+            # (the forward's own S where there is one: the same bits, and nothing more to store)
+            S, labels = ops.score_counts(Vt, Vd, gt, counts, row=row, want_S=(want_S or want_loss) and S_fwd is None, want_labels=want_labels)
+            S = S_fwd if S is None else S
+            loss = _loss_value(Lt, S[:, :1], Ld, S[:, 1:]) if want_loss else None
+        return Validation(counts[row:row + B], labels, S if want_S else None, Vt, Vd, loss)

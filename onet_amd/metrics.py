@@ -9,6 +9,7 @@ import torch
 
 from . import _lib
 from .ops import _p, _stream, require_gpu
+from .ops import label_counts as ops_label_counts
 
 _EPS = float(np.spacing(1))
 
@@ -38,23 +39,42 @@ def confusion_counts(preds: torch.Tensor, targets: torch.Tensor) -> torch.Tensor
 
 
 def _tot(counts):
+    if not isinstance(counts, torch.Tensor):                 # host rows (EvalCounts.rows() as numpy, a list): [4] or [n, 4]
+        c = np.asarray(counts, dtype=np.int64)
+        return [int(v) for v in (c.sum(axis=0) if c.ndim == 2 else c)]
     c = counts.sum(dim=0).tolist() if counts.dim() == 2 else counts.tolist()
     return [int(v) for v in c]
 
 
-def _acc(counts) -> float:
-    """(TP + TN) / all  (UT:100-117)."""
-    tp, fp, fn, tn = _tot(counts)
+def label_counts(preds: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+    """[1, 4] int64 = (TP, FP, FN, TN) of two label tensors of one shape taken as ONE image, each read in its own dtype (uint8 / bool,
+    int32, int64, float32: no conversion pass) by ops.label_counts -- what the reference-signature forms of the helpers below count with."""
+    assert isinstance(preds, torch.Tensor) and isinstance(targets, torch.Tensor)
+    assert preds.shape == targets.shape
+    counts = torch.zeros((1, 4), dtype=torch.int64, device=preds.device)
+    return ops_label_counts(preds.reshape(1, -1), targets.reshape(1, -1), counts)
+
+
+def _counts_of(preds, targets):
+    """The helpers below take confusion counts ([4] or [n, 4], summed) or, like the reference's, (preds, targets[, num_k]) label
+    tensors: -> the counts either way"""
+    return preds if targets is None else label_counts(preds, targets)
+
+
+def _acc(preds, targets=None, num_k=2) -> float:
+    """(TP + TN) / all  (UT:100-117).  _acc(counts) | _acc(preds, targets, num_k)."""
+    tp, fp, fn, tn = _tot(_counts_of(preds, targets))
     return (tp + tn) / float(tp + fp + fn + tn)
 
 
-def _miou(counts) -> float:
-    """mean IoU over the 2 classes with the reference's empty-class rules (UT:119-155): a class absent from
+def _miou(preds, targets=None, num_k=2) -> float:
+    """_miou(counts) | _miou(preds, targets, num_k): mean IoU over the 2 classes with the reference's empty-class rules (UT:119-155): a class absent from
     both prediction and ground truth scores 1, absent from exactly one scores 0.  The reference accumulates
     `torch.sum(inter) / torch.sum(union)` (a float32 tensor) and ends with `miou.item() / nums`: when NEITHER class
     takes the tensor branch -- prediction and ground truth each a single, different class -- `miou` is still a python
     float there and UT:152 raises AttributeError; mirrored, since "same error behaviour" is the drop-in rule."""
-    tp, fp, fn, tn = _tot(counts)
+    assert num_k == 2
+    tp, fp, fn, tn = _tot(_counts_of(preds, targets))
     miou, is_tensor = np.float32(0.0), False
     for inter, gt, pd in ((tn, tn + fp, tn + fn), (tp, tp + fn, tp + fp)):      # class 0, class 1
         if gt == 0 and pd == 0:
@@ -75,24 +95,90 @@ def _ratio32(num: int, den: int) -> float:
     return float(np.float32(num) / (np.float32(den) + np.float32(_EPS)))
 
 
-def _target_iou(counts) -> float:
-    tp, fp, fn, tn = _tot(counts)
+def _target_iou(preds, targets=None) -> float:
+    tp, fp, fn, tn = _tot(_counts_of(preds, targets))
     return _ratio32(tp, tp + fp + fn)                                            # UT:157-173
 
 
-def _detection_rate(counts) -> float:
-    tp, fp, fn, tn = _tot(counts)
+def _detection_rate(preds, targets=None) -> float:
+    tp, fp, fn, tn = _tot(_counts_of(preds, targets))
     return _ratio32(tp, tp + fn)                                                 # UT:175-186
 
 
-def _false_alarm_rate(counts) -> float:
-    tp, fp, fn, tn = _tot(counts)
+def _false_alarm_rate(preds, targets=None) -> float:
+    tp, fp, fn, tn = _tot(_counts_of(preds, targets))
     return _ratio32(fp, fp + tn)                                                 # UT:188-192
 
 
 def flipped(counts):
     """confusion counts of 1 - pred: TP<->FN, FP<->TN."""
     return counts[..., [2, 3, 0, 1]]
+
+
+def evaluate_nau_segmentation_v2(predict_label, gt_label=None, gt_k=2):
+    """UT:213-234 -> (acc, miou, dr, far, t_iou).  (predict_label, gt_label) label tensors as in the reference, or confusion counts
+    alone."""
+    if gt_label is not None:
+        assert predict_label.numel() == gt_label.numel()
+        predict_label = label_counts(predict_label.reshape(-1), gt_label.reshape(-1))
+    c = _tot(predict_label)                                    # (one copy to the host, then integers)
+    return _acc(c), _miou(c), _detection_rate(c), _false_alarm_rate(c), _target_iou(c)
+
+
+def _matched(counts):
+    """Confusion counts of the prediction relabelled by its Hungarian match with the ground truth (UT:397-402): kept, or flipped"""
+    c = np.asarray(_tot(counts), dtype=np.int64)
+    return flipped(c) if dict(_hungarian_match(c, 2)).get(0, 0) == 1 else c
+
+
+def evaluate_segmentation(predict_label, gt_label=None, gt_k=2, verbose=0):
+    """UT:377-407 for two classes -> (acc, miou) of the prediction relabelled by its Hungarian match with the ground truth.
+    (predict_label, gt_label) label tensors as in the reference, or confusion counts alone."""
+    assert gt_k == 2
+    if gt_label is not None:
+        assert predict_label.numel() == gt_label.numel()
+        predict_label = label_counts(predict_label.reshape(-1), gt_label.reshape(-1))
+    c = _tot(predict_label)
+    if verbose == 2:
+        print("num_test: %d" % sum(c))
+        for k, n in enumerate((c[1] + c[3], c[0] + c[2])):
+            print("gt_k: %d count: %d" % (k, n))
+    c = _matched(c)
+    return _acc(c), _miou(c)
+
+
+def epoch_metrics(rows, batch_sizes, protocol):
+    """The metrics of a validation epoch from the per-image confusion counts alone: `rows` [n, 4] (EvalCounts.rows()), `batch_sizes`
+    the images of each batch in order (EvalCounts.batch_sizes).  Host integer arithmetic, the reference's float32 steps included.
+    protocol "simclutter" (TS:98-172): per batch the hard re-assignment on the batch totals (UT:439-453: the flip TP<->FN, FP<->TN
+      where acc < acc of the flipped counts), the five metrics of evaluate_nau_segmentation_v2 on them, the mean over batches
+      -> (acc, miou, dr, far, tiou).
+    protocol "zy3" (UZ:151-208): per batch the Hungarian match on the batch totals (reorder_segmentation) and evaluate_segmentation
+      on the relabelled batch (its values are not part of the epoch's result, its AttributeError is), then acc, miou, dr, far of every
+      image on its relabelled counts (evaluate_nau_segmentation_v2), the mean over images -> (acc, miou, dr, far).
+    UT:149's AttributeError is raised where the reference raises it: a batch (simclutter, zy3) or an image (zy3) whose prediction and
+    ground truth are each one class, and different ones."""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 4)
+    if sum(batch_sizes) != rows.shape[0]:
+        raise ValueError(f"epoch_metrics: {rows.shape[0]} rows for batches of {list(batch_sizes)}")
+    if protocol not in ("simclutter", "zy3"):
+        raise ValueError(f"epoch_metrics: protocol must be 'simclutter' or 'zy3', not {protocol!r}")
+    vals, r0 = [], 0
+    for n in batch_sizes:
+        batch = rows[r0:r0 + n]
+        r0 += n
+        tot = batch.sum(axis=0)
+        if protocol == "simclutter":
+            if _acc(tot) < _acc(flipped(tot)):
+                tot = flipped(tot)
+            vals.append(evaluate_nau_segmentation_v2(tot))
+        else:
+            flip = dict(_hungarian_match(tot, 2)).get(0, 0) == 1
+            evaluate_segmentation(flipped(tot) if flip else tot)
+            for c in batch:
+                vals.append(evaluate_nau_segmentation_v2(flipped(c) if flip else c)[:4])
+    # (np.array(list).mean() of each list like the reference: numpy's pairwise sum of a 1-D array, not a row-by-row one)
+    return tuple(float(np.array([v[k] for v in vals], dtype=np.float64).mean()) for k in range(len(vals[0])))
 
 
 def _hungarian_match(counts, num_k: int = 2):

@@ -2323,6 +2323,63 @@ def softmax2_labels(Vt, Vd, want_S=True, want_labels=True):
     return S, Y
 
 
+# dtype codes of a label map (include/onet_hip_eval.h): read in place, no conversion pass
+_LABEL_DTYPES = {torch.uint8: 0, torch.bool: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3}
+
+
+def _label_map(t, B, HW, what):
+    """-> (tensor, dtype code, batch stride in elements) of a label map of B images of HW elements, each image contiguous (a batch
+    slice of a wider tensor is read where it lies; anything else is copied)"""
+    require_gpu(t)
+    if t.dtype not in _LABEL_DTYPES:
+        raise TypeError(f"{what}: label maps are uint8 / bool, int32, int64 or float32, not {t.dtype}")
+    if t.dim() < 2 or t.shape[0] != B or t.numel() != B * HW:
+        raise ValueError(f"{what}: a label map of {B} images of {HW} elements expected, got {tuple(t.shape)}")
+    if not t[0].is_contiguous() or (B > 1 and t.stride(0) < HW):
+        t = t.contiguous()
+    return t, _LABEL_DTYPES[t.dtype], (t.stride(0) if B > 1 else HW)
+
+
+def _count_rows(counts, row, B, what):
+    if counts.dtype != torch.int64 or counts.dim() != 2 or counts.shape[1] != 4 or not counts.is_cuda or not counts.is_contiguous():
+        raise ValueError(f"{what}: counts must be a contiguous int64 [n, 4] tensor on the GPU")
+    if row < 0 or row + B > counts.shape[0]:
+        raise ValueError(f"{what}: rows [{row}, {row + B}) outside a counts tensor of {counts.shape[0]} rows")
+    return counts.data_ptr() + 32 * row
+
+
+def score_counts(Vt, Vd, gt, counts, row=0, want_S=False, want_labels=False):
+    """The validation step in one launch: per-image confusion counts (TP, FP, FN, TN) of the head's labels of Vt, Vd [B, 1, H, W]
+    against the ground truth `gt` (B images in its own dtype, positive where != 0), ADDED to rows [row, row + B) of `counts` (int64
+    [n, 4]: the caller zeroes it once per epoch).  -> (S [B, 2, H, W] | None, Y int64 [B, H, W] | None): softmax2_labels' bits, written
+    by the same launch where asked for."""
+    require_gpu(Vt, Vd)
+    if Vt.shape != Vd.shape or Vt.dim() != 4 or Vt.shape[1] != 1 or Vt.dtype != F32 or Vd.dtype != F32:
+        raise ValueError("score_counts: Vt and Vd must be fp32 [B, 1, H, W] tensors of one shape")
+    Vt, Vd = Vt.contiguous(), Vd.contiguous()
+    B, _, H, W = Vt.shape
+    gt, code, gbs = _label_map(gt, B, H * W, "score_counts")
+    dst = _count_rows(counts, row, B, "score_counts")
+    S = torch.empty((B, 2, H, W), dtype=F32, device=Vt.device) if want_S else None
+    Y = torch.empty((B, H, W), dtype=torch.int64, device=Vt.device) if want_labels else None
+    _lib.call("onet_score_counts", _p(Vt), _p(Vd), _p(gt), code, gbs, _p(S), _p(Y), dst, B, H * W, _stream(),
+              nbytes=B * H * W * (4.0 * (2 + 2 * want_S + 2 * want_labels) + gt.element_size()))
+    return S, Y
+
+
+def label_counts(pred, gt, counts, row=0):
+    """Per-image confusion counts of a label map `pred` against `gt` (B images each, any of the label dtypes, read in place), ADDED to
+    rows [row, row + B) of `counts` like score_counts.  -> counts"""
+    B = pred.shape[0]
+    HW = pred.numel() // max(B, 1)
+    pred, pcode, pbs = _label_map(pred, B, HW, "label_counts")
+    gt, gcode, gbs = _label_map(gt, B, HW, "label_counts")
+    dst = _count_rows(counts, row, B, "label_counts")
+    _lib.call("onet_label_counts", _p(pred), pcode, pbs, _p(gt), gcode, gbs, dst, B, HW, _stream(),
+              nbytes=float(B * HW * (pred.element_size() + gt.element_size())))
+    return counts
+
+
 # ----------------------------------------------------------------------------- optimizer
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
     require_gpu(p, g, m, v)
