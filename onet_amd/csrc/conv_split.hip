@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include "common.hpp"
+#include "../../include/onet_hip_ragged.h"
 
 using namespace onet;
 
@@ -1188,10 +1189,14 @@ __device__ __forceinline__ u32x4s pre16_slot_transpose(const f32x4s& d1, const f
     const unsigned r0 = (unsigned)__shfl_xor((int)(o4 ? Alo : Blo), 4, 64), r1 = (unsigned)__shfl_xor((int)(o4 ? Ahi : Bhi), 4, 64);
     return o4 ? u32x4s{r0, r1, Blo, Bhi} : u32x4s{Alo, Ahi, r0, r1};
 }
-template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false, bool POOL = false>
+// RAG (round 13, the ragged entries): the pooled fp32 store on maps that are not made of full tiles.  Everything else of the kernel
+// already is per-slot / per-float4 bounds-checked (staging: the out-of-range offset; stores: yo < H && xo < W), so the ragged entries
+// launch the full-tile instances; only the pooled fp32 rows, whose two float2 per lane share ONE guard on full tiles, need code.
+template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false, bool POOL = false, bool RAG = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     constexpr bool F16 = PM == 1;
     static_assert(!POOL || ACT, "conv3x3_pre16_kernel: the pooled stores ride on the activation epilogue");
+    static_assert(!RAG || (POOL && PM == 2), "conv3x3_pre16_kernel: the ragged instance is the one-part pooled epilogue's");
     static_assert(!ACT || (PM == 2 && !ST && !W16 && !RD), "conv3x3_pre16_kernel: the activation epilogue goes with the one-part bf16 slot store");
     static_assert(!HEAD || (PM != 0 && !ST && !W16 && !RD && !ACT), "conv3x3_pre16_kernel: the head epilogue replaces every store of a plain forward launch");
     using C = SpPreCfg<W16>;
@@ -1647,7 +1652,21 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
                     pm[ct][2 * ch] = fmaxf(fmaxf(t[0], t[1]), fmaxf(u[0], u[1]));
                     pm[ct][2 * ch + 1] = fmaxf(fmaxf(t[2], t[3]), fmaxf(u[2], u[3]));
                 }
-            if (a.pl_y && yp < Hp && xp0 + 9 < Wp) {
+            if constexpr (RAG) {
+                // one guard per float2: Wp and xp0 are even (W % 4 == 0), so a pair is wholly inside the pooled row or wholly outside;
+                // the address is formed under the guard
+                if (a.pl_y && yp < Hp) {
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) {
+                        const int co = co0 + ct * 16 + r16;
+                        if (co < a.Cout) {
+                            float* row = a.pl_y + (int64_t)b * a.pl_y_bs + ((int64_t)co * Hp + yp) * Wp;
+                            if (xp0 + 1 < Wp) *reinterpret_cast<float2*>(row + xp0) = make_float2(pm[ct][0], pm[ct][1]);
+                            if (xp0 + 9 < Wp) *reinterpret_cast<float2*>(row + xp0 + 8) = make_float2(pm[ct][2], pm[ct][3]);
+                        }
+                    }
+                }
+            } else if (a.pl_y && yp < Hp && xp0 + 9 < Wp) {
 #pragma unroll
                 for (int ct = 0; ct < 4; ++ct) {
                     const int co = co0 + ct * 16 + r16;
@@ -1745,7 +1764,7 @@ int sp_launch_persistent(void (*kern)(Args), PerDeviceOnce& once, int lds_bytes,
     return check_launch(name);
 }
 
-template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false, bool POOL = false>
+template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false, bool POOL = false, bool RAG = false>
 int launch_split_pre(SpPreArgs a, hipStream_t st) {
     using C = SpPreCfg<W16>;
     const int LDS_BYTES = C::LDS_BYTES + (ST ? C::NW * 64 * 2 * 4 : 0) + (ACT || HEAD ? 2 * 3 * 64 * 4 : 0);
@@ -1761,7 +1780,8 @@ int launch_split_pre(SpPreArgs a, hipStream_t st) {
     // level (that instance of the new kernel exceeds the register budget).  The head epilogue exists on the 16x16x32 kernel alone.
     constexpr bool P16 = RD || PM == 2 || (ST && !W16) || HEAD;
     void (*kern)(SpPreArgs);
-    if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD, ACT, HEAD, POOL>;      // (constexpr: the instances not dispatched are not built)
+    static_assert(!RAG || P16, "launch_split_pre: the ragged instance exists on the 16x16x32 kernel alone");
+    if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD, ACT, HEAD, POOL, RAG>;      // (constexpr: the instances not dispatched are not built)
     else kern = conv3x3_split_pre_kernel<ST, PM, W16, ACT, POOL>;
     static PerDeviceOnce attr_once;
     return sp_launch_persistent(kern, attr_once, LDS_BYTES, tiles, C::NW * 64,
@@ -2721,15 +2741,28 @@ int onet_conv3x3_split_fwd_pre_act(const void* xs, int64_t xs_bs, const void* x_
 // receive the exact max a; a (may be NULL): the activation as fp32 NCHW too.  Bit for bit what the plain launch (fp32 z) followed by
 // onet_bn_relu_apply_split(nparts = 1) writes; z itself is never stored.  Returns 1 (nothing launched) where the map is not made of full
 // 16 x 32 tiles, Cin is not a multiple of 32 or Cout not one of 64.
-int onet_conv3x3_plain16_fwd_pre_act(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs, void* a_amax,
-                                     float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
-    ONET_REQUIRE(xs && wq && save && aP, "conv3x3_plain16_fwd_pre_act: null pointer");
-    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv3x3_plain16_fwd_pre_act: bad shape");
-    if (W < 32 || (W % 32) || (H % 16) || (Cin % 32) || (Cout % 64)) return 1;
-    if (const int rc = pre_operand_checks("conv3x3_plain16_fwd_pre_act", xs, xs_bs, 2, Cin, Cout, H, W)) return rc;
-    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "conv3x3_plain16_fwd_pre_act: 16-byte aligned slots required");
-    ONET_REQUIRE(!a || ((a_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0), "conv3x3_plain16_fwd_pre_act: 16-byte aligned rows required");
-    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W / 2 && (!a || a_bs >= (int64_t)Cout * H * W), "conv3x3_plain16_fwd_pre_act: batch stride too small");
+// The maps an eval-mode entry takes: made of full 16 x 32 tiles, or -- the _ragged entries of include/onet_hip_ragged.h (round 13,
+// one-part operands only) -- any map of even H and W % 4 == 0 below 2^24 pixels: the tile counts are cdiv, the staging gives every
+// out-of-map slot the out-of-range offset and every store is guarded per slot / float4 / pooled float2.  With H and W even and tiles
+// starting on even coordinates a 2 x 2 pooling window is wholly inside the map or wholly outside.
+static bool pre_map_ok(bool ragged, int H, int W) {
+    if (ragged) return !((H & 1) || (W & 3) || (int64_t)H * W >= (1 << 24));
+    return !(W < 32 || (W % 32) || (H % 16));
+}
+// The exact-maximum record of the activation epilogue covers a tile's out-of-map accumulators too: the ragged entries do not take one
+#define ONET_RAGGED_NO_AMAX(entry, ragged, a_amax) \
+    ONET_REQUIRE(!(ragged) || !(a_amax), "%s: the ragged entry records no exact maximum (a_amax must be NULL)", entry)
+
+static int plain16_pre_act_impl(const char* entry, bool ragged, const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP,
+                                int64_t aP_bs, void* a_amax, float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    ONET_REQUIRE(xs && wq && save && aP, "%s: null pointer", entry);
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
+    if (!pre_map_ok(ragged, H, W) || (Cin % 32) || (Cout % 64)) return 1;
+    ONET_RAGGED_NO_AMAX(entry, ragged, a_amax);
+    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 2, Cin, Cout, H, W)) return rc;
+    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "%s: 16-byte aligned slots required", entry);
+    ONET_REQUIRE(!a || ((a_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0), "%s: 16-byte aligned rows required", entry);
+    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W / 2 && (!a || a_bs >= (int64_t)Cout * H * W), "%s: batch stride too small", entry);
     SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, nullptr, 0, nullptr, 0};
     p.zP = aP;
     p.zP_bs = aP_bs;
@@ -2741,19 +2774,49 @@ int onet_conv3x3_plain16_fwd_pre_act(const void* xs, int64_t xs_bs, const void* 
     return launch_split_pre<false, 2, false, false, true>(p, as_stream(stream));
 }
 
+int onet_conv3x3_plain16_fwd_pre_act(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs, void* a_amax,
+                                     float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    return plain16_pre_act_impl("conv3x3_plain16_fwd_pre_act", false, xs, xs_bs, wq, save, aP, aP_bs, a_amax, a, a_bs, B, Cin, Cout, H, W, stream);
+}
+
+// The same launch on a ragged map (pre_map_ok): the full-tile entry on the map zero-padded to whole tiles, value for value on the map,
+// nothing written outside it.  Returns 1 (nothing launched) for odd H, W % 4, Cin % 32 or Cout % 64.
+int onet_conv3x3_plain16_fwd_pre_act_ragged(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
+                                            void* a_amax, float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    return plain16_pre_act_impl("conv3x3_plain16_fwd_pre_act_ragged", true, xs, xs_bs, wq, save, aP, aP_bs, a_amax, a, a_bs, B, Cin, Cout, H, W,
+                                stream);
+}
+
+// The plain forward of onet_conv3x3_split_fwd_pre(wq_f16 = 2, fp32 z, no statistics) on a ragged map: the one-part plan's last unit
+// where no head epilogue follows.  Returns 1 (nothing launched) outside the ragged domain.
+int onet_conv3x3_plain16_fwd_pre_plain_ragged(const void* xs, int64_t xs_bs, const void* wq, float* z, int64_t z_bs, int B, int Cin, int Cout,
+                                              int H, int W, void* stream) {
+    const char* entry = "conv3x3_plain16_fwd_pre_plain_ragged";
+    ONET_REQUIRE(xs && wq && z, "%s: null pointer", entry);
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
+    if (!pre_map_ok(true, H, W) || (Cin % 32) || (Cout % 64)) return 1;
+    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 2, Cin, Cout, H, W)) return rc;
+    ONET_REQUIRE((z_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0, "%s: 16-byte aligned rows required", entry);
+    ONET_REQUIRE(z_bs >= (int64_t)Cout * H * W, "%s: batch stride too small", entry);
+    SpPreArgs a{xs, xs_bs, (const __bf16*)wq, z, z_bs, B, Cin, Cout, H, W, 0, 0, 0, nullptr, nullptr, 0, nullptr, 0};
+    return launch_split_pre<false, 2, false>(a, as_stream(stream));
+}
+
 // Eval-mode inference, an encoder block's second unit: the _act entries above with the 2 x 2 max-pooling of the activation in the same
 // epilogue (SpPreArgs::pl_*).  Everything the _act entry writes is written as it writes it -- aP (the leading channel groups of a concat
 // buffer qualify), a, a_amax -- plus the pooled tensor m = max over each 2 x 2 window of relu(bn(z)): as slots yP [B][Cout/8][H/2][parts]
 // [W/2][8] (fp16: the parts of 2^k m with aP's k; plain bf16: one part, unscaled; batch stride yP_bs in 4-byte units), as fp32 y
 // [B][Cout][H/2][W/2] (batch stride y_bs), or both; at least one.  Bit for bit what the plain launch followed by
 // onet_bn_relu_apply_pool_split writes.  Returns 1 (nothing launched) outside the _act entry's domain.
-static int pre_act_pool_impl(const char* entry, int wq_f16, const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2,
+static int pre_act_pool_impl(const char* entry, bool ragged, int wq_f16, const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2,
                              int split_ch, const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
                              int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
     ONET_REQUIRE(xs && wq && save && aP && (aP_slots || wq_f16 == 2), "%s: null pointer", entry);
     ONET_REQUIRE(yP || y, "%s: a pooled destination is required (yP, y or both)", entry);
     ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
-    if (W < 32 || (W % 32) || (H % 16) || (Cin % (wq_f16 == 2 ? 32 : 16)) || (Cout % 64)) return 1;
+    if (!pre_map_ok(ragged, H, W) || (Cin % (wq_f16 == 2 ? 32 : 16)) || (Cout % 64)) return 1;
+    ONET_REQUIRE(!ragged || wq_f16 == 2, "%s: the ragged entry takes one-part operands", entry);
+    ONET_RAGGED_NO_AMAX(entry, ragged, a_amax);
     ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
     if (const int rc = pre_operand_checks(entry, xs, xs_bs, wq_f16, Cin, Cout, H, W)) return rc;
     const int64_t n = (int64_t)Cout * H * W, per = wq_f16 == 2 ? 2 : 1;       // slot elements per 4-byte unit: one bf16 part / two fp16 parts
@@ -2776,6 +2839,8 @@ static int pre_act_pool_impl(const char* entry, int wq_f16, const void* xs, int6
     p.pl_P_bs = yP_bs;
     p.pl_y = y;
     p.pl_y_bs = y_bs;
+    // a map of full tiles takes the full-tile instance from either entry: the same launch, the same bits
+    if (ragged && !pre_map_ok(false, H, W)) return launch_split_pre<false, 2, false, false, true, false, true, true>(p, as_stream(stream));
     if (wq_f16 == 2) return launch_split_pre<false, 2, false, false, true, false, true>(p, as_stream(stream));
     return launch_split_pre<false, 1, false, false, true, false, true>(p, as_stream(stream));
 }
@@ -2783,15 +2848,23 @@ static int pre_act_pool_impl(const char* entry, int wq_f16, const void* xs, int6
 int onet_conv3x3_plain16_fwd_pre_act_pool(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs, void* a_amax,
                                           float* a, int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin, int Cout, int H,
                                           int W, void* stream) {
-    return pre_act_pool_impl("conv3x3_plain16_fwd_pre_act_pool", 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, aP, aP_bs, nullptr, a_amax, a, a_bs,
-                             yP, yP_bs, y, y_bs, B, Cin, Cout, H, W, stream);
+    return pre_act_pool_impl("conv3x3_plain16_fwd_pre_act_pool", false, 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, aP, aP_bs, nullptr, a_amax, a,
+                             a_bs, yP, yP_bs, y, y_bs, B, Cin, Cout, H, W, stream);
+}
+
+// ... on a ragged map (pre_map_ok; H / 2 x W / 2 pooled maps, pooled fp32 rows of W / 2 floats): see onet_conv3x3_plain16_fwd_pre_act_ragged
+int onet_conv3x3_plain16_fwd_pre_act_pool_ragged(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
+                                                 void* a_amax, float* a, int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B,
+                                                 int Cin, int Cout, int H, int W, void* stream) {
+    return pre_act_pool_impl("conv3x3_plain16_fwd_pre_act_pool_ragged", true, 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, aP, aP_bs, nullptr,
+                             a_amax, a, a_bs, yP, yP_bs, y, y_bs, B, Cin, Cout, H, W, stream);
 }
 
 int onet_conv3x3_split_fwd_pre_act_pool(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
                                         const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
                                         int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin, int Cout, int H, int W,
                                         void* stream) {
-    return pre_act_pool_impl("conv3x3_split_fwd_pre_act_pool", 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, aP, aP_bs, aP_slots,
+    return pre_act_pool_impl("conv3x3_split_fwd_pre_act_pool", false, 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, aP, aP_bs, aP_slots,
                              a_amax, a, a_bs, yP, yP_bs, y, y_bs, B, Cin, Cout, H, W, stream);
 }
 
@@ -2799,12 +2872,12 @@ int onet_conv3x3_split_fwd_pre_act_pool(const void* xs, int64_t xs_bs, const voi
 // the forward convolution of the _act entries above on the same operands, form h = max(0, fma(z - mean, sc, sh)) from save [4][Cout] on
 // the accumulators and write V [B][H][W] = sum_c L[c] h[c] (L: fp32 NCHW, batch stride L_bs) -- nothing else: neither z nor h is stored.
 // Returns 1 (nothing launched, nothing written) outside maps made of full 16 x 32 tiles, Cin % 32 (plain bf16) / % 16 (fp16), Cout == 64.
-static int pre_head_impl(const char* entry, int wq_f16, const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2,
+static int pre_head_impl(const char* entry, bool ragged, int wq_f16, const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2,
                          int split_ch, const void* wq, const float* save, const float* L, int64_t L_bs, float* V, int B, int Cin, int Cout,
                          int H, int W, void* stream) {
     ONET_REQUIRE(xs && wq && save && L && V, "%s: null pointer", entry);
     ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
-    if (W < 32 || (W % 32) || (H % 16) || (Cin % (wq_f16 == 2 ? 32 : 16)) || Cout != 64) return 1;
+    if (!pre_map_ok(ragged, H, W) || (Cin % (wq_f16 == 2 ? 32 : 16)) || Cout != 64) return 1;
     ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
     ONET_REQUIRE((L_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(L) & 15) == 0 && (reinterpret_cast<uintptr_t>(V) & 15) == 0,
                  "%s: 16-byte aligned rows required", entry);
@@ -2822,13 +2895,20 @@ static int pre_head_impl(const char* entry, int wq_f16, const void* xs, int64_t 
 
 int onet_conv3x3_plain16_fwd_pre_head(const void* xs, int64_t xs_bs, const void* wq, const float* save, const float* L, int64_t L_bs, float* V,
                                       int B, int Cin, int Cout, int H, int W, void* stream) {
-    return pre_head_impl("conv3x3_plain16_fwd_pre_head", 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, L, L_bs, V, B, Cin, Cout, H, W, stream);
+    return pre_head_impl("conv3x3_plain16_fwd_pre_head", false, 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, L, L_bs, V, B, Cin, Cout, H, W, stream);
+}
+
+// ... on a ragged map (pre_map_ok): the L loads and the V store are guarded per float4; see onet_conv3x3_plain16_fwd_pre_act_ragged
+int onet_conv3x3_plain16_fwd_pre_head_ragged(const void* xs, int64_t xs_bs, const void* wq, const float* save, const float* L, int64_t L_bs,
+                                             float* V, int B, int Cin, int Cout, int H, int W, void* stream) {
+    return pre_head_impl("conv3x3_plain16_fwd_pre_head_ragged", true, 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, L, L_bs, V, B, Cin, Cout, H, W,
+                         stream);
 }
 
 int onet_conv3x3_split_fwd_pre_head(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
                                     const void* wq, const float* save, const float* L, int64_t L_bs, float* V, int B, int Cin, int Cout, int H,
                                     int W, void* stream) {
-    return pre_head_impl("conv3x3_split_fwd_pre_head", 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, L, L_bs, V, B, Cin, Cout,
+    return pre_head_impl("conv3x3_split_fwd_pre_head", false, 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, L, L_bs, V, B, Cin, Cout,
                          H, W, stream);
 }
 

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include "common.hpp"
+#include "../../include/onet_hip_ragged.h"
 
 using namespace onet;
 
@@ -572,7 +573,12 @@ __device__ __forceinline__ void slot_wait() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int NP>
+// RAG (round 13: onet_convT2x2_fwd_slots_ragged, maps with h w % 128 != 0): the pixel tiles are cdiv(h w, 128) PER IMAGE (SArgs::nTiles
+// counts them over the batch), a B-operand slot of a pixel p >= h w takes the out-of-range offset -- the plain arithmetic would alias
+// the next channel group inside the resource -- and the epilogue stores only p < h w.  Pixels are independent GEMM columns: the map's
+// own values are those of the full-tile instance on the map with zero rows appended.
+constexpr unsigned SLOT_OOB = 0x80000000u;        // beyond every resource (< 2 GiB, host-checked), chunk steps included
+template <int NP, bool RAG = false>
 __global__ __launch_bounds__(256, SLOT_OCC) void convt_slot_fwd_kernel(SArgs g) {
     constexpr int KS = 4 / NP;                     // slots (8 channels each) per chunk: 16 channels (NP = 2) / 32 (NP = 1)
     constexpr int TILE = KS * NP * 128;            // slots of one operand tile: [slot of the chunk][part][row / pixel] = 8 KB
@@ -590,7 +596,8 @@ __global__ __launch_bounds__(256, SLOT_OCC) void convt_slot_fwd_kernel(SArgs g) 
     const int wr = wid >> 1, wc = wid & 1, l31 = lane & 31, kh = lane >> 5;
     const int hw = g.h * g.w, M = 4 * g.Ct;
     const int m0 = mt * 128, n0 = nt * 128;        // global pixel index b * hw + p; hw % 128 == 0: one image per tile
-    const int b = n0 / hw, p0 = n0 % hw;
+    const int tpi = RAG ? (hw + 127) / 128 : 1;    // RAG: pixel tiles per image
+    const int b = RAG ? nt / tpi : n0 / hw, p0 = RAG ? (nt % tpi) * 128 : n0 % hw;
 
     const i32x4g ra = g_rsrc(g.wP, (int64_t)(g.Cin / 8) * NP * M * 16);
     const i32x4g rb = g_rsrc(reinterpret_cast<const unsigned*>(g.xP) + (int64_t)b * g.x_bs, (int64_t)(g.Cin / 8) * hw * NP * 16);
@@ -602,6 +609,9 @@ __global__ __launch_bounds__(256, SLOT_OCC) void convt_slot_fwd_kernel(SArgs g) 
         a_off[j] = (unsigned)((((int64_t)c8 * NP + part) * M + m0 + r) * 16);
         const int p = p0 + r, i = p / g.w, jx = p % g.w;
         b_off[j] = (unsigned)(((((int64_t)c8 * g.h + i) * NP + part) * g.w + jx) * 16);
+        if constexpr (RAG) {
+            if (p >= hw) b_off[j] = SLOT_OOB;
+        }
     }
     const unsigned a_step = (unsigned)((int64_t)KS * NP * M * 16), b_step = (unsigned)((int64_t)KS * hw * NP * 16);
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) u32x4g*)lds;
@@ -706,6 +716,9 @@ __global__ __launch_bounds__(256, SLOT_OCC) void convt_slot_fwd_kernel(SArgs g) 
                     px[dj][2 * gq] = __builtin_bit_cast(float, even);
                     px[dj][2 * gq + 1] = __builtin_bit_cast(float, odd);
                 }
+            }
+            if constexpr (RAG) {
+                if (p >= hw) continue;              // (behind the lane exchange: both partners hold the same pixel)
             }
             u32x4g* dst = reinterpret_cast<u32x4g*>(reinterpret_cast<unsigned*>(g.yP) + (int64_t)b * g.y_bs) +
                           ((int64_t)(c8 * (2 * g.h) + 2 * y + kh) * NP) * (2 * g.w) + 2 * x;
@@ -1411,6 +1424,25 @@ int onet_convT2x2_fwd_slots(const void* xP, int64_t xP_bs, const void* x_amax, c
     ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "convT2x2_fwd_slots: grid too large");
     if (nparts == 2) hipLaunchKernelGGL(convt_slot_fwd_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
     else hipLaunchKernelGGL(convt_slot_fwd_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
+    return check_launch("convt_slot_fwd_kernel");
+}
+
+// onet_convT2x2_fwd_slots (nparts = 1) on maps whose pixel count is no multiple of 128 (include/onet_hip_ragged.h): its domain without
+// h w % 128 == 0.  Returns 1 (nothing launched) outside it.
+int onet_convT2x2_fwd_slots_ragged(const void* xP, int64_t xP_bs, const void* wP, const float* bias, void* yP, int64_t yP_bs, int B, int Cin, int Ct,
+                                   int h, int w, void* stream) {
+    ONET_REQUIRE(xP && wP && yP && B > 0 && Cin > 0 && Ct > 0 && h > 0 && w > 0, "convT2x2_fwd_slots_ragged: bad args");
+    const int64_t hw = (int64_t)h * w;
+    if ((Cin % 32) || Cin < 128 || (Ct % 32) || (w & 1) || !aligned16(xP) || !aligned16(wP) || !aligned16(yP) || (xP_bs & 3) || (yP_bs & 3) ||
+        (int64_t)Cin * hw * 2 >= (1ll << 31) || (int64_t)Cin * 4 * Ct * 2 >= (1ll << 31))
+        return 1;
+    ONET_REQUIRE(xP_bs >= (int64_t)Cin * hw / 2 && yP_bs >= (int64_t)Ct * 4 * hw / 2, "convT2x2_fwd_slots_ragged: batch stride too small");
+    const int64_t ntiles = (int64_t)B * ((hw + 127) / 128);
+    ONET_REQUIRE(ntiles < (1ll << 24), "convT2x2_fwd_slots_ragged: grid too large");
+    SArgs g{wP, xP, xP_bs, bias, yP, yP_bs, nullptr, nullptr, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)ntiles};
+    const int64_t blocks = (int64_t)g.mTiles * g.nTiles;
+    ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "convT2x2_fwd_slots_ragged: grid too large");
+    hipLaunchKernelGGL((convt_slot_fwd_kernel<1, true>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
     return check_launch("convt_slot_fwd_kernel");
 }
 

@@ -34,6 +34,14 @@ ReLU + pooling pass reading it back -- as ONE launch (ops.conv3x3_*_pre_act_pool
 same accumulators).  Those units keep handing on their bound as scale AND amax, so every launch behind them sees the magnitude slots of
 the two-pass form and the whole forward is bit-identical to the plan without "+pool".
 
+Settings.fused_eval = "bf16+pool+ragged" (ops.fused_eval_ragged()): the plan of "bf16+pool" that also takes RAGGED levels -- maps not
+made of full 16 x 32 tiles, of even H and W % 4 == 0 above 16 pixels (ops.eval_layer_ok_ragged): the data sets' 224 x 224 down to its
+28-pixel level, 200 x 200 down to 100.  _build_plan marks such a level (_Level.ragged) and its units run the *_ragged entry points
+(include/onet_hip_ragged.h: the same kernels, bounds-checked loads that return zero and guarded stores); a ConvTranspose2d edge carries
+its route (_Level.route): the slot-operand GEMM or its ragged entry (h w % 128 != 0), and from a fall-back level the fp32-operand GEMM
+or, where that does not take the map, the general kernel and one conversion pass.  On a level made of full tiles the launches, their
+order and the bits are those of "bf16+pool".
+
 The validation step (validate, EvalCounts): the scores of a batch -- by the labels-only plan where it applies, the ordinary forward
 elsewhere -- then ONE launch (ops.score_counts) that forms the labels and adds each image's confusion counts against the ground truth
 into a device tensor; nothing synchronises, and metrics.epoch_metrics turns an epoch's rows into the reference's metrics on the host.
@@ -70,16 +78,22 @@ def _units(blk):
 # The slot format of a plan: parts per slot, the weight pack, the layer predicate, the three launches (act_pool: the unit in front of a
 # max-pool in one launch, taken where ops.fused_eval_pool() holds), whether tensors carry magnitude slots (without them: scale = amax =
 # None everywhere, no bound launches) and whether the pooled tensors are traced
-_Format = namedtuple("_Format", "operands parts pack layer_ok act act_pool head magnitude trace_pool")
+# (ragged: the launches of a level whose maps are not made of full 16 x 32 tiles -- None: the format takes no such level)
+_Format = namedtuple("_Format", "operands parts pack layer_ok act act_pool head magnitude trace_pool ragged", defaults=(None,))
+_Ragged = namedtuple("_Ragged", "act act_pool head plain")
+_RAGGED = _Ragged(ops.conv3x3_plain16_pre_act_ragged, ops.conv3x3_plain16_pre_act_pool_ragged, ops.conv3x3_plain16_pre_head_ragged,
+                  ops.conv3x3_plain16_pre_plain_ragged)
 
 
 def _format():
-    """The format Settings.fused_eval selects: fp16 (hi | mid) parts, or one part of plain bf16 ("bf16")"""
+    """The format Settings.fused_eval selects: fp16 (hi | mid) parts, or one part of plain bf16 ("bf16"; "bf16+pool+ragged": with the
+    ragged launches and their wider layer predicate)"""
     name = ops.fused_eval_operands()
     if name == "bf16":
         # (trace_pool: the one-part plan's trace is complete -- every convolution's exact input can be rebuilt)
-        return _Format(name, 1, "plain16", ops.eval_layer_ok_bf16, ops.conv3x3_plain16_pre_act, ops.conv3x3_plain16_pre_act_pool,
-                       ops.conv3x3_plain16_pre_head, False, True)
+        rag = ops.fused_eval_ragged()
+        return _Format(name, 1, "plain16", ops.eval_layer_ok_ragged if rag else ops.eval_layer_ok_bf16, ops.conv3x3_plain16_pre_act,
+                       ops.conv3x3_plain16_pre_act_pool, ops.conv3x3_plain16_pre_head, False, True, _RAGGED if rag else None)
     return _Format(name, 2, "split", ops.eval_layer_ok, ops.conv3x3_split_pre_act, ops.conv3x3_split_pre_act_pool, ops.conv3x3_split_pre_head,
                    True, False)
 
@@ -129,7 +143,14 @@ def _depth(units, ups, layer_ok, N, H, W):
         h, w = H >> k, W >> k
         for name, conv, _ in e + d:
             if not layer_ok(N, conv.in_channels, conv.out_channels, h, w):
-                return k, f"level {k}: {name} ({conv.in_channels} -> {conv.out_channels} on {N} maps of {h} x {w}) is outside ops.{layer_ok.__name__}"
+                # (on a map made of full tiles, or no wider than 16 pixels, the ragged predicate IS eval_layer_ok_bf16, and the reason
+                # says so: the answer of "bf16+pool")
+                ragged = layer_ok is ops.eval_layer_ok_ragged and w > 16 and not ops.full_tiles(h, w)
+                ok_name = layer_ok.__name__ if ragged or layer_ok is not ops.eval_layer_ok_ragged else ops.eval_layer_ok_bf16.__name__
+                why = f"level {k}: {name} ({conv.in_channels} -> {conv.out_channels} on {N} maps of {h} x {w}) is outside ops.{ok_name}"
+                if ragged and (w % 4 or h % 2):
+                    why += f": W = {w} must be a multiple of 4 and H = {h} even"
+                return k, why
         if k < 4:
             C, up = e[-1][1].out_channels, ups[k].up
             if C % 32 or d[0][1].in_channels != C + up.out_channels or up.out_channels % 8:
@@ -153,8 +174,11 @@ def _check_head(head):
 _Unit = namedtuple("_Unit", "name conv bn kind keep_fp32")
 # One level: its encoder and decoder units in execution order, the ConvTranspose2d that fills its concat buffer with its kind ("slots":
 # from the slots of the level below; "fp32->slots": from an fp32 tensor; level 4 has none), and whether the pooled tensor leaves as
-# slots (fp32: for the fall-back levels)
-_Level = namedtuple("_Level", "enc dec up convt pooled_slots")
+# slots (fp32: for the fall-back levels); ragged: the level's maps are not made of full tiles, its units take the format's ragged
+# launches; route: the launch(es) behind `convt` -- "slots" / "slots_ragged" (the slot-operand GEMM, on maps with h w % 128 != 0 its ragged
+# entry), "gemm" (the fp32-operand GEMM that writes slots) / "pack" (where that GEMM does not take the map, h w % 128 != 0: the general
+# ConvTranspose2d into an fp32 tensor, then one conversion pass into the concat buffer's up-sampled groups)
+_Level = namedtuple("_Level", "enc dec up convt pooled_slots ragged route", defaults=(False, None))
 # One U-Net pass.  reason: why the plan does not run (None: it runs); static: the part of it that holds whatever the input;
 # levels 0 .. depth - 1 are fused, fallback_reason says why level `depth` is not; head: the last unit ends in the head-epilogue launch
 _Plan = namedtuple("_Plan", "fmt batch reason static depth fallback_reason unet levels head", defaults=(None, 0, None, None, (), False))
@@ -179,9 +203,18 @@ def _build_plan(unet, shape, head=None):
         return _Plan(fmt, N, why_d, None, 0, why_d)
     # the ConvTranspose2d of level k reads the output of level k + 1: slots where that level is fused and the slot-operand kernel takes
     # the map, else the fp32 tensor its producer -- the last unit of level k + 1, or the fall-back levels -- leaves
-    convt = ["fallback" if k >= d else
-             "slots" if k + 1 < d and ops.convt_slots_ok(N, up.up.in_channels, up.up.out_channels, H >> (k + 1), W >> (k + 1), parts=fmt.parts) else
-             "fp32->slots" for k, up in enumerate(ups)]
+    def up_edge(k, up):
+        h, w, cin, ct = H >> (k + 1), W >> (k + 1), up.up.in_channels, up.up.out_channels
+        if k >= d:
+            return "fallback", None
+        if k + 1 < d and ops.convt_slots_ok(N, cin, ct, h, w, parts=fmt.parts):
+            return "slots", "slots"
+        if k + 1 < d and fmt.ragged and (h * w) % 128 and ops.convt_slots_ok_ragged(N, cin, ct, h, w):
+            return "slots", "slots_ragged"
+        # (without ragged levels a fused level is made of full 16 x 32 tiles, so the map below it has h w % 128 == 0)
+        return "fp32->slots", ("pack" if fmt.ragged and (h * w) % 128 else "gemm")
+    edges = [up_edge(k, up) for k, up in enumerate(ups)]
+    convt = [e[0] for e in edges]
     with_head = head == "fused" and _head_ok(unet)
     # pooled units: plain convolution + BatchNorm / ReLU / pooling pass writing slots, or -- "+pool" -- all of it in the convolution's launch
     pooled_kind = "fused+pool" if ops.fused_eval_pool() else "two-pass"
@@ -195,7 +228,8 @@ def _build_plan(unet, shape, head=None):
             kind["inc.c1"], kind[dec[-1][0]] = "stem", ("fused+head" if with_head else "plain+head")
         keep = {(dec or e)[-1][0]} if 0 < k < d and convt[k - 1] == "fp32->slots" else ()
         enc_u, dec_u = ([_Unit(name, conv, bn, kind[name], name in keep) for name, conv, bn in us] for us in (e, dec))
-        levels.append(_Level(enc_u, dec_u, ups[k].up if k < 4 else None, convt[k] if k < 4 else None, k + 1 < d))
+        levels.append(_Level(enc_u, dec_u, ups[k].up if k < 4 else None, convt[k] if k < 4 else None, k + 1 < d,
+                             k < d and not ops.full_tiles(H >> k, W >> k), edges[k][1] if k < 4 else None))
     return _Plan(fmt, N, None, None, d, why_d, unet, tuple(levels), with_head)
 
 
@@ -349,25 +383,33 @@ def _stem_unit(fmt, u, x):
     return _T(a0, None, scale0, scale0)
 
 
-def _fused_unit(fmt, u, t):
-    """Conv-BatchNorm-ReLU in one launch, output as slots (+ fp32 when another reader needs it)"""
+def _fused_unit(fmt, u, t, ragged=False):
+    """Conv-BatchNorm-ReLU in one launch, output as slots (+ fp32 when another reader needs it); ragged: by the format's ragged launch"""
     conv = u.conv
     save = _coeffs(u.bn)
     scale = _bound(fmt, conv, save, t)
     B, _, H, _, W, _ = t.P.shape
     amax = ops.new_amax(t.P.device) if fmt.magnitude else None
     a = torch.empty((B, conv.out_channels, H, W), dtype=torch.float32, device=t.P.device) if u.keep_fp32 else None
-    aP = fmt.act(t.P, _wq(fmt, conv), conv.out_channels, save, a=a, **_slot_kw(fmt, t, aP_slots=scale, a_amax=amax))
+    if ragged:
+        aP = fmt.ragged.act(t.P, _wq(fmt, conv), conv.out_channels, save, a=a)
+    else:
+        aP = fmt.act(t.P, _wq(fmt, conv), conv.out_channels, save, a=a, **_slot_kw(fmt, t, aP_slots=scale, a_amax=amax))
     if aP is None:
         raise RuntimeError(f"onet_amd: the fused eval kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
     return _T(aP, a, scale, amax)
 
 
-def _plain_conv(fmt, conv, t):
+def _plain_conv(fmt, conv, t, ragged=False):
+    if ragged:
+        z = fmt.ragged.plain(t.P, _wq(fmt, conv), conv.out_channels)
+        if z is None:
+            raise RuntimeError(f"onet_amd: the ragged convolution refused a shape ops.{fmt.layer_ok.__name__} accepted")
+        return z
     return ops.conv3x3_split_pre(t.P, _wq(fmt, conv), conv.out_channels, **_slot_kw(fmt, t))
 
 
-def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots):
+def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots, ragged=False):
     """An encoder block's second unit, which writes the skip slots into the concat buffer, the pooled tensor (slots, or fp32 for a
     fall-back level) and -- level 0 -- the fp32 tensor the caller receives.  "two-pass": plain convolution, then ONE BatchNorm + ReLU +
     2 x 2 max-pooling pass; "fused+pool": all of it in the convolution's launch, the same bits (no exact maximum is taken from it: the
@@ -376,11 +418,14 @@ def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots):
     scale = _bound(fmt, u.conv, save, t)
     B, _, H, _, W, _ = t.P.shape
     C, dev = u.conv.out_channels, t.P.device
-    z = None if u.kind == "fused+pool" else _plain_conv(fmt, u.conv, t)
+    z = None if u.kind == "fused+pool" else _plain_conv(fmt, u.conv, t, ragged)
     L = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if want_L else None
     yP = ops.p16_empty(B, C, H // 2, W // 2, dev, parts=fmt.parts) if pooled_slots else None
     yF = None if pooled_slots else torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=dev)
-    if z is None:
+    if z is None and ragged:
+        if fmt.ragged.act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF) is None:
+            raise RuntimeError(f"onet_amd: the ragged pooling kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
+    elif z is None:
         if fmt.act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, aP_slots=scale)) is None:
             raise RuntimeError(f"onet_amd: the fused pooling kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
     elif not ops.bn_relu_apply_pool_split(z, save, skipP, L, yP, yF, slots=scale):
@@ -390,21 +435,34 @@ def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots):
     return _T(skipP, None, scale, scale), _T(yP, yF, scale, scale), L
 
 
-def _conv_t(fmt, up, t, catP, C2):
-    """ConvTranspose2d(k=2, s=2) + bias into the up-sampled channel groups of the pre-split concat buffer -> their magnitude slots
-    (None on a format without: the weight pack of that many parts, no slots on either side)"""
+def _conv_t(fmt, lv, t, catP, C2):
+    """ConvTranspose2d(k=2, s=2) + bias into the up-sampled channel groups of the pre-split concat buffer, by the launches lv.route names
+    -> their magnitude slots (None on a format without: the weight pack of that many parts, no slots on either side)"""
+    up = lv.up
     Ct = up.out_channels
     s_up = None
     if fmt.magnitude:
         s_up = ops.convT2x2_out_bound(up.weight, up.bias, _amax(t))
     dst = catP[:, C2 // 8:]
     packed = up.packed()
+    if lv.route == "slots_ragged":
+        if not ops.convT2x2_fwd_slots_ragged(t.P, packed.slots(fmt.parts), up.bias, dst, Ct):
+            raise RuntimeError("onet_amd: the ragged slot-operand ConvTranspose2d refused a shape ops.convt_slots_ok_ragged accepted")
+        return s_up
+    if lv.route == "pack":
+        # (the smallest maps of the pass: the general kernel into an fp32 tensor, then one conversion pass -- what the training forward
+        # does where the GEMM's fast path does not take the map)
+        B, _, h, w = t.F.shape
+        y = torch.empty((B, Ct, 2 * h, 2 * w), dtype=torch.float32, device=t.F.device)
+        ops.convT2x2_fwd(t.F, packed[0], up.bias, y, Ct, 0, 0)
+        ops.split_pack_act(y, out=dst, slots=s_up)
+        return s_up
     if t.P is not None and ops.convT2x2_fwd_slots(t.P, packed.slots(fmt.parts), up.bias, dst, Ct, x_slots=t.scale, slots=s_up,
                                                    kind="convt_slot_fwd_kernel"):
         return s_up
     if t.F is None:
         raise RuntimeError("onet_amd: the slot-operand ConvTranspose2d refused a shape ops.convt_slots_ok accepted")
-    # (a fused level is made of full 16 x 32 tiles, so the map below it has h w % 128 == 0: the GEMM's fast path takes it)
+    # (route "gemm": the map has h w % 128 == 0 -- _build_plan -- so the GEMM's fast path takes it)
     if not ops.convT2x2_fwd_p(t.F, packed[0], up.bias, dst, Ct, 0, 0, slots=s_up):
         raise RuntimeError("onet_amd: the ConvTranspose2d GEMM refused the fp32 input of a fused level")
     return s_up
@@ -418,9 +476,12 @@ def _tail(unet, k, xk):
     return ups[k](_tail(unet, k + 1, downs[k](xk)), xk)
 
 
-def _head_unit(fmt, u, t, L):
+def _head_unit(fmt, u, t, L, ragged=False):
     """The last Conv-BatchNorm-ReLU unit with the head's channel product in the epilogue -> V [N, 1, H, W]"""
-    V = fmt.head(t.P, _wq(fmt, u.conv), u.conv.out_channels, _coeffs(u.bn), L, **_slot_kw(fmt, t))
+    if ragged:
+        V = fmt.ragged.head(t.P, _wq(fmt, u.conv), u.conv.out_channels, _coeffs(u.bn), L)
+    else:
+        V = fmt.head(t.P, _wq(fmt, u.conv), u.conv.out_channels, _coeffs(u.bn), L, **_slot_kw(fmt, t))
     if V is None:
         raise RuntimeError("onet_amd: the fused head kernel refused a shape the plan accepted")
     return V
@@ -446,11 +507,11 @@ def _unet_pass_L(plan, x):
             if u.kind == "stem":
                 t = _note(u.name, _stem_unit(fmt, u, x))
             elif u.kind == "fused":
-                t = _note(u.name, _fused_unit(fmt, u, t))
+                t = _note(u.name, _fused_unit(fmt, u, t, lv.ragged))
             else:
                 C = u.conv.out_channels
                 catP[k] = ops.p16_empty(N, C + lv.up.out_channels, H >> k, W >> k, x.device, parts=fmt.parts)
-                skips[k], t, Lk = _pooled_unit(fmt, u, t, catP[k][:, :C // 8], k == 0, lv.pooled_slots)
+                skips[k], t, Lk = _pooled_unit(fmt, u, t, catP[k][:, :C // 8], k == 0, lv.pooled_slots, lv.ragged)
                 _note(u.name, skips[k])
                 if fmt.trace_pool and lv.pooled_slots:
                     _note(_ENC[k] + ".pool", t)
@@ -467,17 +528,17 @@ def _unet_pass_L(plan, x):
             continue
         u1, u2 = lv.dec
         C = lv.enc[-1].conv.out_channels
-        s_up = _conv_t(fmt, lv.up, t, catP[k], C)
+        s_up = _conv_t(fmt, lv, t, catP[k], C)
         cat = _T(catP[k], None, (skips[k].scale, s_up, C), (skips[k].amax, s_up, C)) if fmt.magnitude else _T(catP[k])
         _note(_DEC[k] + ".up", _T(catP[k][:, C // 8:], None, s_up, s_up))
-        t = _note(u1.name, _fused_unit(fmt, u1, cat))
+        t = _note(u1.name, _fused_unit(fmt, u1, cat, lv.ragged))
         catP[k] = None
         if u2.kind == "fused":
-            t = _note(u2.name, _fused_unit(fmt, u2, t))
+            t = _note(u2.name, _fused_unit(fmt, u2, t, lv.ragged))
         elif u2.kind == "fused+head":
-            return L, _head_unit(fmt, u2, t, L)
+            return L, _head_unit(fmt, u2, t, L, lv.ragged)
         else:
-            z, save = _plain_conv(fmt, u2.conv, t), _coeffs(u2.bn)
+            z, save = _plain_conv(fmt, u2.conv, t, lv.ragged), _coeffs(u2.bn)
     return L, z, save
 
 

@@ -65,7 +65,10 @@ class Settings:
                     forward falls back to the default path); "bf16": ONE part of plain bf16 per slot -- the arithmetic conv == "bf16"
                     trains with, a third of the matrix instructions and half the slot bytes -- under any conv with pre-split storage
                     (fused_eval_operands()); "fp16x2+pool" / "bf16+pool": the plan of True / "bf16" with the four encoder units in front
-                    of a max-pool in ONE launch each, the pooling in the convolution's epilogue (fused_eval_pool()) -- the same bits.
+                    of a max-pool in ONE launch each, the pooling in the convolution's epilogue (fused_eval_pool()) -- the same bits;
+                    "bf16+pool+ragged": the plan of "bf16+pool" that also takes levels whose maps are not made of full 16 x 32 tiles
+                    (fused_eval_ragged(), eval_layer_ok_ragged: even H, W % 4 == 0 -- the data sets' 224 x 224 down to its 28-pixel
+                    level); on levels made of full tiles the launches and the bits of "bf16+pool".
                     Any other string is a ValueError where the setting is read"""
     __slots__ = ("conv", "twin", "convt_bf16", "lazy_nan", "split", "bn_on_load", "split_f16", "grad_f16", "split_dgrad",
                  "stem_fused", "sync_bn", "presplit", "z_bf16", "fused_eval")
@@ -163,10 +166,11 @@ def presplit():
     return split_enabled() and conv_algo() in ("auto", "split") and split_f16() and split_dgrad()
 
 
-# The string values of Settings.fused_eval -> (slot format, pooled units in one launch); True is ("fp16x2", False)
-_FUSED_EVAL_VALUES = {"bf16": ("bf16", False), "fp16x2+pool": ("fp16x2", True), "bf16+pool": ("bf16", True)}
+# The string values of Settings.fused_eval -> (slot format, pooled units in one launch[, ragged levels]); True is ("fp16x2", False)
+_FUSED_EVAL_VALUES = {"bf16": ("bf16", False), "fp16x2+pool": ("fp16x2", True), "bf16+pool": ("bf16", True),
+                      "bf16+pool+ragged": ("bf16", True, True)}
 # 1: eval forwards under no_grad take the fused inference plan (Settings.fused_eval); bf16: its one-part plain-bf16 form; either with
-# "+pool" ("fp16x2+pool", "bf16+pool"): the pooled units in one launch
+# "+pool" ("fp16x2+pool", "bf16+pool"): the pooled units in one launch; "bf16+pool+ragged": ... on maps not made of full tiles too
 FUSED_EVAL = _FLAGS["FUSED_EVAL"] if _FLAGS.get("FUSED_EVAL") in _FUSED_EVAL_VALUES else _flag("FUSED_EVAL", False)
 
 
@@ -194,6 +198,12 @@ def fused_eval_pool():
     """Does the fused eval plan run a unit in front of a max-pool as ONE launch, the pooling in the convolution's epilogue
     (Settings.fused_eval = "fp16x2+pool" | "bf16+pool": conv3x3_*_pre_act_pool)?"""
     return _fused_eval_value()[1]
+
+
+def fused_eval_ragged():
+    """Does the fused eval plan take levels whose maps are not made of full 16 x 32 tiles (Settings.fused_eval = "bf16+pool+ragged":
+    the *_ragged entry points of include/onet_hip_ragged.h, layer predicate eval_layer_ok_ragged)?"""
+    return len(_fused_eval_value()) > 2
 
 
 Z_BF16 = _flag("Z_BF16", True)       # BASELINE configs[2] (conv == "bf16", pre-split operands): conv outputs stored as bf16 (Settings.z_bf16)
@@ -628,6 +638,28 @@ def convT2x2_fwd_slots(xP, wP, bias, outP, Ct, x_slots=None, slots=None, kind="c
     _prof_end(kind, flops if rc == 0 else 0.0, e0, nb if rc == 0 else 0.0)
     if rc < 0:
         raise _lib.OnetHipError(f"onet_convT2x2_fwd_slots failed ({rc}): {_lib.last_error()}")
+    return rc == 0
+
+
+def convt_slots_ok_ragged(B, Cin, Ct, h, w):
+    """convt_slots_ok(parts = 1) without h w % 128 == 0: onet_convT2x2_fwd_slots_ragged's predicate (pixel tiles counted per image)."""
+    return bool(CONVT_SLOTS and presplit() and CONVT_BF16 and Cin % 32 == 0 and Cin >= 128 and Ct % 32 == 0 and w % 2 == 0
+                and Cin * h * w * 2 < 2 ** 31)
+
+
+def convT2x2_fwd_slots_ragged(xP, wP, bias, outP, Ct, kind="convt_slot_fwd_kernel"):
+    """convT2x2_fwd_slots on one-part bf16 slots whose map has h w % 128 != 0 (any map of even w qualifies): the pixels of the map,
+    value for value, as convT2x2_fwd_slots writes them on the map with zero rows appended.  -> False where the kernel does not take the
+    shape (nothing written)."""
+    B, C8, h, parts, w, _ = xP.shape
+    assert parts == 1 and outP.shape[3] == 1 and outP.shape[2] == 2 * h and outP.shape[4] == 2 * w and xP.dtype == wP.dtype == outP.dtype == BF
+    Cin = C8 * 8
+    e0 = _prof_begin(kind)
+    rc = _lib.load().onet_convT2x2_fwd_slots_ragged(_p(xP), _pbs(xP), _p(wP), _p(bias), _p(outP), _pbs(outP), B, Cin, Ct, h, w, _stream())
+    flops, nb = 2.0 * B * h * w * Cin * 4 * Ct, 2.0 * (B * h * w * (Cin + 4 * Ct) + 4 * Cin * Ct)
+    _prof_end(kind, flops if rc == 0 else 0.0, e0, nb if rc == 0 else 0.0)
+    if rc < 0:
+        raise _lib.OnetHipError(f"onet_convT2x2_fwd_slots_ragged failed ({rc}): {_lib.last_error()}")
     return rc == 0
 
 
@@ -1238,13 +1270,48 @@ def eval_layer_ok_bf16(B, Cin, Cout, H, W):
     return B * (H // 16) * (W // 32) * (Cout // 64) >= (n_cu() * 3) // 4
 
 
-def _pre_act(entry, kind, two, cin_mult, xs, wq, Cout, save, out, a_amax, a, extra_in, extra_out, pooled=None):
+def full_tiles(H, W):
+    """Is an H x W map made of full 16 x 32 tiles -- the domain of the fused eval entry points without `_ragged`?"""
+    return W >= 32 and W % 32 == 0 and H % 16 == 0
+
+
+def _ragged_map(H, W):
+    """The maps the *_ragged entry points take (include/onet_hip_ragged.h)"""
+    return H > 0 and W > 0 and H % 2 == 0 and W % 4 == 0 and H * W < 2 ** 24
+
+
+# The narrowest map that is not made of full tiles which eval_layer_ok_ragged takes (ONET_FLAGS / tools: 32, 64, 128 leave the 28-, 56-,
+# 112-pixel level of a 224 x 224 input to the fall-back -- tools/time_ragged_eval.py times the plan level by level with it)
+RAGGED_MIN_W = int(_FLAGS.get("RAGGED_MIN_W", 20))
+
+
+def eval_layer_ok_ragged(B, Cin, Cout, H, W):
+    """eval_layer_ok_bf16 for Settings.fused_eval = "bf16+pool+ragged": the domain of onet_conv3x3_plain16_fwd_pre_act_ragged -- even H
+    and W (every fused level is then pooled and up-sampled without pad offsets, and a 2 x 2 window never straddles the map's edge),
+    W % 4 == 0 (the float4 accesses of L, z and the fp32 activation), Cin % 32 == 0, Cout % 64 == 0, inside the buffer-resource range,
+    with pre-split storage on.  conv in ("bf16", "split"): every such layer; otherwise conv3x3_algo's fill rule on the tile counts the
+    kernel walks (cdiv: a partly filled tile occupies a compute unit like a full one).  On a map made of full tiles the answer is
+    eval_layer_ok_bf16's.  Narrower than the entry points' domain by one rule: W >= RAGGED_MIN_W = 20, that is W > 16 -- a map 16 pixels
+    wide or narrower fills at most half of every tile's columns (the existing dispatch's own special case: image pairs), is left to the
+    fall-back levels, and so the plan of an input made of full tiles (256 x 256: its 16-pixel level) stays the plan of "bf16+pool"."""
+    if not presplit():
+        return False
+    if Cin % 32 or Cout % 64 or W <= 16 or not _ragged_map(H, W) or not _in_buffer_range(Cin, Cout, H, W):
+        return False
+    if W < RAGGED_MIN_W and not full_tiles(H, W):
+        return False
+    if conv_algo() in ("bf16", "split"):
+        return True
+    return B * -(-H // 16) * -(-W // 32) * (Cout // 64) >= (n_cu() * 3) // 4
+
+
+def _pre_act(entry, kind, two, cin_mult, xs, wq, Cout, save, out, a_amax, a, extra_in, extra_out, pooled=None, ragged=False):
     """pooled: (yP, y) of the _pool entries -- the pooled slots and / or the pooled fp32 tensor, at least one"""
     B, C8, H, _, W, _ = xs.shape
     Cin = C8 * 8
     if pooled is not None and pooled[0] is None and pooled[1] is None:
         raise ValueError(f"{entry[len('onet_'):]}: a pooled destination is required (yP, y or both)")
-    if W < 32 or W % 32 or H % 16 or Cin % cin_mult or Cout % 64:
+    if not (_ragged_map(H, W) if ragged else full_tiles(H, W)) or Cin % cin_mult or Cout % 64:
         return None
     if out is None:
         out = p16_empty(B, Cout, H, W, xs.device, parts=two)
@@ -1273,6 +1340,45 @@ def conv3x3_plain16_pre_act(xs, wq, Cout, save, out=None, a_amax=None, a=None):
     if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
         raise TypeError("conv3x3_plain16_pre_act: xs and wq must be one-part bf16 packs on the GPU")
     return _pre_act("onet_conv3x3_plain16_fwd_pre_act", "conv3x3_pre16_act_kernel", 1, 32, xs, wq, Cout, save, out, a_amax, a, (), ())
+
+
+def conv3x3_plain16_pre_act_ragged(xs, wq, Cout, save, out=None, a=None):
+    """conv3x3_plain16_pre_act on a ragged map (even H, W % 4 == 0; onet_conv3x3_plain16_fwd_pre_act_ragged): on the map, value for value,
+    what conv3x3_plain16_pre_act writes on the map zero-padded to whole 16 x 32 tiles; nothing outside the map is written.  No exact
+    maximum is recorded.  -> aP, or None where the kernel does not take the shape (nothing launched)."""
+    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
+        raise TypeError("conv3x3_plain16_pre_act_ragged: xs and wq must be one-part bf16 packs on the GPU")
+    return _pre_act("onet_conv3x3_plain16_fwd_pre_act_ragged", "conv3x3_pre16_act_kernel", 1, 32, xs, wq, Cout, save, out, None, a, (), (), ragged=True)
+
+
+def conv3x3_plain16_pre_act_pool_ragged(xs, wq, Cout, save, out=None, a=None, yP=None, y=None):
+    """conv3x3_plain16_pre_act_pool on a ragged map (conv3x3_plain16_pre_act_ragged's domain): the pooled maps are H / 2 x W / 2.
+    -> aP, or None (nothing launched)."""
+    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
+        raise TypeError("conv3x3_plain16_pre_act_pool_ragged: xs and wq must be one-part bf16 packs on the GPU")
+    return _pre_act("onet_conv3x3_plain16_fwd_pre_act_pool_ragged", "conv3x3_pre16_act_pool_kernel", 1, 32, xs, wq, Cout, save, out, None, a, (), (),
+                    pooled=(yP, y), ragged=True)
+
+
+def conv3x3_plain16_pre_plain_ragged(xs, wq, Cout, out=None):
+    """z = conv3x3 (fp32) of one-part bf16 slots on a ragged map (conv3x3_plain16_pre_act_ragged's domain): conv3x3_split_pre's launch
+    there.  -> z, or None (nothing launched)."""
+    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
+        raise TypeError("conv3x3_plain16_pre_plain_ragged: xs and wq must be one-part bf16 packs on the GPU")
+    B, C8, H, _, W, _ = xs.shape
+    Cin = C8 * 8
+    if not _ragged_map(H, W) or Cin % 32 or Cout % 64:
+        return None
+    if out is None:
+        out = torch.empty((B, Cout, H, W), dtype=F32, device=xs.device)
+    e0 = _prof_begin("conv3x3_split_pre_kernel")
+    rc = _lib.load().onet_conv3x3_plain16_fwd_pre_plain_ragged(_p(xs), _pbs(xs), _p(wq), _p(out), out.stride(0) if B > 1 else Cout * H * W, B, Cin,
+                                                               Cout, H, W, _stream())
+    _prof_end("conv3x3_split_pre_kernel", 2.0 * B * H * W * Cin * Cout * 9 if rc == 0 else 0.0, e0,
+              (B * H * W * (2.0 * Cin + 4.0 * Cout) + 2.0 * 9 * Cin * Cout) if rc == 0 else 0.0)
+    if rc < 0:
+        raise _lib.OnetHipError(f"onet_conv3x3_plain16_fwd_pre_plain_ragged failed ({rc}): {_lib.last_error()}")
+    return out if rc == 0 else None
 
 
 def conv3x3_plain16_pre_act_pool(xs, wq, Cout, save, out=None, a_amax=None, a=None, yP=None, y=None):
@@ -1350,6 +1456,14 @@ def conv3x3_plain16_pre_head(xs, wq, Cout, save, L, out=None):
     if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
         raise TypeError("conv3x3_plain16_pre_head: xs and wq must be one-part bf16 packs on the GPU")
     return _pre_head("onet_conv3x3_plain16_fwd_pre_head", "conv3x3_pre16_head_kernel", 1, xs, wq, Cout, save, L, out, ())
+
+
+def conv3x3_plain16_pre_head_ragged(xs, wq, Cout, save, L, out=None):
+    """conv3x3_plain16_pre_head on a ragged map (conv3x3_plain16_pre_act_ragged's domain, Cout == 64).  -> V, or None (nothing launched,
+    nothing written)."""
+    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
+        raise TypeError("conv3x3_plain16_pre_head_ragged: xs and wq must be one-part bf16 packs on the GPU")
+    return _pre_head("onet_conv3x3_plain16_fwd_pre_head_ragged", "conv3x3_pre16_head_kernel", 1, xs, wq, Cout, save, L, out, ())
 
 
 def conv3x3_split_pre_head(xs, wq, Cout, save, L, out=None, slots=None, slots2=None, split_ch=0):
