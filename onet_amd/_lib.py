@@ -1,5 +1,5 @@
 """ctypes binding of libonet_hip.so (C ABI: include/onet_hip.h, include/onet_hip_eval.h for the validation step and
-include/onet_hip_ragged.h for the eval plan on ragged maps).
+include/onet_hip_ragged.h / include/onet_hip_ragged_split.h for the one-part / fp16 two-part eval plan on ragged maps).
 
 The prototypes are PARSED from the header, so the Python side cannot drift from
 the ABI.  There is no CPU fallback: if the library cannot be loaded (or built),
@@ -17,6 +17,8 @@ EVAL_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_eval.h")
 # ONET_HIP_LIB: another build of the same library (onet_amd.build --variant ...) for same-box A/B runs
 # the ragged-map entry points of the one-part eval plan (Settings.fused_eval = "bf16+pool+ragged"): likewise
 RAGGED_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_ragged.h")
+# ... and of the fp16 (hi | mid) plan (Settings.fused_eval = "fp16x2+ragged")
+RAGGED_SPLIT_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_ragged_split.h")
 LIBPATH = os.environ.get("ONET_HIP_LIB") or os.path.join(HERE, "libonet_hip.so")
 
 _CT = {
@@ -75,7 +77,7 @@ def load(build_if_missing: bool = True):
         _build.build()
     lib = ctypes.CDLL(LIBPATH)
     _protos = {}
-    for header in (HEADER, EVAL_HEADER, RAGGED_HEADER):
+    for header in (HEADER, EVAL_HEADER, RAGGED_HEADER, RAGGED_SPLIT_HEADER):
         protos = parse_header(header)
         for name, (restype, argtypes, _) in protos.items():
             try:

@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include "common.hpp"
 #include "../../include/onet_hip_ragged.h"
+#include "../../include/onet_hip_ragged_split.h"
 
 using namespace onet;
 
@@ -709,9 +710,15 @@ template <bool W16> struct SpPreCfg {
 template <int CTRL> __device__ __forceinline__ float dpp_max(float x) {     // max(x, x of the lane DPP control CTRL selects)
     return fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false)));
 }
-template <bool ST, int PM, bool W16, bool ACT = false, bool POOL = false>
+// RAG (round 14, the fp16 ragged entries of include/onet_hip_ragged_split.h): the activation epilogue on maps that are not made of full
+// tiles.  The staging (the out-of-range offset), the tile counts (cdiv) and every store (yo < H && xo < W; the pooled ones: pst) already
+// are ragged-ready, and both lane exchanges (v_permlane32_swap, the pooling's DPP step) run outside those guards, in every lane.  What
+// needs code is the exact-maximum record (act_amax): an out-of-map accumulator is relu(bn(.)) of a partial or empty sum -- not zero --
+// and must not enter the maximum the next layer's bound starts from.
+template <bool ST, int PM, bool W16, bool ACT = false, bool POOL = false, bool RAG = false>
 __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void conv3x3_split_pre_kernel(SpPreArgs a) {
     constexpr bool F16 = PM == 1;
+    static_assert(!RAG || ACT, "conv3x3_split_pre_kernel: the ragged instance is the activation epilogue's (masked exact maximum)");
     static_assert(!ACT || (PM == 1 && !ST && !W16), "conv3x3_split_pre_kernel: the activation epilogue goes with the fp16 slot store");
     static_assert(!POOL || ACT, "conv3x3_split_pre_kernel: the pooled stores ride on the activation epilogue");
     using C = SpPreCfg<W16>;
@@ -987,6 +994,11 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
             // acc[m][n] is channel m 32 + 8 (r / 4) + 4 kh + r % 4 of the tile: four consecutive floats per coefficient and group
             const float* cf = act_cf + cf_par * 192;
             float vmax = 0.f;
+            [[maybe_unused]] float vrow[NT];                      // RAG: the maximum per row n (the lane's pixel column is fixed)
+            if constexpr (RAG) {
+#pragma unroll
+                for (int n = 0; n < NT; ++n) vrow[n] = 0.f;
+            }
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -1001,9 +1013,16 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
                         for (int j = 0; j < 4; ++j) {
                             const float v = fmaxf(fmaf(acc[m][n][4 * g + j] - mean[j], sc[j], sh[j]), 0.f);
                             acc[m][n][4 * g + j] = v;
-                            vmax = fmaxf(vmax, v);
+                            if constexpr (RAG) vrow[n] = fmaxf(vrow[n], v);
+                            else vmax = fmaxf(vmax, v);
                         }
                 }
+            if constexpr (RAG) {
+                // only the map's own pixels: one predicate per row (a.act_a's and the slot stores' guard)
+#pragma unroll
+                for (int n = 0; n < NT; ++n)
+                    if (y0 + wn * NT + n < a.H && xo < a.W) vmax = fmaxf(vmax, vrow[n]);
+            }
             if (a.act_amax) {
                 // the exact maximum of what this wave wrote: one atomicMax on the fp32 bit pattern per wave and tile
 #pragma unroll
@@ -1780,9 +1799,8 @@ int launch_split_pre(SpPreArgs a, hipStream_t st) {
     // level (that instance of the new kernel exceeds the register budget).  The head epilogue exists on the 16x16x32 kernel alone.
     constexpr bool P16 = RD || PM == 2 || (ST && !W16) || HEAD;
     void (*kern)(SpPreArgs);
-    static_assert(!RAG || P16, "launch_split_pre: the ragged instance exists on the 16x16x32 kernel alone");
     if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD, ACT, HEAD, POOL, RAG>;      // (constexpr: the instances not dispatched are not built)
-    else kern = conv3x3_split_pre_kernel<ST, PM, W16, ACT, POOL>;
+    else kern = conv3x3_split_pre_kernel<ST, PM, W16, ACT, POOL, RAG>;
     static PerDeviceOnce attr_once;
     return sp_launch_persistent(kern, attr_once, LDS_BYTES, tiles, C::NW * 64,
                                 HEAD   ? (PM == 2 ? "conv3x3_pre16_head_kernel" : "conv3x3_split_pre_head_kernel")
@@ -2711,16 +2729,17 @@ int onet_conv3x3_split_dgrad_pre_slots(const void* dzs, int64_t dzs_bs, const vo
 // guard rule from the bound aP_slots holds BEFORE the launch (onet_conv3x3_act_bound).  Bit for bit what the plain launch followed by
 // onet_bn_relu_apply_split(z, save, slots = aP_slots) writes; z itself is never stored.  Returns 1 (nothing launched) where the map is
 // not made of full 16 x 32 tiles or Cout is not a multiple of 64.
-int onet_conv3x3_split_fwd_pre_act(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
-                                   const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
-                                   int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
-    ONET_REQUIRE(xs && wq && save && aP && aP_slots, "conv3x3_split_fwd_pre_act: null pointer");
-    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv3x3_split_fwd_pre_act: bad shape");
-    if (W < 32 || (W % 32) || (H % 16) || (Cin % 16) || (Cout % 64)) return 1;
-    ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "conv3x3_split_fwd_pre_act: split_ch must be a multiple of 32 inside Cin");
-    if (const int rc = pre_operand_checks("conv3x3_split_fwd_pre_act", xs, xs_bs, 1, Cin, Cout, H, W)) return rc;
-    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "conv3x3_split_fwd_pre_act: 16-byte aligned slots required");
-    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W && (!a || a_bs >= (int64_t)Cout * H * W), "conv3x3_split_fwd_pre_act: batch stride too small");
+static bool pre_map_ok(bool ragged, int H, int W);
+static int split_pre_act_impl(const char* entry, bool ragged, const void* xs, int64_t xs_bs, const void* x_amax, int scale_always,
+                              const void* x_amax2, int split_ch, const void* wq, const float* save, void* aP, int64_t aP_bs,
+                              const void* aP_slots, void* a_amax, float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    ONET_REQUIRE(xs && wq && save && aP && aP_slots, "%s: null pointer", entry);
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
+    if (!pre_map_ok(ragged, H, W) || (Cin % 16) || (Cout % 64)) return 1;
+    ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
+    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 1, Cin, Cout, H, W)) return rc;
+    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "%s: 16-byte aligned slots required", entry);
+    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W && (!a || a_bs >= (int64_t)Cout * H * W), "%s: batch stride too small", entry);
     SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)x_amax, scale_always,
                 (const unsigned*)x_amax2, split_ch};
     p.zP = aP;
@@ -2731,7 +2750,44 @@ int onet_conv3x3_split_fwd_pre_act(const void* xs, int64_t xs_bs, const void* x_
     p.act_amax = (unsigned*)a_amax;
     p.act_a = a;
     p.act_a_bs = a_bs;
+    // a map of full tiles takes the full-tile instance from either entry: the same launch, the same bits
+    if (ragged && !pre_map_ok(false, H, W)) return launch_split_pre<false, 1, false, false, true, false, false, true>(p, as_stream(stream));
     return launch_split_pre<false, 1, false, false, true>(p, as_stream(stream));
+}
+
+int onet_conv3x3_split_fwd_pre_act(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
+                                   const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
+                                   int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    return split_pre_act_impl("conv3x3_split_fwd_pre_act", false, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, aP, aP_bs, aP_slots,
+                              a_amax, a, a_bs, B, Cin, Cout, H, W, stream);
+}
+
+// ... on a ragged map (pre_map_ok; include/onet_hip_ragged_split.h): the full-tile entry on the map zero-padded to whole tiles, value for
+// value on the map, nothing written outside it; a_amax receives the maximum over the MAP's pixels (the RAG instance's masked record).
+// Returns 1 (nothing launched) for odd H, W % 4, Cin % 16 or Cout % 64.
+int onet_conv3x3_split_fwd_pre_act_ragged(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
+                                          const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
+                                          int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    return split_pre_act_impl("conv3x3_split_fwd_pre_act_ragged", true, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, aP, aP_bs,
+                              aP_slots, a_amax, a, a_bs, B, Cin, Cout, H, W, stream);
+}
+
+// The plain forward of onet_conv3x3_split_fwd_pre(wq_f16 = 1, fp32 z, no statistics) on a ragged map: the fp16 plan's last unit where
+// no head epilogue follows.  x_amax / scale_always / x_amax2 / split_ch: the operand's magnitude slots, as there.  Returns 1 (nothing
+// launched) outside the ragged domain.
+int onet_conv3x3_split_fwd_pre_plain_ragged(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
+                                            const void* wq, float* z, int64_t z_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    const char* entry = "conv3x3_split_fwd_pre_plain_ragged";
+    ONET_REQUIRE(xs && wq && z, "%s: null pointer", entry);
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
+    if (!pre_map_ok(true, H, W) || (Cin % 16) || (Cout % 64)) return 1;
+    ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
+    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 1, Cin, Cout, H, W)) return rc;
+    ONET_REQUIRE((z_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0, "%s: 16-byte aligned rows required", entry);
+    ONET_REQUIRE(z_bs >= (int64_t)Cout * H * W, "%s: batch stride too small", entry);
+    SpPreArgs a{xs, xs_bs, (const __bf16*)wq, z, z_bs, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)x_amax, scale_always,
+                (const unsigned*)x_amax2, split_ch};
+    return launch_split_pre<false, 1, false>(a, as_stream(stream));
 }
 
 // Eval-mode inference on PLAIN bf16 operands (one part, unscaled: bf16 has fp32's exponent range, so no magnitude slots, bound or guard):
@@ -2742,7 +2798,8 @@ int onet_conv3x3_split_fwd_pre_act(const void* xs, int64_t xs_bs, const void* x_
 // onet_bn_relu_apply_split(nparts = 1) writes; z itself is never stored.  Returns 1 (nothing launched) where the map is not made of full
 // 16 x 32 tiles, Cin is not a multiple of 32 or Cout not one of 64.
 // The maps an eval-mode entry takes: made of full 16 x 32 tiles, or -- the _ragged entries of include/onet_hip_ragged.h (round 13,
-// one-part operands only) -- any map of even H and W % 4 == 0 below 2^24 pixels: the tile counts are cdiv, the staging gives every
+// one-part operands) and include/onet_hip_ragged_split.h (round 14, fp16 hi | mid parts) -- any map of even H and W % 4 == 0 below
+// 2^24 pixels: the tile counts are cdiv, the staging gives every
 // out-of-map slot the out-of-range offset and every store is guarded per slot / float4 / pooled float2.  With H and W even and tiles
 // starting on even coordinates a 2 x 2 pooling window is wholly inside the map or wholly outside.
 static bool pre_map_ok(bool ragged, int H, int W) {
@@ -2815,8 +2872,8 @@ static int pre_act_pool_impl(const char* entry, bool ragged, int wq_f16, const v
     ONET_REQUIRE(yP || y, "%s: a pooled destination is required (yP, y or both)", entry);
     ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
     if (!pre_map_ok(ragged, H, W) || (Cin % (wq_f16 == 2 ? 32 : 16)) || (Cout % 64)) return 1;
-    ONET_REQUIRE(!ragged || wq_f16 == 2, "%s: the ragged entry takes one-part operands", entry);
-    ONET_RAGGED_NO_AMAX(entry, ragged, a_amax);
+    // (the one-part ragged instance records no maximum; the fp16 one -- round 14 -- masks its record to the map)
+    ONET_RAGGED_NO_AMAX(entry, ragged && wq_f16 == 2, a_amax);
     ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
     if (const int rc = pre_operand_checks(entry, xs, xs_bs, wq_f16, Cin, Cout, H, W)) return rc;
     const int64_t n = (int64_t)Cout * H * W, per = wq_f16 == 2 ? 2 : 1;       // slot elements per 4-byte unit: one bf16 part / two fp16 parts
@@ -2840,7 +2897,10 @@ static int pre_act_pool_impl(const char* entry, bool ragged, int wq_f16, const v
     p.pl_y = y;
     p.pl_y_bs = y_bs;
     // a map of full tiles takes the full-tile instance from either entry: the same launch, the same bits
-    if (ragged && !pre_map_ok(false, H, W)) return launch_split_pre<false, 2, false, false, true, false, true, true>(p, as_stream(stream));
+    if (ragged && !pre_map_ok(false, H, W)) {
+        if (wq_f16 == 2) return launch_split_pre<false, 2, false, false, true, false, true, true>(p, as_stream(stream));
+        return launch_split_pre<false, 1, false, false, true, false, true, true>(p, as_stream(stream));
+    }
     if (wq_f16 == 2) return launch_split_pre<false, 2, false, false, true, false, true>(p, as_stream(stream));
     return launch_split_pre<false, 1, false, false, true, false, true>(p, as_stream(stream));
 }
@@ -2866,6 +2926,15 @@ int onet_conv3x3_split_fwd_pre_act_pool(const void* xs, int64_t xs_bs, const voi
                                         void* stream) {
     return pre_act_pool_impl("conv3x3_split_fwd_pre_act_pool", false, 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, aP, aP_bs, aP_slots,
                              a_amax, a, a_bs, yP, yP_bs, y, y_bs, B, Cin, Cout, H, W, stream);
+}
+
+// ... on a ragged map (pre_map_ok; H / 2 x W / 2 pooled maps): see onet_conv3x3_split_fwd_pre_act_ragged -- a_amax is taken, masked to the map
+int onet_conv3x3_split_fwd_pre_act_pool_ragged(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2,
+                                               int split_ch, const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots,
+                                               void* a_amax, float* a, int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin,
+                                               int Cout, int H, int W, void* stream) {
+    return pre_act_pool_impl("conv3x3_split_fwd_pre_act_pool_ragged", true, 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, aP, aP_bs,
+                             aP_slots, a_amax, a, a_bs, yP, yP_bs, y, y_bs, B, Cin, Cout, H, W, stream);
 }
 
 // Labels-only inference: the model's LAST unit with the head in the convolution's epilogue (SpPreArgs::hd_*).  The two entries below run
@@ -2910,6 +2979,14 @@ int onet_conv3x3_split_fwd_pre_head(const void* xs, int64_t xs_bs, const void* x
                                     int W, void* stream) {
     return pre_head_impl("conv3x3_split_fwd_pre_head", false, 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, L, L_bs, V, B, Cin, Cout,
                          H, W, stream);
+}
+
+// ... on a ragged map (pre_map_ok): the L loads and the V store are guarded per float4, the staging per slot
+int onet_conv3x3_split_fwd_pre_head_ragged(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
+                                           const void* wq, const float* save, const float* L, int64_t L_bs, float* V, int B, int Cin, int Cout,
+                                           int H, int W, void* stream) {
+    return pre_head_impl("conv3x3_split_fwd_pre_head_ragged", true, 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, L, L_bs, V, B, Cin,
+                         Cout, H, W, stream);
 }
 
 // a[co] = relu(sc (z - mean) + sh) with |z[co]| <= sum_ci |w[co][ci][.]| max |x[ci]|:  |a[co]| <= |sc| (S1 max1 + S2 max2) + |sh - mean sc|,

@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include "common.hpp"
 #include "../../include/onet_hip_ragged.h"
+#include "../../include/onet_hip_ragged_split.h"
 
 using namespace onet;
 
@@ -576,7 +577,9 @@ __device__ __forceinline__ void slot_wait() {
 // RAG (round 13: onet_convT2x2_fwd_slots_ragged, maps with h w % 128 != 0): the pixel tiles are cdiv(h w, 128) PER IMAGE (SArgs::nTiles
 // counts them over the batch), a B-operand slot of a pixel p >= h w takes the out-of-range offset -- the plain arithmetic would alias
 // the next channel group inside the resource -- and the epilogue stores only p < h w.  Pixels are independent GEMM columns: the map's
-// own values are those of the full-tile instance on the map with zero rows appended.
+// own values are those of the full-tile instance on the map with zero rows appended.  NP = 2 (round 14:
+// onet_convT2x2_fwd_slots_split_ragged): the same three rules on both parts of a slot -- the offset of a pixel p >= h w is out of range
+// whatever its part, and the magnitude slots of input and output apply as in the full-tile instance.
 constexpr unsigned SLOT_OOB = 0x80000000u;        // beyond every resource (< 2 GiB, host-checked), chunk steps included
 template <int NP, bool RAG = false>
 __global__ __launch_bounds__(256, SLOT_OCC) void convt_slot_fwd_kernel(SArgs g) {
@@ -1443,6 +1446,27 @@ int onet_convT2x2_fwd_slots_ragged(const void* xP, int64_t xP_bs, const void* wP
     const int64_t blocks = (int64_t)g.mTiles * g.nTiles;
     ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "convT2x2_fwd_slots_ragged: grid too large");
     hipLaunchKernelGGL((convt_slot_fwd_kernel<1, true>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
+    return check_launch("convt_slot_fwd_kernel");
+}
+
+// onet_convT2x2_fwd_slots (nparts = 2: fp16 hi | mid operands with their magnitude slots) on maps whose pixel count is no multiple of 128
+// (include/onet_hip_ragged_split.h): its domain without h w % 128 == 0.  Returns 1 (nothing launched) outside it, nparts = 1 included
+// (onet_convT2x2_fwd_slots_ragged is that entry).  h w % 128 == 0: the launch of onet_convT2x2_fwd_slots.
+int onet_convT2x2_fwd_slots_split_ragged(const void* xP, int64_t xP_bs, const void* x_amax, const void* wP, const float* bias, void* yP,
+                                         int64_t yP_bs, const void* y_amax, int nparts, int B, int Cin, int Ct, int h, int w, void* stream) {
+    ONET_REQUIRE(xP && wP && yP && B > 0 && Cin > 0 && Ct > 0 && h > 0 && w > 0 && (nparts == 1 || nparts == 2), "convT2x2_fwd_slots_split_ragged: bad args");
+    const int64_t hw = (int64_t)h * w;
+    if (nparts != 2 || (Cin % 32) || Cin < 128 || (Ct % 32) || (w & 1) || !aligned16(xP) || !aligned16(wP) || !aligned16(yP) || (xP_bs & 3) ||
+        (yP_bs & 3) || (int64_t)Cin * hw * 4 >= (1ll << 31) || (int64_t)Cin * 4 * Ct * 4 >= (1ll << 31))
+        return 1;
+    ONET_REQUIRE(xP_bs >= (int64_t)Cin * hw && yP_bs >= (int64_t)Ct * 4 * hw, "convT2x2_fwd_slots_split_ragged: batch stride too small");
+    if ((hw % 128) == 0) return onet_convT2x2_fwd_slots(xP, xP_bs, x_amax, wP, bias, yP, yP_bs, y_amax, 2, B, Cin, Ct, h, w, stream);
+    const int64_t ntiles = (int64_t)B * ((hw + 127) / 128);
+    ONET_REQUIRE(ntiles < (1ll << 24), "convT2x2_fwd_slots_split_ragged: grid too large");
+    SArgs g{wP, xP, xP_bs, bias, yP, yP_bs, (const unsigned*)x_amax, (const unsigned*)y_amax, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)ntiles};
+    const int64_t blocks = (int64_t)g.mTiles * g.nTiles;
+    ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "convT2x2_fwd_slots_split_ragged: grid too large");
+    hipLaunchKernelGGL((convt_slot_fwd_kernel<2, true>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
     return check_launch("convt_slot_fwd_kernel");
 }
 

@@ -42,6 +42,13 @@ its route (_Level.route): the slot-operand GEMM or its ragged entry (h w % 128 !
 or, where that does not take the map, the general kernel and one conversion pass.  On a level made of full tiles the launches, their
 order and the bits are those of "bf16+pool".
 
+Settings.fused_eval = "fp16x2+ragged": the plan of "fp16x2+pool" that also takes ragged levels (ops.eval_layer_ok_ragged_fp16; the
+entry points of include/onet_hip_ragged_split.h) -- the fp32-level plan at the data sets' resolution.  Everything said about magnitude
+slots above holds on a ragged level: a fused unit's amax is the EXACT maximum over the map's own pixels (the ragged kernel instance
+masks its record: relu(bn(.)) of an out-of-map accumulator is not zero and would otherwise loosen every later bound), the pooled units
+hand on their bound, the `pack` route's conversion pass writes two parts scaled by the ConvTranspose2d's own bound.  On a level made
+of full tiles the launches, their order and the bits are those of "fp16x2+pool".
+
 The validation step (validate, EvalCounts): the scores of a batch -- by the labels-only plan where it applies, the ordinary forward
 elsewhere -- then ONE launch (ops.score_counts) that forms the labels and adds each image's confusion counts against the ground truth
 into a device tensor; nothing synchronises, and metrics.epoch_metrics turns an epoch's rows into the reference's metrics on the host.
@@ -83,19 +90,21 @@ _Format = namedtuple("_Format", "operands parts pack layer_ok act act_pool head 
 _Ragged = namedtuple("_Ragged", "act act_pool head plain")
 _RAGGED = _Ragged(ops.conv3x3_plain16_pre_act_ragged, ops.conv3x3_plain16_pre_act_pool_ragged, ops.conv3x3_plain16_pre_head_ragged,
                   ops.conv3x3_plain16_pre_plain_ragged)
+_RAGGED_FP16 = _Ragged(ops.conv3x3_split_pre_act_ragged, ops.conv3x3_split_pre_act_pool_ragged, ops.conv3x3_split_pre_head_ragged,
+                       ops.conv3x3_split_pre_plain_ragged)
 
 
 def _format():
-    """The format Settings.fused_eval selects: fp16 (hi | mid) parts, or one part of plain bf16 ("bf16"; "bf16+pool+ragged": with the
-    ragged launches and their wider layer predicate)"""
+    """The format Settings.fused_eval selects: fp16 (hi | mid) parts, or one part of plain bf16 ("bf16"); "bf16+pool+ragged" /
+    "fp16x2+ragged": with the format's ragged launches and their wider layer predicate"""
     name = ops.fused_eval_operands()
+    rag = ops.fused_eval_ragged()
     if name == "bf16":
         # (trace_pool: the one-part plan's trace is complete -- every convolution's exact input can be rebuilt)
-        rag = ops.fused_eval_ragged()
         return _Format(name, 1, "plain16", ops.eval_layer_ok_ragged if rag else ops.eval_layer_ok_bf16, ops.conv3x3_plain16_pre_act,
                        ops.conv3x3_plain16_pre_act_pool, ops.conv3x3_plain16_pre_head, False, True, _RAGGED if rag else None)
-    return _Format(name, 2, "split", ops.eval_layer_ok, ops.conv3x3_split_pre_act, ops.conv3x3_split_pre_act_pool, ops.conv3x3_split_pre_head,
-                   True, False)
+    return _Format(name, 2, "split", ops.eval_layer_ok_ragged_fp16 if rag else ops.eval_layer_ok, ops.conv3x3_split_pre_act,
+                   ops.conv3x3_split_pre_act_pool, ops.conv3x3_split_pre_head, True, False, _RAGGED_FP16 if rag else None)
 
 
 def _static_reason(unet, fmt):
@@ -145,8 +154,9 @@ def _depth(units, ups, layer_ok, N, H, W):
             if not layer_ok(N, conv.in_channels, conv.out_channels, h, w):
                 # (on a map made of full tiles, or no wider than 16 pixels, the ragged predicate IS eval_layer_ok_bf16, and the reason
                 # says so: the answer of "bf16+pool")
-                ragged = layer_ok is ops.eval_layer_ok_ragged and w > 16 and not ops.full_tiles(h, w)
-                ok_name = layer_ok.__name__ if ragged or layer_ok is not ops.eval_layer_ok_ragged else ops.eval_layer_ok_bf16.__name__
+                full = {ops.eval_layer_ok_ragged: ops.eval_layer_ok_bf16, ops.eval_layer_ok_ragged_fp16: ops.eval_layer_ok}.get(layer_ok)
+                ragged = full is not None and w > 16 and not ops.full_tiles(h, w)
+                ok_name = (layer_ok if ragged or full is None else full).__name__
                 why = f"level {k}: {name} ({conv.in_channels} -> {conv.out_channels} on {N} maps of {h} x {w}) is outside ops.{ok_name}"
                 if ragged and (w % 4 or h % 2):
                     why += f": W = {w} must be a multiple of 4 and H = {h} even"
@@ -209,7 +219,7 @@ def _build_plan(unet, shape, head=None):
             return "fallback", None
         if k + 1 < d and ops.convt_slots_ok(N, cin, ct, h, w, parts=fmt.parts):
             return "slots", "slots"
-        if k + 1 < d and fmt.ragged and (h * w) % 128 and ops.convt_slots_ok_ragged(N, cin, ct, h, w):
+        if k + 1 < d and fmt.ragged and (h * w) % 128 and ops.convt_slots_ok_ragged(N, cin, ct, h, w, parts=fmt.parts):
             return "slots", "slots_ragged"
         # (without ragged levels a fused level is made of full 16 x 32 tiles, so the map below it has h w % 128 == 0)
         return "fp32->slots", ("pack" if fmt.ragged and (h * w) % 128 else "gemm")
@@ -391,10 +401,9 @@ def _fused_unit(fmt, u, t, ragged=False):
     B, _, H, _, W, _ = t.P.shape
     amax = ops.new_amax(t.P.device) if fmt.magnitude else None
     a = torch.empty((B, conv.out_channels, H, W), dtype=torch.float32, device=t.P.device) if u.keep_fp32 else None
-    if ragged:
-        aP = fmt.ragged.act(t.P, _wq(fmt, conv), conv.out_channels, save, a=a)
-    else:
-        aP = fmt.act(t.P, _wq(fmt, conv), conv.out_channels, save, a=a, **_slot_kw(fmt, t, aP_slots=scale, a_amax=amax))
+    # (a ragged launch takes its sibling's magnitude-slot arguments: none on the one-part format, whose ragged entries record no maximum)
+    launch = fmt.ragged.act if ragged else fmt.act
+    aP = launch(t.P, _wq(fmt, conv), conv.out_channels, save, a=a, **_slot_kw(fmt, t, aP_slots=scale, a_amax=amax))
     if aP is None:
         raise RuntimeError(f"onet_amd: the fused eval kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
     return _T(aP, a, scale, amax)
@@ -402,7 +411,7 @@ def _fused_unit(fmt, u, t, ragged=False):
 
 def _plain_conv(fmt, conv, t, ragged=False):
     if ragged:
-        z = fmt.ragged.plain(t.P, _wq(fmt, conv), conv.out_channels)
+        z = fmt.ragged.plain(t.P, _wq(fmt, conv), conv.out_channels, **_slot_kw(fmt, t))
         if z is None:
             raise RuntimeError(f"onet_amd: the ragged convolution refused a shape ops.{fmt.layer_ok.__name__} accepted")
         return z
@@ -423,7 +432,7 @@ def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots, ragged=False):
     yP = ops.p16_empty(B, C, H // 2, W // 2, dev, parts=fmt.parts) if pooled_slots else None
     yF = None if pooled_slots else torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=dev)
     if z is None and ragged:
-        if fmt.ragged.act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF) is None:
+        if fmt.ragged.act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, aP_slots=scale)) is None:
             raise RuntimeError(f"onet_amd: the ragged pooling kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
     elif z is None:
         if fmt.act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, aP_slots=scale)) is None:
@@ -446,7 +455,11 @@ def _conv_t(fmt, lv, t, catP, C2):
     dst = catP[:, C2 // 8:]
     packed = up.packed()
     if lv.route == "slots_ragged":
-        if not ops.convT2x2_fwd_slots_ragged(t.P, packed.slots(fmt.parts), up.bias, dst, Ct):
+        if fmt.parts == 2:
+            done = ops.convT2x2_fwd_slots_split_ragged(t.P, packed.slots(2), up.bias, dst, Ct, x_slots=t.scale, slots=s_up)
+        else:
+            done = ops.convT2x2_fwd_slots_ragged(t.P, packed.slots(fmt.parts), up.bias, dst, Ct)
+        if not done:
             raise RuntimeError("onet_amd: the ragged slot-operand ConvTranspose2d refused a shape ops.convt_slots_ok_ragged accepted")
         return s_up
     if lv.route == "pack":
@@ -479,7 +492,7 @@ def _tail(unet, k, xk):
 def _head_unit(fmt, u, t, L, ragged=False):
     """The last Conv-BatchNorm-ReLU unit with the head's channel product in the epilogue -> V [N, 1, H, W]"""
     if ragged:
-        V = fmt.ragged.head(t.P, _wq(fmt, u.conv), u.conv.out_channels, _coeffs(u.bn), L)
+        V = fmt.ragged.head(t.P, _wq(fmt, u.conv), u.conv.out_channels, _coeffs(u.bn), L, **_slot_kw(fmt, t))
     else:
         V = fmt.head(t.P, _wq(fmt, u.conv), u.conv.out_channels, _coeffs(u.bn), L, **_slot_kw(fmt, t))
     if V is None:

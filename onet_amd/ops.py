@@ -69,6 +69,9 @@ class Settings:
                     "bf16+pool+ragged": the plan of "bf16+pool" that also takes levels whose maps are not made of full 16 x 32 tiles
                     (fused_eval_ragged(), eval_layer_ok_ragged: even H, W % 4 == 0 -- the data sets' 224 x 224 down to its 28-pixel
                     level); on levels made of full tiles the launches and the bits of "bf16+pool".
+                    "fp16x2+ragged": the plan of "fp16x2+pool" ("+pool" implied) that also takes such levels, at fp32 level
+                    (eval_layer_ok_ragged_fp16; the exact maxima its bounds start from are taken over the map's own pixels); on
+                    levels made of full tiles the launches and the bits of "fp16x2+pool".
                     Any other string is a ValueError where the setting is read"""
     __slots__ = ("conv", "twin", "convt_bf16", "lazy_nan", "split", "bn_on_load", "split_f16", "grad_f16", "split_dgrad",
                  "stem_fused", "sync_bn", "presplit", "z_bf16", "fused_eval")
@@ -168,9 +171,17 @@ def presplit():
 
 # The string values of Settings.fused_eval -> (slot format, pooled units in one launch[, ragged levels]); True is ("fp16x2", False)
 _FUSED_EVAL_VALUES = {"bf16": ("bf16", False), "fp16x2+pool": ("fp16x2", True), "bf16+pool": ("bf16", True),
-                      "bf16+pool+ragged": ("bf16", True, True)}
+                      "bf16+pool+ragged": ("bf16", True, True), "fp16x2+ragged": ("fp16x2", True, True)}
 # 1: eval forwards under no_grad take the fused inference plan (Settings.fused_eval); bf16: its one-part plain-bf16 form; either with
-# "+pool" ("fp16x2+pool", "bf16+pool"): the pooled units in one launch; "bf16+pool+ragged": ... on maps not made of full tiles too
+# "+pool" ("fp16x2+pool", "bf16+pool"): the pooled units in one launch; "bf16+pool+ragged" / "fp16x2+ragged" ("+pool" implied): ... on
+# maps not made of full tiles too
+#   value                format    pooled units    ragged levels    layer predicate
+#   True                 fp16x2    two passes      no               eval_layer_ok
+#   "fp16x2+pool"        fp16x2    one launch      no               eval_layer_ok
+#   "fp16x2+ragged"      fp16x2    one launch      yes              eval_layer_ok_ragged_fp16
+#   "bf16"               bf16      two passes      no               eval_layer_ok_bf16
+#   "bf16+pool"          bf16      one launch      no               eval_layer_ok_bf16
+#   "bf16+pool+ragged"   bf16      one launch      yes              eval_layer_ok_ragged
 FUSED_EVAL = _FLAGS["FUSED_EVAL"] if _FLAGS.get("FUSED_EVAL") in _FUSED_EVAL_VALUES else _flag("FUSED_EVAL", False)
 
 
@@ -189,20 +200,21 @@ def fused_eval():
 
 
 def fused_eval_operands():
-    """The slot format of the fused eval plan: "fp16x2" (Settings.fused_eval = True or "fp16x2+pool": fp16 hi | mid parts), "bf16"
-    (= "bf16" or "bf16+pool": one part of plain bf16), None (off)."""
+    """The slot format of the fused eval plan: "fp16x2" (Settings.fused_eval = True, "fp16x2+pool" or "fp16x2+ragged": fp16 hi | mid
+    parts), "bf16" (= "bf16", "bf16+pool" or "bf16+pool+ragged": one part of plain bf16), None (off)."""
     return _fused_eval_value()[0]
 
 
 def fused_eval_pool():
     """Does the fused eval plan run a unit in front of a max-pool as ONE launch, the pooling in the convolution's epilogue
-    (Settings.fused_eval = "fp16x2+pool" | "bf16+pool": conv3x3_*_pre_act_pool)?"""
+    (Settings.fused_eval = "fp16x2+pool" | "bf16+pool" and the two ragged values: conv3x3_*_pre_act_pool)?"""
     return _fused_eval_value()[1]
 
 
 def fused_eval_ragged():
     """Does the fused eval plan take levels whose maps are not made of full 16 x 32 tiles (Settings.fused_eval = "bf16+pool+ragged":
-    the *_ragged entry points of include/onet_hip_ragged.h, layer predicate eval_layer_ok_ragged)?"""
+    the *_ragged entry points of include/onet_hip_ragged.h, layer predicate eval_layer_ok_ragged; "fp16x2+ragged": those of
+    include/onet_hip_ragged_split.h, eval_layer_ok_ragged_fp16)?"""
     return len(_fused_eval_value()) > 2
 
 
@@ -641,10 +653,11 @@ def convT2x2_fwd_slots(xP, wP, bias, outP, Ct, x_slots=None, slots=None, kind="c
     return rc == 0
 
 
-def convt_slots_ok_ragged(B, Cin, Ct, h, w):
-    """convt_slots_ok(parts = 1) without h w % 128 == 0: onet_convT2x2_fwd_slots_ragged's predicate (pixel tiles counted per image)."""
-    return bool(CONVT_SLOTS and presplit() and CONVT_BF16 and Cin % 32 == 0 and Cin >= 128 and Ct % 32 == 0 and w % 2 == 0
-                and Cin * h * w * 2 < 2 ** 31)
+def convt_slots_ok_ragged(B, Cin, Ct, h, w, parts=1):
+    """convt_slots_ok(parts) without h w % 128 == 0: the predicate of onet_convT2x2_fwd_slots_ragged (parts = 1, the default) /
+    onet_convT2x2_fwd_slots_split_ragged (parts = 2: fp16 hi | mid operands) -- pixel tiles counted per image."""
+    return bool(CONVT_SLOTS and presplit() and (parts == 2 or CONVT_BF16) and Cin % 32 == 0 and Cin >= 128 and Ct % 32 == 0 and w % 2 == 0
+                and Cin * h * w * 2 * parts < 2 ** 31)
 
 
 def convT2x2_fwd_slots_ragged(xP, wP, bias, outP, Ct, kind="convt_slot_fwd_kernel"):
@@ -660,6 +673,24 @@ def convT2x2_fwd_slots_ragged(xP, wP, bias, outP, Ct, kind="convt_slot_fwd_kerne
     _prof_end(kind, flops if rc == 0 else 0.0, e0, nb if rc == 0 else 0.0)
     if rc < 0:
         raise _lib.OnetHipError(f"onet_convT2x2_fwd_slots_ragged failed ({rc}): {_lib.last_error()}")
+    return rc == 0
+
+
+def convT2x2_fwd_slots_split_ragged(xP, wP, bias, outP, Ct, x_slots=None, slots=None, kind="convt_slot_fwd_kernel"):
+    """convT2x2_fwd_slots on fp16 (hi | mid) slots whose map has h w % 128 != 0 (any map of even w qualifies; x_slots / slots: the
+    magnitude slots of input / output): the pixels of the map, value for value, as convT2x2_fwd_slots writes them on the map with zero
+    rows appended.  -> False where the kernel does not take the shape (nothing written)."""
+    B, C8, h, parts, w, _ = xP.shape
+    assert parts == 2 and outP.shape[3] == 2 and outP.shape[2] == 2 * h and outP.shape[4] == 2 * w
+    assert xP.dtype == wP.dtype == outP.dtype == torch.float16
+    Cin = C8 * 8
+    e0 = _prof_begin(kind)
+    rc = _lib.load().onet_convT2x2_fwd_slots_split_ragged(_p(xP), _pbs(xP), _p(x_slots), _p(wP), _p(bias), _p(outP), _pbs(outP), _p(slots), 2, B,
+                                                          Cin, Ct, h, w, _stream())
+    flops, nb = 2.0 * B * h * w * Cin * 4 * Ct, 4.0 * (B * h * w * (Cin + 4 * Ct) + 4 * Cin * Ct)
+    _prof_end(kind, flops if rc == 0 else 0.0, e0, nb if rc == 0 else 0.0)
+    if rc < 0:
+        raise _lib.OnetHipError(f"onet_convT2x2_fwd_slots_split_ragged failed ({rc}): {_lib.last_error()}")
     return rc == 0
 
 
@@ -1281,7 +1312,8 @@ def _ragged_map(H, W):
 
 
 # The narrowest map that is not made of full tiles which eval_layer_ok_ragged takes (ONET_FLAGS / tools: 32, 64, 128 leave the 28-, 56-,
-# 112-pixel level of a 224 x 224 input to the fall-back -- tools/time_ragged_eval.py times the plan level by level with it)
+# 112-pixel level of a 224 x 224 input to the fall-back -- tools/time_ragged_eval.py times the plan level by level with it).
+# eval_layer_ok_ragged_fp16 keeps the same floor (tools/time_ragged_fp16_eval.py: every level is faster fused on that format too)
 RAGGED_MIN_W = int(_FLAGS.get("RAGGED_MIN_W", 20))
 
 
@@ -1303,6 +1335,22 @@ def eval_layer_ok_ragged(B, Cin, Cout, H, W):
     if conv_algo() in ("bf16", "split"):
         return True
     return B * -(-H // 16) * -(-W // 32) * (Cout // 64) >= (n_cu() * 3) // 4
+
+
+def eval_layer_ok_ragged_fp16(B, Cin, Cout, H, W):
+    """eval_layer_ok for Settings.fused_eval = "fp16x2+ragged": the domain of onet_conv3x3_split_fwd_pre_act_ragged -- fp16 (hi | mid)
+    parts with pre-split storage, Cin % 16 == 0, Cout % 64 == 0, even H and W % 4 == 0 (_ragged_map: the kernel's own slot stores are
+    per pixel, but the stem's and the `pack` route's passes, the head's float4 accesses and the fall-back levels need W % 4) -- where
+    today's dispatch selects the split kernel (conv3x3_algo: its fill rule counts tiles by cdiv).  On a map made of full tiles the
+    answer is eval_layer_ok's.  A map that is not must be wider than 16 pixels and no narrower than RAGGED_MIN_W (eval_layer_ok_ragged's
+    floor: a 256 x 256 input keeps the plan of "fp16x2+pool")."""
+    if full_tiles(H, W):
+        return eval_layer_ok(B, Cin, Cout, H, W)
+    if not presplit() or p16_parts() != 2:
+        return False
+    if Cin % 16 or Cout % 64 or W <= 16 or W < RAGGED_MIN_W or not _ragged_map(H, W):
+        return False
+    return conv3x3_algo(B, Cin, Cout, H, W) == "split"
 
 
 def _pre_act(entry, kind, two, cin_mult, xs, wq, Cout, save, out, a_amax, a, extra_in, extra_out, pooled=None, ragged=False):
@@ -1402,6 +1450,59 @@ def conv3x3_split_pre_act_pool(xs, wq, Cout, save, aP_slots, out=None, slots=Non
     return _pre_act("onet_conv3x3_split_fwd_pre_act_pool", "conv3x3_split_pre_act_pool_kernel", 2, 16, xs, wq, Cout, save, out, a_amax, a,
                     (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)), (_p(aP_slots),),
                     pooled=(yP, y))
+
+
+def _fp16_packs(name, xs, wq):
+    if wq is None or not wq.is_cuda or wq.dtype != torch.float16 or xs.dtype != torch.float16 or xs.shape[3] != 2:
+        raise TypeError(f"{name}: xs and wq must be fp16 (hi | mid) split packs on the GPU")
+
+
+def conv3x3_split_pre_act_pool_ragged(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None,
+                                      yP=None, y=None):
+    """conv3x3_split_pre_act_pool on a ragged map (even H, W % 4 == 0; onet_conv3x3_split_fwd_pre_act_pool_ragged): the pooled maps are
+    H / 2 x W / 2; a_amax receives the maximum over the map's own pixels.  -> aP, or None (nothing launched)."""
+    _fp16_packs("conv3x3_split_pre_act_pool_ragged", xs, wq)
+    return _pre_act("onet_conv3x3_split_fwd_pre_act_pool_ragged", "conv3x3_split_pre_act_pool_kernel", 2, 16, xs, wq, Cout, save, out, a_amax, a,
+                    (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)), (_p(aP_slots),),
+                    pooled=(yP, y), ragged=True)
+
+
+def conv3x3_split_pre_act_ragged(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None):
+    """conv3x3_split_pre_act on a ragged map (even H, W % 4 == 0; onet_conv3x3_split_fwd_pre_act_ragged): on the map, value for value,
+    what conv3x3_split_pre_act writes on the map zero-padded to whole 16 x 32 tiles; nothing outside the map is written.  a_amax: the
+    exact maximum over the MAP's pixels (bit-equal to a.max() of the same launch).  -> aP, or None (nothing launched)."""
+    _fp16_packs("conv3x3_split_pre_act_ragged", xs, wq)
+    return _pre_act("onet_conv3x3_split_fwd_pre_act_ragged", "conv3x3_split_pre_act_kernel", 2, 16, xs, wq, Cout, save, out, a_amax, a,
+                    (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)), (_p(aP_slots),), ragged=True)
+
+
+def conv3x3_split_pre_head_ragged(xs, wq, Cout, save, L, out=None, slots=None, slots2=None, split_ch=0):
+    """conv3x3_split_pre_head on a ragged map (conv3x3_split_pre_act_ragged's domain, Cout == 64).  -> V, or None (nothing launched,
+    nothing written)."""
+    _fp16_packs("conv3x3_split_pre_head_ragged", xs, wq)
+    return _pre_head("onet_conv3x3_split_fwd_pre_head_ragged", "conv3x3_split_pre_head_kernel", 2, xs, wq, Cout, save, L, out,
+                     (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)))
+
+
+def conv3x3_split_pre_plain_ragged(xs, wq, Cout, out=None, slots=None, slots2=None, split_ch=0):
+    """z = conv3x3 (fp32) of fp16 (hi | mid) slots on a ragged map (conv3x3_split_pre_act_ragged's domain): conv3x3_split_pre's launch
+    there (slots / slots2 / split_ch: the magnitude slots the producers scaled xs by).  -> z, or None (nothing launched)."""
+    _fp16_packs("conv3x3_split_pre_plain_ragged", xs, wq)
+    B, C8, H, _, W, _ = xs.shape
+    Cin = C8 * 8
+    if not _ragged_map(H, W) or Cin % 16 or Cout % 64:
+        return None
+    if out is None:
+        out = torch.empty((B, Cout, H, W), dtype=F32, device=xs.device)
+    e0 = _prof_begin("conv3x3_split_pre_kernel")
+    rc = _lib.load().onet_conv3x3_split_fwd_pre_plain_ragged(_p(xs), _pbs(xs), _p(slots), 0, _p(slots2),
+                                                             int(split_ch if slots2 is not None or slots is not None else 0), _p(wq), _p(out),
+                                                             out.stride(0) if B > 1 else Cout * H * W, B, Cin, Cout, H, W, _stream())
+    _prof_end("conv3x3_split_pre_kernel", 2.0 * B * H * W * Cin * Cout * 9 if rc == 0 else 0.0, e0,
+              (B * H * W * (4.0 * Cin + 4.0 * Cout) + 4.0 * 9 * Cin * Cout) if rc == 0 else 0.0)
+    if rc < 0:
+        raise _lib.OnetHipError(f"onet_conv3x3_split_fwd_pre_plain_ragged failed ({rc}): {_lib.last_error()}")
+    return out if rc == 0 else None
 
 
 def conv3x3_act_bound(weight, save, x_amax, x_amax2=None, split_ch=0):
