@@ -25,6 +25,7 @@
 #include "common.hpp"
 #include "../../include/onet_hip_ragged.h"
 #include "../../include/onet_hip_ragged_split.h"
+#include "../../include/onet_hip_anymap.h"
 
 using namespace onet;
 
@@ -1211,9 +1212,15 @@ __device__ __forceinline__ u32x4s pre16_slot_transpose(const f32x4s& d1, const f
 // RAG (round 13, the ragged entries): the pooled fp32 store on maps that are not made of full tiles.  Everything else of the kernel
 // already is per-slot / per-float4 bounds-checked (staging: the out-of-range offset; stores: yo < H && xo < W), so the ragged entries
 // launch the full-tile instances; only the pooled fp32 rows, whose two float2 per lane share ONE guard on full tiles, need code.
-template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false, bool POOL = false, bool RAG = false>
+// ANY (round 15, the entries of include/onet_hip_anymap.h): the activation epilogue's two fp32 side outputs on maps of ANY H and W --
+// rows of W floats are not 16-byte aligned at W = 25 or 50, and an odd map ends in the middle of a float4 / a pooled float2 -- stored
+// float by float, each under its own guard.  Pooling is floor pooling (Hp = H >> 1, Wp = W >> 1): a 2 x 2 window that is only partly
+// inside an odd map has a pooled index >= Hp / Wp, so the guards on pooled coordinates keep it out of every pooled store.  Staging,
+// main loop and slot stores are the other instances': per slot, at any width.
+template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false, bool POOL = false, bool RAG = false, bool ANY = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     constexpr bool F16 = PM == 1;
+    static_assert(!ANY || (ACT && PM == 2 && !RAG), "conv3x3_pre16_kernel: the any-map instance is the one-part activation epilogue's");
     static_assert(!POOL || ACT, "conv3x3_pre16_kernel: the pooled stores ride on the activation epilogue");
     static_assert(!RAG || (POOL && PM == 2), "conv3x3_pre16_kernel: the ragged instance is the one-part pooled epilogue's");
     static_assert(!ACT || (PM == 2 && !ST && !W16 && !RD), "conv3x3_pre16_kernel: the activation epilogue goes with the one-part bf16 slot store");
@@ -1616,7 +1623,19 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
                     if constexpr (PM == 2 && !ST && !W16 && !RD) {
                         if constexpr (ACT) {
                             // the activation in fp32 NCHW too, for a reader that takes no slots: the plain z store's float4s
-                            if (a.act_a && yo < a.H && xo < a.W) {
+                            if constexpr (ANY) {
+                                // no row alignment, and the map may end inside the lane's four pixels: one guard per float
+                                if (a.act_a && yo < a.H && xo < a.W) {
+                                    const int co = co0 + ct * 16 + c8;
+                                    float* o = a.act_a + (int64_t)b * a.act_a_bs + (int64_t)co * HW + (int64_t)yo * a.W + xo;
+#pragma unroll
+                                    for (int i = 0; i < 4; ++i)
+                                        if (xo + i < a.W) {
+                                            if (co < a.Cout) o[i] = d1[i];
+                                            if (co + 8 < a.Cout) o[(int64_t)8 * HW + i] = d2[i];
+                                        }
+                                }
+                            } else if (a.act_a && yo < a.H && xo < a.W) {
                                 const int co = co0 + ct * 16 + c8;
                                 float* o = a.act_a + (int64_t)b * a.act_a_bs + (int64_t)co * HW + (int64_t)yo * a.W + xo;
                                 if (co < a.Cout) *reinterpret_cast<f32x4s*>(o) = d1;
@@ -1671,7 +1690,23 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
                     pm[ct][2 * ch] = fmaxf(fmaxf(t[0], t[1]), fmaxf(u[0], u[1]));
                     pm[ct][2 * ch + 1] = fmaxf(fmaxf(t[2], t[3]), fmaxf(u[2], u[3]));
                 }
-            if constexpr (RAG) {
+            if constexpr (ANY) {
+                // one guard per float: Wp may be odd and the pooled rows are not 8-byte aligned; the address is formed under the guard
+                if (a.pl_y && yp < Hp) {
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) {
+                        const int co = co0 + ct * 16 + r16;
+                        if (co < a.Cout) {
+                            float* row = a.pl_y + (int64_t)b * a.pl_y_bs + ((int64_t)co * Hp + yp) * Wp;
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                const int xp = xp0 + (i & 1) + (i & 2 ? 8 : 0);
+                                if (xp < Wp) row[xp] = pm[ct][i];
+                            }
+                        }
+                    }
+                }
+            } else if constexpr (RAG) {
                 // one guard per float2: Wp and xp0 are even (W % 4 == 0), so a pair is wholly inside the pooled row or wholly outside;
                 // the address is formed under the guard
                 if (a.pl_y && yp < Hp) {
@@ -1783,7 +1818,7 @@ int sp_launch_persistent(void (*kern)(Args), PerDeviceOnce& once, int lds_bytes,
     return check_launch(name);
 }
 
-template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false, bool POOL = false, bool RAG = false>
+template <bool ST, int PM, bool W16, bool RD = false, bool ACT = false, bool HEAD = false, bool POOL = false, bool RAG = false, bool ANY = false>
 int launch_split_pre(SpPreArgs a, hipStream_t st) {
     using C = SpPreCfg<W16>;
     const int LDS_BYTES = C::LDS_BYTES + (ST ? C::NW * 64 * 2 * 4 : 0) + (ACT || HEAD ? 2 * 3 * 64 * 4 : 0);
@@ -1799,7 +1834,8 @@ int launch_split_pre(SpPreArgs a, hipStream_t st) {
     // level (that instance of the new kernel exceeds the register budget).  The head epilogue exists on the 16x16x32 kernel alone.
     constexpr bool P16 = RD || PM == 2 || (ST && !W16) || HEAD;
     void (*kern)(SpPreArgs);
-    if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD, ACT, HEAD, POOL, RAG>;      // (constexpr: the instances not dispatched are not built)
+    static_assert(!ANY || P16, "launch_split_pre: the any-map instance exists on the 16x16x32 kernel alone");
+    if constexpr (P16) kern = conv3x3_pre16_kernel<ST, PM, W16, RD, ACT, HEAD, POOL, RAG, ANY>;      // (constexpr: the instances not dispatched are not built)
     else kern = conv3x3_split_pre_kernel<ST, PM, W16, ACT, POOL, RAG>;
     static PerDeviceOnce attr_once;
     return sp_launch_persistent(kern, attr_once, LDS_BYTES, tiles, C::NW * 64,
@@ -2918,6 +2954,69 @@ int onet_conv3x3_plain16_fwd_pre_act_pool_ragged(const void* xs, int64_t xs_bs, 
                                                  int Cin, int Cout, int H, int W, void* stream) {
     return pre_act_pool_impl("conv3x3_plain16_fwd_pre_act_pool_ragged", true, 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, aP, aP_bs, nullptr,
                              a_amax, a, a_bs, yP, yP_bs, y, y_bs, B, Cin, Cout, H, W, stream);
+}
+
+// The one-part _act / _act_pool entries on maps of ANY H and W (include/onet_hip_anymap.h, round 15): the levels below the first of an
+// input such as 200 x 200 (50 x 50: W % 4 == 2; 25 x 25: odd).  Domain: H, W > 0, H W < 2^24, Cin % 32 == 0, Cout % 64 == 0, inside
+// the buffer-resource range, a_amax NULL; outside it 1, nothing launched.  A map the ragged entry takes goes to that entry's own
+// launch (on full tiles the full-tile instance); every other map to the ANY instance, whose fp32 side outputs are stored float by
+// float.  pool: the pooled maps are H / 2 x W / 2, rounded DOWN (nn.MaxPool2d(2)), and the stride checks use those sizes.
+static bool anymap_domain(const void* a_amax, int Cin, int Cout, int H, int W) {
+    return !a_amax && (int64_t)H * W < (1 << 24) && !(Cin % 32) && !(Cout % 64) && (int64_t)(Cin + 32) * H * W * 4 < (1ll << 31) &&
+           (int64_t)(Cin + 32) * 2 * 9 * Cout * 2 < (1ll << 31);
+}
+
+int onet_conv3x3_plain16_fwd_pre_act_anymap(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
+                                            void* a_amax, float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    const char* entry = "conv3x3_plain16_fwd_pre_act_anymap";
+    ONET_REQUIRE(xs && wq && save && aP, "%s: null pointer", entry);
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
+    if (!anymap_domain(a_amax, Cin, Cout, H, W)) return 1;
+    if (pre_map_ok(true, H, W)) return plain16_pre_act_impl(entry, true, xs, xs_bs, wq, save, aP, aP_bs, nullptr, a, a_bs, B, Cin, Cout, H, W, stream);
+    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 2, Cin, Cout, H, W)) return rc;
+    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "%s: 16-byte aligned slots required", entry);
+    ONET_REQUIRE(!a || (reinterpret_cast<uintptr_t>(a) & 3) == 0, "%s: 4-byte aligned floats required", entry);
+    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W / 2 && (!a || a_bs >= (int64_t)Cout * H * W), "%s: batch stride too small", entry);
+    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, nullptr, 0, nullptr, 0};
+    p.zP = aP;
+    p.zP_bs = aP_bs;
+    p.zP_ch0 = 0;
+    p.act_save = save;
+    p.act_a = a;
+    p.act_a_bs = a_bs;
+    return launch_split_pre<false, 2, false, false, true, false, false, false, true>(p, as_stream(stream));
+}
+
+int onet_conv3x3_plain16_fwd_pre_act_pool_anymap(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
+                                                 void* a_amax, float* a, int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B,
+                                                 int Cin, int Cout, int H, int W, void* stream) {
+    const char* entry = "conv3x3_plain16_fwd_pre_act_pool_anymap";
+    ONET_REQUIRE(xs && wq && save && aP, "%s: null pointer", entry);
+    ONET_REQUIRE(yP || y, "%s: a pooled destination is required (yP, y or both)", entry);
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
+    if (!anymap_domain(a_amax, Cin, Cout, H, W)) return 1;
+    if (pre_map_ok(true, H, W))
+        return pre_act_pool_impl(entry, true, 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, aP, aP_bs, nullptr, nullptr, a, a_bs, yP, yP_bs, y, y_bs, B,
+                                 Cin, Cout, H, W, stream);
+    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 2, Cin, Cout, H, W)) return rc;
+    const int64_t n = (int64_t)Cout * H * W, np = (int64_t)Cout * (H >> 1) * (W >> 1);      // floor pooling
+    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0 && (!yP || ((yP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(yP) & 15) == 0)),
+                 "%s: 16-byte aligned slots required", entry);
+    ONET_REQUIRE((!a || (reinterpret_cast<uintptr_t>(a) & 3) == 0) && (!y || (reinterpret_cast<uintptr_t>(y) & 3) == 0), "%s: 4-byte aligned floats required",
+                 entry);
+    ONET_REQUIRE(aP_bs >= n / 2 && (!a || a_bs >= n) && (!yP || yP_bs >= np / 2) && (!y || y_bs >= np), "%s: batch stride too small", entry);
+    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, nullptr, 0, nullptr, 0};
+    p.zP = aP;
+    p.zP_bs = aP_bs;
+    p.zP_ch0 = 0;
+    p.act_save = save;
+    p.act_a = a;
+    p.act_a_bs = a_bs;
+    p.pl_P = yP;
+    p.pl_P_bs = yP_bs;
+    p.pl_y = y;
+    p.pl_y_bs = y_bs;
+    return launch_split_pre<false, 2, false, false, true, false, true, false, true>(p, as_stream(stream));
 }
 
 int onet_conv3x3_split_fwd_pre_act_pool(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,

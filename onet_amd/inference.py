@@ -49,6 +49,16 @@ masks its record: relu(bn(.)) of an out-of-map accumulator is not zero and would
 hand on their bound, the `pack` route's conversion pass writes two parts scaled by the ConvTranspose2d's own bound.  On a level made
 of full tiles the launches, their order and the bits are those of "fp16x2+pool".
 
+Settings.fused_eval = "bf16+pool+anymap" (ops.fused_eval_anymap()): the plan of "bf16+pool+ragged" whose levels k >= 1 also take maps of
+ANY H and W above the width floor (ops.eval_layer_ok_anymap; the entry points of include/onet_hip_anymap.h), so that 200 x 200 -- levels
+of 200, 100, 50, 25 and 12 pixels -- is fused down to its 25-pixel level.  Level k is H >> k x W >> k: the pooling rounds down, as
+nn.MaxPool2d(2) does, and a unit in front of a pool on an odd map writes the floor-pooled tensor.  Level 0 keeps the ragged domain (the
+stem's pass and the head's float4 accesses need W % 4 == 0 and even H).  Such a level is marked _Level.ragged = "anymap" where its map
+lies outside the ragged domain; on every other level the launches are those of "bf16+pool+ragged".  A ConvTranspose2d edge takes the
+`pack` route -- the general kernel into an fp32 tensor of the concat map's size at the reference's F.pad offsets (diffY // 2,
+diffX // 2; the pad strip zeroed first), then one conversion pass -- where its output must be padded (level k is odd) or its input map
+has odd w: the slot-operand GEMM keeps its dense 2h x 2w, even-w domain.  The lower level's last unit then also writes fp32 (keep_fp32).
+
 The validation step (validate, EvalCounts): the scores of a batch -- by the labels-only plan where it applies, the ordinary forward
 elsewhere -- then ONE launch (ops.score_counts) that forms the labels and adds each image's confusion counts against the ground truth
 into a device tensor; nothing synchronises, and metrics.epoch_metrics turns an epoch's rows into the reference's metrics on the host.
@@ -86,8 +96,11 @@ def _units(blk):
 # max-pool in one launch, taken where ops.fused_eval_pool() holds), whether tensors carry magnitude slots (without them: scale = amax =
 # None everywhere, no bound launches) and whether the pooled tensors are traced
 # (ragged: the launches of a level whose maps are not made of full 16 x 32 tiles -- None: the format takes no such level)
-_Format = namedtuple("_Format", "operands parts pack layer_ok act act_pool head magnitude trace_pool ragged", defaults=(None,))
+# (anymap: the layer predicate and the launches of a level k >= 1 whose map lies outside the ragged domain -- None: no such level)
+_Format = namedtuple("_Format", "operands parts pack layer_ok act act_pool head magnitude trace_pool ragged anymap", defaults=(None, None))
 _Ragged = namedtuple("_Ragged", "act act_pool head plain")
+_AnyMap = namedtuple("_AnyMap", "layer_ok act act_pool")
+_ANYMAP = _AnyMap(ops.eval_layer_ok_anymap, ops.conv3x3_plain16_pre_act_anymap, ops.conv3x3_plain16_pre_act_pool_anymap)
 _RAGGED = _Ragged(ops.conv3x3_plain16_pre_act_ragged, ops.conv3x3_plain16_pre_act_pool_ragged, ops.conv3x3_plain16_pre_head_ragged,
                   ops.conv3x3_plain16_pre_plain_ragged)
 _RAGGED_FP16 = _Ragged(ops.conv3x3_split_pre_act_ragged, ops.conv3x3_split_pre_act_pool_ragged, ops.conv3x3_split_pre_head_ragged,
@@ -102,7 +115,8 @@ def _format():
     if name == "bf16":
         # (trace_pool: the one-part plan's trace is complete -- every convolution's exact input can be rebuilt)
         return _Format(name, 1, "plain16", ops.eval_layer_ok_ragged if rag else ops.eval_layer_ok_bf16, ops.conv3x3_plain16_pre_act,
-                       ops.conv3x3_plain16_pre_act_pool, ops.conv3x3_plain16_pre_head, False, True, _RAGGED if rag else None)
+                       ops.conv3x3_plain16_pre_act_pool, ops.conv3x3_plain16_pre_head, False, True, _RAGGED if rag else None,
+                       _ANYMAP if ops.fused_eval_anymap() else None)
     return _Format(name, 2, "split", ops.eval_layer_ok_ragged_fp16 if rag else ops.eval_layer_ok, ops.conv3x3_split_pre_act,
                    ops.conv3x3_split_pre_act_pool, ops.conv3x3_split_pre_head, True, False, _RAGGED_FP16 if rag else None)
 
@@ -144,21 +158,29 @@ def _level_layers(unet):
     return [[(name, conv) for name, conv, _ in e + d] for e, d in _level_units(unet)]
 
 
-def _depth(units, ups, layer_ok, N, H, W):
-    """-> (d, why level d is not fused | None): levels 0 .. d - 1 are fused"""
+def _depth(units, ups, layer_ok, N, H, W, anymap_ok=None):
+    """-> (d, why level d is not fused | None): levels 0 .. d - 1 are fused.  anymap_ok: the predicate of the levels k >= 1 of a plan
+    that takes maps of any size there -- level k is then H >> k x W >> k (floor pooling) whatever the input's divisibility"""
+    level0_ok = layer_ok
     for k, (e, d) in enumerate(units):
-        if (H % (1 << k)) or (W % (1 << k)):
+        if anymap_ok is None and ((H % (1 << k)) or (W % (1 << k))):
             return k, f"level {k}: the input size is not a multiple of {1 << k}"
         h, w = H >> k, W >> k
+        if anymap_ok is not None:
+            if h <= 0 or w <= 0:
+                return k, f"level {k}: the map is empty"
+            layer_ok = anymap_ok if k else level0_ok
         for name, conv, _ in e + d:
             if not layer_ok(N, conv.in_channels, conv.out_channels, h, w):
                 # (on a map made of full tiles, or no wider than 16 pixels, the ragged predicate IS eval_layer_ok_bf16, and the reason
                 # says so: the answer of "bf16+pool")
                 full = {ops.eval_layer_ok_ragged: ops.eval_layer_ok_bf16, ops.eval_layer_ok_ragged_fp16: ops.eval_layer_ok}.get(layer_ok)
+                if layer_ok is anymap_ok:
+                    full = ops.eval_layer_ok_bf16
                 ragged = full is not None and w > 16 and not ops.full_tiles(h, w)
                 ok_name = (layer_ok if ragged or full is None else full).__name__
                 why = f"level {k}: {name} ({conv.in_channels} -> {conv.out_channels} on {N} maps of {h} x {w}) is outside ops.{ok_name}"
-                if ragged and (w % 4 or h % 2):
+                if ragged and layer_ok is not anymap_ok and (w % 4 or h % 2):
                     why += f": W = {w} must be a multiple of 4 and H = {h} even"
                 return k, why
         if k < 4:
@@ -185,9 +207,10 @@ _Unit = namedtuple("_Unit", "name conv bn kind keep_fp32")
 # One level: its encoder and decoder units in execution order, the ConvTranspose2d that fills its concat buffer with its kind ("slots":
 # from the slots of the level below; "fp32->slots": from an fp32 tensor; level 4 has none), and whether the pooled tensor leaves as
 # slots (fp32: for the fall-back levels); ragged: the level's maps are not made of full tiles, its units take the format's ragged
-# launches; route: the launch(es) behind `convt` -- "slots" / "slots_ragged" (the slot-operand GEMM, on maps with h w % 128 != 0 its ragged
-# entry), "gemm" (the fp32-operand GEMM that writes slots) / "pack" (where that GEMM does not take the map, h w % 128 != 0: the general
-# ConvTranspose2d into an fp32 tensor, then one conversion pass into the concat buffer's up-sampled groups)
+# launches ("anymap": the map also lies outside the ragged domain, its units take the format's any-map launches); route: the launch(es)
+# behind `convt` -- "slots" / "slots_ragged" (the slot-operand GEMM, on maps with h w % 128 != 0 its ragged entry), "gemm" (the fp32-operand GEMM that writes slots) / "pack" (where that GEMM does not take the map, h w % 128 != 0: the general
+# ConvTranspose2d into an fp32 tensor, then one conversion pass into the concat buffer's up-sampled groups; also wherever the output must be
+# padded into the concat buffer or the input map has odd w -- any-map levels)
 _Level = namedtuple("_Level", "enc dec up convt pooled_slots ragged route", defaults=(False, None))
 # One U-Net pass.  reason: why the plan does not run (None: it runs); static: the part of it that holds whatever the input;
 # levels 0 .. depth - 1 are fused, fallback_reason says why level `depth` is not; head: the last unit ends in the head-epilogue launch
@@ -208,7 +231,7 @@ def _build_plan(unet, shape, head=None):
     if C != unet.inc.double_conv[0].in_channels:
         return _Plan(fmt, N, _WHY_CHANNELS)
     units, ups = _level_units(unet), _blocks(unet)[2]
-    d, why_d = _depth(units, ups, fmt.layer_ok, N, H, W)
+    d, why_d = _depth(units, ups, fmt.layer_ok, N, H, W, fmt.anymap.layer_ok if fmt.anymap else None)
     if d == 0:
         return _Plan(fmt, N, why_d, None, 0, why_d)
     # the ConvTranspose2d of level k reads the output of level k + 1: slots where that level is fused and the slot-operand kernel takes
@@ -217,6 +240,10 @@ def _build_plan(unet, shape, head=None):
         h, w, cin, ct = H >> (k + 1), W >> (k + 1), up.up.in_channels, up.up.out_channels
         if k >= d:
             return "fallback", None
+        if fmt.anymap and ((H >> k, W >> k) != (2 * h, 2 * w) or w % 2):
+            # (any-map levels: the output is padded into the concat buffer -- level k is odd -- or the input map has odd w; the slot
+            # GEMMs keep their dense 2h x 2w, even-w domain)
+            return "fp32->slots", "pack"
         if k + 1 < d and ops.convt_slots_ok(N, cin, ct, h, w, parts=fmt.parts):
             return "slots", "slots"
         if k + 1 < d and fmt.ragged and (h * w) % 128 and ops.convt_slots_ok_ragged(N, cin, ct, h, w, parts=fmt.parts):
@@ -239,8 +266,15 @@ def _build_plan(unet, shape, head=None):
         keep = {(dec or e)[-1][0]} if 0 < k < d and convt[k - 1] == "fp32->slots" else ()
         enc_u, dec_u = ([_Unit(name, conv, bn, kind[name], name in keep) for name, conv, bn in us] for us in (e, dec))
         levels.append(_Level(enc_u, dec_u, ups[k].up if k < 4 else None, convt[k] if k < 4 else None, k + 1 < d,
-                             k < d and not ops.full_tiles(H >> k, W >> k), edges[k][1] if k < 4 else None))
+                             _level_ragged(k < d, H >> k, W >> k), edges[k][1] if k < 4 else None))
     return _Plan(fmt, N, None, None, d, why_d, unet, tuple(levels), with_head)
+
+
+def _level_ragged(fused, h, w):
+    """_Level.ragged of a level of h x w maps: False (fall-back, or full tiles), True (the ragged launches), "anymap" """
+    if not fused or ops.full_tiles(h, w):
+        return False
+    return True if ops._ragged_map(h, w) else "anymap"
 
 
 def _query(unet, shape, head=None, device=None):
@@ -402,7 +436,7 @@ def _fused_unit(fmt, u, t, ragged=False):
     amax = ops.new_amax(t.P.device) if fmt.magnitude else None
     a = torch.empty((B, conv.out_channels, H, W), dtype=torch.float32, device=t.P.device) if u.keep_fp32 else None
     # (a ragged launch takes its sibling's magnitude-slot arguments: none on the one-part format, whose ragged entries record no maximum)
-    launch = fmt.ragged.act if ragged else fmt.act
+    launch = fmt.anymap.act if ragged == "anymap" else fmt.ragged.act if ragged else fmt.act
     aP = launch(t.P, _wq(fmt, conv), conv.out_channels, save, a=a, **_slot_kw(fmt, t, aP_slots=scale, a_amax=amax))
     if aP is None:
         raise RuntimeError(f"onet_amd: the fused eval kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
@@ -432,7 +466,8 @@ def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots, ragged=False):
     yP = ops.p16_empty(B, C, H // 2, W // 2, dev, parts=fmt.parts) if pooled_slots else None
     yF = None if pooled_slots else torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=dev)
     if z is None and ragged:
-        if fmt.ragged.act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, aP_slots=scale)) is None:
+        act_pool = fmt.anymap.act_pool if ragged == "anymap" else fmt.ragged.act_pool
+        if act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, aP_slots=scale)) is None:
             raise RuntimeError(f"onet_amd: the ragged pooling kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
     elif z is None:
         if fmt.act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, aP_slots=scale)) is None:
@@ -465,9 +500,13 @@ def _conv_t(fmt, lv, t, catP, C2):
     if lv.route == "pack":
         # (the smallest maps of the pass: the general kernel into an fp32 tensor, then one conversion pass -- what the training forward
         # does where the GEMM's fast path does not take the map)
+        # any-map levels: an odd concat map takes the up-sampled tensor at the reference's F.pad offsets, the pad strip zero (the kernel
+        # writes its 2h x 2w window alone)
         B, _, h, w = t.F.shape
-        y = torch.empty((B, Ct, 2 * h, 2 * w), dtype=torch.float32, device=t.F.device)
-        ops.convT2x2_fwd(t.F, packed[0], up.bias, y, Ct, 0, 0)
+        Ho, Wo = catP.shape[2], catP.shape[4]
+        padded = (Ho, Wo) != (2 * h, 2 * w)
+        y = (torch.zeros if padded else torch.empty)((B, Ct, Ho, Wo), dtype=torch.float32, device=t.F.device)
+        ops.convT2x2_fwd(t.F, packed[0], up.bias, y, Ct, (Ho - 2 * h) // 2, (Wo - 2 * w) // 2)
         ops.split_pack_act(y, out=dst, slots=s_up)
         return s_up
     if t.P is not None and ops.convT2x2_fwd_slots(t.P, packed.slots(fmt.parts), up.bias, dst, Ct, x_slots=t.scale, slots=s_up,

@@ -72,6 +72,9 @@ class Settings:
                     "fp16x2+ragged": the plan of "fp16x2+pool" ("+pool" implied) that also takes such levels, at fp32 level
                     (eval_layer_ok_ragged_fp16; the exact maxima its bounds start from are taken over the map's own pixels); on
                     levels made of full tiles the launches and the bits of "fp16x2+pool".
+                    "bf16+pool+anymap": the plan of "bf16+pool+ragged" whose levels below the first also take maps of ANY H and W, odd
+                    included (fused_eval_anymap(), eval_layer_ok_anymap: 200 x 200 down to its 25-pixel level; floor pooling, the
+                    reference's F.pad); on every map "bf16+pool+ragged" takes, its launches and bits.
                     Any other string is a ValueError where the setting is read"""
     __slots__ = ("conv", "twin", "convt_bf16", "lazy_nan", "split", "bn_on_load", "split_f16", "grad_f16", "split_dgrad",
                  "stem_fused", "sync_bn", "presplit", "z_bf16", "fused_eval")
@@ -171,10 +174,11 @@ def presplit():
 
 # The string values of Settings.fused_eval -> (slot format, pooled units in one launch[, ragged levels]); True is ("fp16x2", False)
 _FUSED_EVAL_VALUES = {"bf16": ("bf16", False), "fp16x2+pool": ("fp16x2", True), "bf16+pool": ("bf16", True),
-                      "bf16+pool+ragged": ("bf16", True, True), "fp16x2+ragged": ("fp16x2", True, True)}
+                      "bf16+pool+ragged": ("bf16", True, True), "fp16x2+ragged": ("fp16x2", True, True),
+                      "bf16+pool+anymap": ("bf16", True, True, True)}
 # 1: eval forwards under no_grad take the fused inference plan (Settings.fused_eval); bf16: its one-part plain-bf16 form; either with
 # "+pool" ("fp16x2+pool", "bf16+pool"): the pooled units in one launch; "bf16+pool+ragged" / "fp16x2+ragged" ("+pool" implied): ... on
-# maps not made of full tiles too
+# maps not made of full tiles too; "bf16+pool+anymap": the plan of "bf16+pool+ragged" whose levels below the first take maps of any H and W
 #   value                format    pooled units    ragged levels    layer predicate
 #   True                 fp16x2    two passes      no               eval_layer_ok
 #   "fp16x2+pool"        fp16x2    one launch      no               eval_layer_ok
@@ -182,6 +186,7 @@ _FUSED_EVAL_VALUES = {"bf16": ("bf16", False), "fp16x2+pool": ("fp16x2", True), 
 #   "bf16"               bf16      two passes      no               eval_layer_ok_bf16
 #   "bf16+pool"          bf16      one launch      no               eval_layer_ok_bf16
 #   "bf16+pool+ragged"   bf16      one launch      yes              eval_layer_ok_ragged
+#   "bf16+pool+anymap"   bf16      one launch      yes, any map     eval_layer_ok_ragged (level 0), eval_layer_ok_anymap (below)
 FUSED_EVAL = _FLAGS["FUSED_EVAL"] if _FLAGS.get("FUSED_EVAL") in _FUSED_EVAL_VALUES else _flag("FUSED_EVAL", False)
 
 
@@ -216,6 +221,13 @@ def fused_eval_ragged():
     the *_ragged entry points of include/onet_hip_ragged.h, layer predicate eval_layer_ok_ragged; "fp16x2+ragged": those of
     include/onet_hip_ragged_split.h, eval_layer_ok_ragged_fp16)?"""
     return len(_fused_eval_value()) > 2
+
+
+def fused_eval_anymap():
+    """Does the fused eval plan take, at its levels below the first, maps of ANY H and W above the width floor (Settings.fused_eval =
+    "bf16+pool+anymap": the entry points of include/onet_hip_anymap.h, layer predicate eval_layer_ok_anymap)?  Implies
+    fused_eval_ragged(): level 0 and every map of even H and W % 4 == 0 run what "bf16+pool+ragged" runs."""
+    return len(_fused_eval_value()) > 3
 
 
 Z_BF16 = _flag("Z_BF16", True)       # BASELINE configs[2] (conv == "bf16", pre-split operands): conv outputs stored as bf16 (Settings.z_bf16)
@@ -1337,6 +1349,28 @@ def eval_layer_ok_ragged(B, Cin, Cout, H, W):
     return B * -(-H // 16) * -(-W // 32) * (Cout // 64) >= (n_cu() * 3) // 4
 
 
+# The narrowest map outside eval_layer_ok_ragged's domain (odd H or W, W % 4 != 0) that eval_layer_ok_anymap takes: the floor of the ragged
+# levels unless set apart (ONET_FLAGS / tools/time_anymap_eval.py: 26 leaves the 25-pixel level of a 200 x 200 input to the fall-back)
+ANYMAP_MIN_W = int(_FLAGS.get("ANYMAP_MIN_W", RAGGED_MIN_W))
+
+
+def eval_layer_ok_anymap(B, Cin, Cout, H, W):
+    """eval_layer_ok_ragged for the levels below the first of Settings.fused_eval = "bf16+pool+anymap": wherever that predicate says yes,
+    yes; besides, the domain of onet_conv3x3_plain16_fwd_pre_act_anymap -- ANY H and W, odd included (the kernel's fp32 side outputs
+    are stored float by float, pooling rounds down as nn.MaxPool2d(2) does) -- above the same width floor (W > 16, W >= RAGGED_MIN_W
+    and ANYMAP_MIN_W), Cin % 32 == 0, Cout % 64 == 0, inside the buffer-resource range, with pre-split storage on, under the same fill
+    rule on cdiv tile counts."""
+    if eval_layer_ok_ragged(B, Cin, Cout, H, W):
+        return True
+    if not presplit() or _ragged_map(H, W):
+        return False
+    if Cin % 32 or Cout % 64 or H <= 0 or W <= 16 or W < max(RAGGED_MIN_W, ANYMAP_MIN_W) or H * W >= 2 ** 24 or not _in_buffer_range(Cin, Cout, H, W):
+        return False
+    if conv_algo() in ("bf16", "split"):
+        return True
+    return B * -(-H // 16) * -(-W // 32) * (Cout // 64) >= (n_cu() * 3) // 4
+
+
 def eval_layer_ok_ragged_fp16(B, Cin, Cout, H, W):
     """eval_layer_ok for Settings.fused_eval = "fp16x2+ragged": the domain of onet_conv3x3_split_fwd_pre_act_ragged -- fp16 (hi | mid)
     parts with pre-split storage, Cin % 16 == 0, Cout % 64 == 0, even H and W % 4 == 0 (_ragged_map: the kernel's own slot stores are
@@ -1359,7 +1393,9 @@ def _pre_act(entry, kind, two, cin_mult, xs, wq, Cout, save, out, a_amax, a, ext
     Cin = C8 * 8
     if pooled is not None and pooled[0] is None and pooled[1] is None:
         raise ValueError(f"{entry[len('onet_'):]}: a pooled destination is required (yP, y or both)")
-    if not (_ragged_map(H, W) if ragged else full_tiles(H, W)) or Cin % cin_mult or Cout % 64:
+    # (ragged = "anymap": the entries of include/onet_hip_anymap.h -- every map below 2^24 pixels)
+    map_ok = (0 < H * W < 2 ** 24) if ragged == "anymap" else _ragged_map(H, W) if ragged else full_tiles(H, W)
+    if not map_ok or Cin % cin_mult or Cout % 64:
         return None
     if out is None:
         out = p16_empty(B, Cout, H, W, xs.device, parts=two)
@@ -1367,7 +1403,7 @@ def _pre_act(entry, kind, two, cin_mult, xs, wq, Cout, save, out, a_amax, a, ext
     pool_args, pool_bytes = (), 0.0
     if pooled is not None:
         yP, y = pooled
-        pool_args = (_p(yP), 0 if yP is None else _pbs(yP), _p(y), 0 if y is None else (y.stride(0) if B > 1 else n // 4))
+        pool_args = (_p(yP), 0 if yP is None else _pbs(yP), _p(y), 0 if y is None else (y.stride(0) if B > 1 else Cout * (H // 2) * (W // 2)))
         pool_bytes = 0.25 * (2.0 * two * (yP is not None) + 4.0 * (y is not None)) * Cout      # per pixel: a quarter as many pooled ones
     e0 = _prof_begin(kind)
     rc = getattr(_lib.load(), entry)(_p(xs), _pbs(xs), *extra_in, _p(wq), _p(save), _p(out), _pbs(out), *extra_out, _p(a_amax), _p(a),
@@ -1406,6 +1442,24 @@ def conv3x3_plain16_pre_act_pool_ragged(xs, wq, Cout, save, out=None, a=None, yP
         raise TypeError("conv3x3_plain16_pre_act_pool_ragged: xs and wq must be one-part bf16 packs on the GPU")
     return _pre_act("onet_conv3x3_plain16_fwd_pre_act_pool_ragged", "conv3x3_pre16_act_pool_kernel", 1, 32, xs, wq, Cout, save, out, None, a, (), (),
                     pooled=(yP, y), ragged=True)
+
+
+def conv3x3_plain16_pre_act_anymap(xs, wq, Cout, save, out=None, a=None):
+    """conv3x3_plain16_pre_act_ragged on a map of ANY H and W (onet_conv3x3_plain16_fwd_pre_act_anymap): on the map, value for value, what
+    conv3x3_plain16_pre_act writes on the map zero-padded to whole 16 x 32 tiles; nothing outside the map is written, and `a` needs no
+    row alignment.  On a map the ragged entry takes: that entry's launch.  -> aP, or None (nothing launched)."""
+    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
+        raise TypeError("conv3x3_plain16_pre_act_anymap: xs and wq must be one-part bf16 packs on the GPU")
+    return _pre_act("onet_conv3x3_plain16_fwd_pre_act_anymap", "conv3x3_pre16_act_kernel", 1, 32, xs, wq, Cout, save, out, None, a, (), (), ragged="anymap")
+
+
+def conv3x3_plain16_pre_act_pool_anymap(xs, wq, Cout, save, out=None, a=None, yP=None, y=None):
+    """conv3x3_plain16_pre_act_pool_ragged on a map of ANY H and W (onet_conv3x3_plain16_fwd_pre_act_pool_anymap): the pooled maps are
+    H // 2 x W // 2 -- floor pooling, nn.MaxPool2d(2)'s; a window partly outside an odd map is pooled nowhere.  -> aP, or None."""
+    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
+        raise TypeError("conv3x3_plain16_pre_act_pool_anymap: xs and wq must be one-part bf16 packs on the GPU")
+    return _pre_act("onet_conv3x3_plain16_fwd_pre_act_pool_anymap", "conv3x3_pre16_act_pool_kernel", 1, 32, xs, wq, Cout, save, out, None, a, (), (),
+                    pooled=(yP, y), ragged="anymap")
 
 
 def conv3x3_plain16_pre_plain_ragged(xs, wq, Cout, out=None):
