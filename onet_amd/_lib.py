@@ -1,6 +1,7 @@
 """ctypes binding of libonet_hip.so (C ABI: include/onet_hip.h, include/onet_hip_eval.h for the validation step and
 include/onet_hip_ragged.h / include/onet_hip_ragged_split.h for the one-part / fp16 two-part eval plan on ragged maps,
-include/onet_hip_anymap.h for the one-part plan's levels on maps of any size).
+include/onet_hip_anymap.h for the one-part plan's levels on maps of any size, include/onet_hip_pairs.h for its bottom level on
+image-pair tiles).
 
 The prototypes are PARSED from the header, so the Python side cannot drift from
 the ABI.  There is no CPU fallback: if the library cannot be loaded (or built),
@@ -22,6 +23,8 @@ RAGGED_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_ragged.
 RAGGED_SPLIT_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_ragged_split.h")
 # ... and of the one-part plan's levels below the first on maps of any size (Settings.fused_eval = "bf16+pool+anymap")
 ANYMAP_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_anymap.h")
+# ... and of its bottom level, maps 16 pixels wide or narrower on image-pair tiles (Settings.fused_eval = "bf16+pool+anymap+pairs")
+PAIRS_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_pairs.h")
 LIBPATH = os.environ.get("ONET_HIP_LIB") or os.path.join(HERE, "libonet_hip.so")
 
 _CT = {
@@ -80,7 +83,7 @@ def load(build_if_missing: bool = True):
         _build.build()
     lib = ctypes.CDLL(LIBPATH)
     _protos = {}
-    for header in (HEADER, EVAL_HEADER, RAGGED_HEADER, RAGGED_SPLIT_HEADER, ANYMAP_HEADER):
+    for header in (HEADER, EVAL_HEADER, RAGGED_HEADER, RAGGED_SPLIT_HEADER, ANYMAP_HEADER, PAIRS_HEADER):
         protos = parse_header(header)
         for name, (restype, argtypes, _) in protos.items():
             try:

@@ -26,6 +26,7 @@
 #include "../../include/onet_hip_ragged.h"
 #include "../../include/onet_hip_ragged_split.h"
 #include "../../include/onet_hip_anymap.h"
+#include "../../include/onet_hip_pairs.h"
 
 using namespace onet;
 
@@ -652,7 +653,7 @@ struct SpPreArgs {
     const float* rd_z = nullptr;
     union { int64_t rd_z_bs = 0; int64_t pl_y_bs; };
     const float* rd_save = nullptr;
-    int rd_gimg = 0;
+    union { int rd_gimg = 0; int n_img; };     // (n_img: the image count of an activation launch on image-pair tiles, see below)
     float* rd_rec = nullptr;
     unsigned* rd_amax = nullptr;
     // conv3x3_pre16_kernel, plain bf16 operands (BASELINE configs[2]): z16 -- the output z is STORED as bf16 (rounded once, to nearest
@@ -688,6 +689,10 @@ struct SpPreArgs {
     // bn_relu_apply_pool_split_kernel writes from a stored z, bit for bit.  The four fields share the storage of hd_L, hd_L_bs, hd_V and
     // rd_z_bs above -- epilogues POOL excludes (HEAD, RD) -- so that the kernel-argument block, and with it the code of every other
     // instance, keeps its size and layout
+    // conv3x3_pre16_kernel<false, 2, W16 = true, false, ACT = true> (round 16, include/onet_hip_pairs.h: the eval plan's bottom level, maps
+    // of any H and 0 < W <= 16): the activation epilogue on image-pair tiles.  B counts the cdiv(n_img, 2) pairs and n_img (the storage
+    // of rd_gimg: RD and ACT exclude each other) the images -- with an odd count the last tile holds ONE image: its second half stages
+    // the out-of-range offset, stores nothing, and the tile's buffer resource ends with the first image
 };
 
 // PM: 0 = bf16 (hi | mid) parts, 1 = fp16 (hi | mid) parts -- three MFMAs per term on 16-channel chunks; 2 = PLAIN bf16 operands
@@ -1223,7 +1228,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     static_assert(!ANY || (ACT && PM == 2 && !RAG), "conv3x3_pre16_kernel: the any-map instance is the one-part activation epilogue's");
     static_assert(!POOL || ACT, "conv3x3_pre16_kernel: the pooled stores ride on the activation epilogue");
     static_assert(!RAG || (POOL && PM == 2), "conv3x3_pre16_kernel: the ragged instance is the one-part pooled epilogue's");
-    static_assert(!ACT || (PM == 2 && !ST && !W16 && !RD), "conv3x3_pre16_kernel: the activation epilogue goes with the one-part bf16 slot store");
+    static_assert(!ACT || (PM == 2 && !ST && !RD && (!W16 || !(POOL || RAG || ANY))),
+                  "conv3x3_pre16_kernel: the activation epilogue goes with the one-part bf16 slot store; on image-pair tiles: no pooled, ragged or any-map twin");
     static_assert(!HEAD || (PM != 0 && !ST && !W16 && !RD && !ACT), "conv3x3_pre16_kernel: the head epilogue replaces every store of a plain forward launch");
     using C = SpPreCfg<W16>;
     static_assert(C::NW == 8 && C::NT == 2, "conv3x3_pre16_kernel: 8 waves of 2 rows");
@@ -1232,6 +1238,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     constexpr int NII = (2 * IN_PART + 511) / 512;
     constexpr int CH_OFF = W16 ? 18 : 16;                              // column of the second 16-pixel tile in the halo image
     constexpr int NSTEP = PM == 2 ? 9 : 14;
+    constexpr bool PAIRS = W16 && ACT;                                 // the activation epilogue on image-pair tiles (SpPreArgs::n_img)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];
     u32x4s* lds = reinterpret_cast<u32x4s*>(smem_s);
 
@@ -1262,8 +1269,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
     auto setup_stage = [&]() __attribute__((always_inline)) {
         const bool live = st_tile < t_end;
         const auto [co0, tx, ty, b, y0, x0] = sp_tile(live ? st_tile : t_first, a.coTiles, a.tilesX, a.tilesY);
+        // (PAIRS: the last tile of an odd image count holds one image -- the resource ends with it, its second half is out of range)
+        const bool img1 = !PAIRS || 2 * b + 1 < a.n_img;
         xr = sp_rsrc4(reinterpret_cast<const unsigned*>(a.xs) + (int64_t)(W16 ? 2 * b : b) * a.xs_bs,
-                      (W16 ? a.xs_bs * 4 : 0) + (int64_t)a.Cin * HW * (PM == 2 ? 2 : 4));
+                      (W16 && img1 ? a.xs_bs * 4 : 0) + (int64_t)a.Cin * HW * (PM == 2 ? 2 : 4));
 #pragma unroll
         for (int k = 0; k < NII; ++k) {
             const int i = (wn + 8 * k) * 64 + lane;
@@ -1271,7 +1280,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
             const int r = pix / IN_COLS, c = pix % IN_COLS;
             const int img = W16 ? c / 18 : 0;
             const int yy = y0 - 1 + r, xx = W16 ? c % 18 - 1 : x0 - 1 + c;
-            const bool ok = live && i < 2 * IN_PART && pix < C::NPIX && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
+            const bool ok = live && i < 2 * IN_PART && pix < C::NPIX && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W && (!PAIRS || img == 0 || img1);
             const unsigned io = W16 ? (unsigned)(img * a.xs_bs * 4) : 0u;
             in_off[k] = !ok ? OOB_S : PM == 2 ? io + (unsigned)(((ph * a.H + yy) * a.W + xx) * 16)
                                               : io + (unsigned)(((((ph & 1) * a.H + yy) * 2 + (ph >> 1)) * a.W + xx) * 16);
@@ -1620,14 +1629,18 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
                     const i32x4s e2 = {__builtin_amdgcn_update_dpp(vb.x, va.x, 0x128, 0xf, 0x3, false), __builtin_amdgcn_update_dpp(vb.y, va.y, 0x128, 0xf, 0x3, false),
                                        __builtin_amdgcn_update_dpp(vb.z, va.z, 0x128, 0xf, 0x3, false), __builtin_amdgcn_update_dpp(vb.w, va.w, 0x128, 0xf, 0x3, false)};
                     const f32x4s d1 = __builtin_bit_cast(f32x4s, e1), d2 = __builtin_bit_cast(f32x4s, e2);
-                    if constexpr (PM == 2 && !ST && !W16 && !RD) {
+                    if constexpr (PM == 2 && !ST && (!W16 || ACT) && !RD) {
+                        // (PAIRS: after the exchange a lane's half IS the image of the pair -- d1, d2 hold that image's pixels 4 lq .. + 3)
+                        const int img = PAIRS ? 2 * b + half : b;
+                        const bool img_ok = !PAIRS || img < a.n_img;
                         if constexpr (ACT) {
                             // the activation in fp32 NCHW too, for a reader that takes no slots: the plain z store's float4s
-                            if constexpr (ANY) {
-                                // no row alignment, and the map may end inside the lane's four pixels: one guard per float
-                                if (a.act_a && yo < a.H && xo < a.W) {
+                            if constexpr (ANY || PAIRS) {
+                                // no row alignment, and the map may end inside the lane's four pixels: one guard per float (PAIRS: the
+                                // accumulators at columns W .. 15 of a half are relu(bn(partial sums)), not zero)
+                                if (a.act_a && img_ok && yo < a.H && xo < a.W) {
                                     const int co = co0 + ct * 16 + c8;
-                                    float* o = a.act_a + (int64_t)b * a.act_a_bs + (int64_t)co * HW + (int64_t)yo * a.W + xo;
+                                    float* o = a.act_a + (int64_t)img * a.act_a_bs + (int64_t)co * HW + (int64_t)yo * a.W + xo;
 #pragma unroll
                                     for (int i = 0; i < 4; ++i)
                                         if (xo + i < a.W) {
@@ -1647,10 +1660,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pre16_kernel(SpPreArgs a) {
                             // d2 (+ 8) through pre16_slot_transpose -- lane c8 then owns the slot of group (c8 >> 2 ? B : A) at pixel c8 & 3
                             const bool o4 = (c8 & 4) != 0;
                             const u32x4s slot = pre16_slot_transpose(d1, d2, c8);
-                            const int xs = x0 + 16 * half + 4 * lq + (c8 & 3);
-                            if (yo < a.H && xs < a.W) {
+                            const int xs = (PAIRS ? 0 : x0 + 16 * half) + 4 * lq + (c8 & 3);
+                            if (img_ok && yo < a.H && xs < a.W) {
                                 const int g8 = ((co0 - a.zP_ch0) >> 3) + 2 * ct + (o4 ? 1 : 0);
-                                u32x4s* zp = reinterpret_cast<u32x4s*>(reinterpret_cast<unsigned*>(a.zP) + (int64_t)b * a.zP_bs);
+                                u32x4s* zp = reinterpret_cast<u32x4s*>(reinterpret_cast<unsigned*>(a.zP) + (int64_t)img * a.zP_bs);
                                 zp[((int64_t)g8 * a.H + yo) * a.W + xs] = slot;
                             }
                             continue;
@@ -1825,7 +1838,12 @@ int launch_split_pre(SpPreArgs a, hipStream_t st) {
     a.tilesX = W16 ? 1 : cdiv(a.W, C::TW);
     a.tilesY = cdiv(a.H, C::ROWS);
     a.coTiles = cdiv(a.Cout, C::CO_T);
-    if (W16) a.B /= 2;                               // tiles hold image pairs
+    if (W16 && ACT) {                                // tiles hold image pairs; an odd count: the last tile holds one image
+        a.n_img = a.B;
+        a.B = (a.B + 1) / 2;
+    } else if (W16) {
+        a.B /= 2;                                    // tiles hold image pairs
+    }
     const int64_t tiles = (int64_t)a.B * a.tilesX * a.tilesY * a.coTiles;
     ONET_REQUIRE(tiles > 0 && tiles < (1ll << 31), "conv3x3_split_pre: tile count %lld out of range", (long long)tiles);
     // which launches take the 16x16x32 kernel (profiles/r05_mfma_shape_ab.md): plain bf16 operands (K = 32 channels: no packing) always; the
@@ -1841,7 +1859,7 @@ int launch_split_pre(SpPreArgs a, hipStream_t st) {
     return sp_launch_persistent(kern, attr_once, LDS_BYTES, tiles, C::NW * 64,
                                 HEAD   ? (PM == 2 ? "conv3x3_pre16_head_kernel" : "conv3x3_split_pre_head_kernel")
                                 : POOL ? (PM == 2 ? "conv3x3_pre16_act_pool_kernel" : "conv3x3_split_pre_act_pool_kernel")
-                                : ACT  ? (PM == 2 ? "conv3x3_pre16_act_kernel" : "conv3x3_split_pre_act_kernel")
+                                : ACT  ? (W16 ? "conv3x3_pre16_act_pairs_kernel" : PM == 2 ? "conv3x3_pre16_act_kernel" : "conv3x3_split_pre_act_kernel")
                                       : "conv3x3_split_pre_kernel", a, st);
 }
 
@@ -3017,6 +3035,34 @@ int onet_conv3x3_plain16_fwd_pre_act_pool_anymap(const void* xs, int64_t xs_bs, 
     p.pl_y = y;
     p.pl_y_bs = y_bs;
     return launch_split_pre<false, 2, false, false, true, false, true, false, true>(p, as_stream(stream));
+}
+
+// The one-part _act entry on IMAGE-PAIR tiles (include/onet_hip_pairs.h, round 16): maps of any H and 0 < W <= 16 -- the bottom level of
+// the eval plan (16 x 16, 14 x 14, 12 x 12) -- two images side by side in a tile's 32 columns, each with its own halo columns
+// (SpPreCfg<true>), where the any-map entry walks one half-empty tile per image.  On the map, value for value, what that entry writes:
+// the same chunks and taps in the same order per pixel, the same epilogue expressions.  Any batch size: the last tile of an odd one
+// holds one image.  Returns 1 (nothing launched, nothing written) for W > 16, Cin % 32, Cout % 64, a non-NULL a_amax or an image pair
+// beyond the buffer-resource range.
+int onet_conv3x3_plain16_fwd_pre_act_pairs(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
+                                           void* a_amax, float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    const char* entry = "conv3x3_plain16_fwd_pre_act_pairs";
+    ONET_REQUIRE(xs && wq && save && aP, "%s: null pointer", entry);
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
+    if (W > 16 || !anymap_domain(a_amax, Cin, Cout, H, W)) return 1;
+    // a tile's buffer resource spans an image pair: the batch stride, then one image and the chunk the staging runs ahead by
+    if (xs_bs > (1ll << 29) || xs_bs * 4 + (int64_t)(Cin + 32) * H * W * 4 >= (1ll << 31)) return 1;
+    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 2, Cin, Cout, H, W)) return rc;
+    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "%s: 16-byte aligned slots required", entry);
+    ONET_REQUIRE(!a || (reinterpret_cast<uintptr_t>(a) & 3) == 0, "%s: 4-byte aligned floats required", entry);
+    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W / 2 && (!a || a_bs >= (int64_t)Cout * H * W), "%s: batch stride too small", entry);
+    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, nullptr, 0, nullptr, 0};
+    p.zP = aP;
+    p.zP_bs = aP_bs;
+    p.zP_ch0 = 0;
+    p.act_save = save;
+    p.act_a = a;
+    p.act_a_bs = a_bs;
+    return launch_split_pre<false, 2, true, false, true>(p, as_stream(stream));
 }
 
 int onet_conv3x3_split_fwd_pre_act_pool(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,

@@ -59,6 +59,16 @@ lies outside the ragged domain; on every other level the launches are those of "
 diffX // 2; the pad strip zeroed first), then one conversion pass -- where its output must be padded (level k is odd) or its input map
 has odd w: the slot-operand GEMM keeps its dense 2h x 2w, even-w domain.  The lower level's last unit then also writes fp32 (keep_fp32).
 
+Settings.fused_eval = "bf16+pool+anymap+pairs" (ops.fused_eval_pairs()): the plan of "bf16+pool+anymap" at FULL depth.  Level 4 -- down4.c1,
+down4.c2 and the ConvTranspose2d of up1 that reads them -- is 16 x 16, 14 x 14 and 12 x 12 for inputs of 256, 224 and 200 pixels: maps
+the predicates above refuse (W > 16) because one image fills at most half of a 16 x 32 tile.  Under this value level 4, and level 4
+alone, takes ops.eval_layer_ok_pairs: a map of ops.PAIRS_MIN_W <= W <= 16 runs ops.conv3x3_plain16_pre_act_pairs (include/
+onet_hip_pairs.h), TWO images side by side per tile, and is marked _Level.ragged = "pairs".  The level has no pooled unit and no head;
+its input is the pooled slots of down3.c2 (the any-map / ragged / full-tile _act_pool launch of level 3), its output goes to the
+ConvTranspose2d by the routes above (slots where h w % 128 == 0, the ragged slot GEMM for even w, `pack` with keep_fp32 elsewhere).  A
+level k < 4 whose map is 16 pixels wide or narrower stays a fall-back level (its pooled unit would need a pooled pair launch), so an
+input whose level 4 is wider than 16 pixels or narrower than the floor launches what "bf16+pool+anymap" launches: the same bits.
+
 The validation step (validate, EvalCounts): the scores of a batch -- by the labels-only plan where it applies, the ordinary forward
 elsewhere -- then ONE launch (ops.score_counts) that forms the labels and adds each image's confusion counts against the ground truth
 into a device tensor; nothing synchronises, and metrics.epoch_metrics turns an epoch's rows into the reference's metrics on the host.
@@ -99,8 +109,10 @@ def _units(blk):
 # (anymap: the layer predicate and the launches of a level k >= 1 whose map lies outside the ragged domain -- None: no such level)
 _Format = namedtuple("_Format", "operands parts pack layer_ok act act_pool head magnitude trace_pool ragged anymap", defaults=(None, None))
 _Ragged = namedtuple("_Ragged", "act act_pool head plain")
-_AnyMap = namedtuple("_AnyMap", "layer_ok act act_pool")
+# (pairs_ok, pairs_act: the layer predicate and the launch of level 4 on maps no wider than 16 pixels -- None: such a level is not fused)
+_AnyMap = namedtuple("_AnyMap", "layer_ok act act_pool pairs_ok pairs_act", defaults=(None, None))
 _ANYMAP = _AnyMap(ops.eval_layer_ok_anymap, ops.conv3x3_plain16_pre_act_anymap, ops.conv3x3_plain16_pre_act_pool_anymap)
+_ANYMAP_PAIRS = _ANYMAP._replace(pairs_ok=ops.eval_layer_ok_pairs, pairs_act=ops.conv3x3_plain16_pre_act_pairs)
 _RAGGED = _Ragged(ops.conv3x3_plain16_pre_act_ragged, ops.conv3x3_plain16_pre_act_pool_ragged, ops.conv3x3_plain16_pre_head_ragged,
                   ops.conv3x3_plain16_pre_plain_ragged)
 _RAGGED_FP16 = _Ragged(ops.conv3x3_split_pre_act_ragged, ops.conv3x3_split_pre_act_pool_ragged, ops.conv3x3_split_pre_head_ragged,
@@ -116,7 +128,7 @@ def _format():
         # (trace_pool: the one-part plan's trace is complete -- every convolution's exact input can be rebuilt)
         return _Format(name, 1, "plain16", ops.eval_layer_ok_ragged if rag else ops.eval_layer_ok_bf16, ops.conv3x3_plain16_pre_act,
                        ops.conv3x3_plain16_pre_act_pool, ops.conv3x3_plain16_pre_head, False, True, _RAGGED if rag else None,
-                       _ANYMAP if ops.fused_eval_anymap() else None)
+                       (_ANYMAP_PAIRS if ops.fused_eval_pairs() else _ANYMAP) if ops.fused_eval_anymap() else None)
     return _Format(name, 2, "split", ops.eval_layer_ok_ragged_fp16 if rag else ops.eval_layer_ok, ops.conv3x3_split_pre_act,
                    ops.conv3x3_split_pre_act_pool, ops.conv3x3_split_pre_head, True, False, _RAGGED_FP16 if rag else None)
 
@@ -158,9 +170,10 @@ def _level_layers(unet):
     return [[(name, conv) for name, conv, _ in e + d] for e, d in _level_units(unet)]
 
 
-def _depth(units, ups, layer_ok, N, H, W, anymap_ok=None):
+def _depth(units, ups, layer_ok, N, H, W, anymap_ok=None, pairs_ok=None):
     """-> (d, why level d is not fused | None): levels 0 .. d - 1 are fused.  anymap_ok: the predicate of the levels k >= 1 of a plan
-    that takes maps of any size there -- level k is then H >> k x W >> k (floor pooling) whatever the input's divisibility"""
+    that takes maps of any size there -- level k is then H >> k x W >> k (floor pooling) whatever the input's divisibility;
+    pairs_ok: the predicate of level 4 of such a plan where that level's map is 16 pixels wide or narrower"""
     level0_ok = layer_ok
     for k, (e, d) in enumerate(units):
         if anymap_ok is None and ((H % (1 << k)) or (W % (1 << k))):
@@ -170,8 +183,12 @@ def _depth(units, ups, layer_ok, N, H, W, anymap_ok=None):
             if h <= 0 or w <= 0:
                 return k, f"level {k}: the map is empty"
             layer_ok = anymap_ok if k else level0_ok
+            if pairs_ok is not None and k == 4 and w <= 16:
+                layer_ok = pairs_ok
         for name, conv, _ in e + d:
             if not layer_ok(N, conv.in_channels, conv.out_channels, h, w):
+                if layer_ok is pairs_ok:
+                    return k, f"level {k}: {name} ({conv.in_channels} -> {conv.out_channels} on {N} maps of {h} x {w}) is outside ops.{pairs_ok.__name__}"
                 # (on a map made of full tiles, or no wider than 16 pixels, the ragged predicate IS eval_layer_ok_bf16, and the reason
                 # says so: the answer of "bf16+pool")
                 full = {ops.eval_layer_ok_ragged: ops.eval_layer_ok_bf16, ops.eval_layer_ok_ragged_fp16: ops.eval_layer_ok}.get(layer_ok)
@@ -207,7 +224,8 @@ _Unit = namedtuple("_Unit", "name conv bn kind keep_fp32")
 # One level: its encoder and decoder units in execution order, the ConvTranspose2d that fills its concat buffer with its kind ("slots":
 # from the slots of the level below; "fp32->slots": from an fp32 tensor; level 4 has none), and whether the pooled tensor leaves as
 # slots (fp32: for the fall-back levels); ragged: the level's maps are not made of full tiles, its units take the format's ragged
-# launches ("anymap": the map also lies outside the ragged domain, its units take the format's any-map launches); route: the launch(es)
+# launches ("anymap": the map also lies outside the ragged domain, its units take the format's any-map launches; "pairs": level 4 on maps
+# no wider than 16 pixels, its units take the image-pair launch); route: the launch(es)
 # behind `convt` -- "slots" / "slots_ragged" (the slot-operand GEMM, on maps with h w % 128 != 0 its ragged entry), "gemm" (the fp32-operand GEMM that writes slots) / "pack" (where that GEMM does not take the map, h w % 128 != 0: the general
 # ConvTranspose2d into an fp32 tensor, then one conversion pass into the concat buffer's up-sampled groups; also wherever the output must be
 # padded into the concat buffer or the input map has odd w -- any-map levels)
@@ -231,7 +249,7 @@ def _build_plan(unet, shape, head=None):
     if C != unet.inc.double_conv[0].in_channels:
         return _Plan(fmt, N, _WHY_CHANNELS)
     units, ups = _level_units(unet), _blocks(unet)[2]
-    d, why_d = _depth(units, ups, fmt.layer_ok, N, H, W, fmt.anymap.layer_ok if fmt.anymap else None)
+    d, why_d = _depth(units, ups, fmt.layer_ok, N, H, W, fmt.anymap.layer_ok if fmt.anymap else None, fmt.anymap.pairs_ok if fmt.anymap else None)
     if d == 0:
         return _Plan(fmt, N, why_d, None, 0, why_d)
     # the ConvTranspose2d of level k reads the output of level k + 1: slots where that level is fused and the slot-operand kernel takes
@@ -266,14 +284,18 @@ def _build_plan(unet, shape, head=None):
         keep = {(dec or e)[-1][0]} if 0 < k < d and convt[k - 1] == "fp32->slots" else ()
         enc_u, dec_u = ([_Unit(name, conv, bn, kind[name], name in keep) for name, conv, bn in us] for us in (e, dec))
         levels.append(_Level(enc_u, dec_u, ups[k].up if k < 4 else None, convt[k] if k < 4 else None, k + 1 < d,
-                             _level_ragged(k < d, H >> k, W >> k), edges[k][1] if k < 4 else None))
+                             _level_ragged(k < d, H >> k, W >> k, k == 4 and fmt.anymap is not None and fmt.anymap.pairs_ok is not None),
+                             edges[k][1] if k < 4 else None))
     return _Plan(fmt, N, None, None, d, why_d, unet, tuple(levels), with_head)
 
 
-def _level_ragged(fused, h, w):
-    """_Level.ragged of a level of h x w maps: False (fall-back, or full tiles), True (the ragged launches), "anymap" """
+def _level_ragged(fused, h, w, pairs=False):
+    """_Level.ragged of a level of h x w maps: False (fall-back, or full tiles), True (the ragged launches), "anymap", "pairs" (pairs:
+    level 4 of a plan that takes it on image-pair tiles -- a fused map no wider than 16 pixels is there by that predicate alone)"""
     if not fused or ops.full_tiles(h, w):
         return False
+    if pairs and w <= 16:
+        return "pairs"
     return True if ops._ragged_map(h, w) else "anymap"
 
 
@@ -436,7 +458,7 @@ def _fused_unit(fmt, u, t, ragged=False):
     amax = ops.new_amax(t.P.device) if fmt.magnitude else None
     a = torch.empty((B, conv.out_channels, H, W), dtype=torch.float32, device=t.P.device) if u.keep_fp32 else None
     # (a ragged launch takes its sibling's magnitude-slot arguments: none on the one-part format, whose ragged entries record no maximum)
-    launch = fmt.anymap.act if ragged == "anymap" else fmt.ragged.act if ragged else fmt.act
+    launch = fmt.anymap.pairs_act if ragged == "pairs" else fmt.anymap.act if ragged == "anymap" else fmt.ragged.act if ragged else fmt.act
     aP = launch(t.P, _wq(fmt, conv), conv.out_channels, save, a=a, **_slot_kw(fmt, t, aP_slots=scale, a_amax=amax))
     if aP is None:
         raise RuntimeError(f"onet_amd: the fused eval kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")

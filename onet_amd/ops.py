@@ -75,6 +75,10 @@ class Settings:
                     "bf16+pool+anymap": the plan of "bf16+pool+ragged" whose levels below the first also take maps of ANY H and W, odd
                     included (fused_eval_anymap(), eval_layer_ok_anymap: 200 x 200 down to its 25-pixel level; floor pooling, the
                     reference's F.pad); on every map "bf16+pool+ragged" takes, its launches and bits.
+                    "bf16+pool+anymap+pairs": the plan of "bf16+pool+anymap" whose BOTTOM level (level 4: down4 and the ConvTranspose2d
+                    of up1) is fused too where its map is 16 pixels wide or narrower (fused_eval_pairs(), eval_layer_ok_pairs: 256 x 256,
+                    224 x 224 and 200 x 200 at full depth), two images per tile (include/onet_hip_pairs.h); elsewhere the launches
+                    and bits of "bf16+pool+anymap".
                     Any other string is a ValueError where the setting is read"""
     __slots__ = ("conv", "twin", "convt_bf16", "lazy_nan", "split", "bn_on_load", "split_f16", "grad_f16", "split_dgrad",
                  "stem_fused", "sync_bn", "presplit", "z_bf16", "fused_eval")
@@ -175,10 +179,11 @@ def presplit():
 # The string values of Settings.fused_eval -> (slot format, pooled units in one launch[, ragged levels]); True is ("fp16x2", False)
 _FUSED_EVAL_VALUES = {"bf16": ("bf16", False), "fp16x2+pool": ("fp16x2", True), "bf16+pool": ("bf16", True),
                       "bf16+pool+ragged": ("bf16", True, True), "fp16x2+ragged": ("fp16x2", True, True),
-                      "bf16+pool+anymap": ("bf16", True, True, True)}
+                      "bf16+pool+anymap": ("bf16", True, True, True), "bf16+pool+anymap+pairs": ("bf16", True, True, True, True)}
 # 1: eval forwards under no_grad take the fused inference plan (Settings.fused_eval); bf16: its one-part plain-bf16 form; either with
 # "+pool" ("fp16x2+pool", "bf16+pool"): the pooled units in one launch; "bf16+pool+ragged" / "fp16x2+ragged" ("+pool" implied): ... on
-# maps not made of full tiles too; "bf16+pool+anymap": the plan of "bf16+pool+ragged" whose levels below the first take maps of any H and W
+# maps not made of full tiles too; "bf16+pool+anymap": the plan of "bf16+pool+ragged" whose levels below the first take maps of any H and W;
+# "bf16+pool+anymap+pairs": the plan of "bf16+pool+anymap" with level 4 fused on image-pair tiles where its map is at most 16 pixels wide
 #   value                format    pooled units    ragged levels    layer predicate
 #   True                 fp16x2    two passes      no               eval_layer_ok
 #   "fp16x2+pool"        fp16x2    one launch      no               eval_layer_ok
@@ -187,6 +192,7 @@ _FUSED_EVAL_VALUES = {"bf16": ("bf16", False), "fp16x2+pool": ("fp16x2", True), 
 #   "bf16+pool"          bf16      one launch      no               eval_layer_ok_bf16
 #   "bf16+pool+ragged"   bf16      one launch      yes              eval_layer_ok_ragged
 #   "bf16+pool+anymap"   bf16      one launch      yes, any map     eval_layer_ok_ragged (level 0), eval_layer_ok_anymap (below)
+#   "bf16+pool+anymap+pairs"  bf16  one launch     yes, any map     ... and eval_layer_ok_pairs (level 4)
 FUSED_EVAL = _FLAGS["FUSED_EVAL"] if _FLAGS.get("FUSED_EVAL") in _FUSED_EVAL_VALUES else _flag("FUSED_EVAL", False)
 
 
@@ -228,6 +234,13 @@ def fused_eval_anymap():
     "bf16+pool+anymap": the entry points of include/onet_hip_anymap.h, layer predicate eval_layer_ok_anymap)?  Implies
     fused_eval_ragged(): level 0 and every map of even H and W % 4 == 0 run what "bf16+pool+ragged" runs."""
     return len(_fused_eval_value()) > 3
+
+
+def fused_eval_pairs():
+    """Does the fused eval plan take its bottom level (level 4) on image-pair tiles where that level's map is 16 pixels wide or narrower
+    (Settings.fused_eval = "bf16+pool+anymap+pairs": the entry point of include/onet_hip_pairs.h, layer predicate eval_layer_ok_pairs)?
+    Implies fused_eval_anymap(): every other level runs what "bf16+pool+anymap" runs."""
+    return len(_fused_eval_value()) > 4
 
 
 Z_BF16 = _flag("Z_BF16", True)       # BASELINE configs[2] (conv == "bf16", pre-split operands): conv outputs stored as bf16 (Settings.z_bf16)
@@ -1371,6 +1384,30 @@ def eval_layer_ok_anymap(B, Cin, Cout, H, W):
     return B * -(-H // 16) * -(-W // 32) * (Cout // 64) >= (n_cu() * 3) // 4
 
 
+# The narrowest map eval_layer_ok_pairs takes: a map of 8 or fewer columns fills at most half of each image's half of a pair tile -- the
+# argument of the W > 16 rule above, one size down (four images per tile would be the answer there), not a measurement
+PAIRS_MIN_W = int(_FLAGS.get("PAIRS_MIN_W", 9))
+# tools/time_pairs_eval.py's diagnostic: the maps eval_layer_ok_pairs adds are launched one image per (half-empty) tile by the any-map
+# entry -- what pairing itself is worth
+PAIRS_SINGLE = _flag("PAIRS_SINGLE", False)
+
+
+def eval_layer_ok_pairs(B, Cin, Cout, H, W):
+    """eval_layer_ok_anymap for level 4 of Settings.fused_eval = "bf16+pool+anymap+pairs": on W > 16 that predicate's answer; on
+    PAIRS_MIN_W <= W <= 16 the domain of onet_conv3x3_plain16_fwd_pre_act_pairs -- any H > 0, Cin % 32 == 0, Cout % 64 == 0, inside the
+    buffer-resource range, with pre-split storage on.  conv in ("bf16", "split"): every such layer; otherwise the fill rule on the tiles
+    the kernel walks, which hold two images each: cdiv(B, 2) cdiv(H, 16) Cout / 64 >= 3/4 n_cu."""
+    if W > 16:
+        return eval_layer_ok_anymap(B, Cin, Cout, H, W)
+    if not presplit():
+        return False
+    if Cin % 32 or Cout % 64 or B <= 0 or H <= 0 or W < max(PAIRS_MIN_W, 1) or not _in_buffer_range(Cin, Cout, H, W):
+        return False
+    if conv_algo() in ("bf16", "split"):
+        return True
+    return -(-B // 2) * -(-H // 16) * (Cout // 64) >= (n_cu() * 3) // 4
+
+
 def eval_layer_ok_ragged_fp16(B, Cin, Cout, H, W):
     """eval_layer_ok for Settings.fused_eval = "fp16x2+ragged": the domain of onet_conv3x3_split_fwd_pre_act_ragged -- fp16 (hi | mid)
     parts with pre-split storage, Cin % 16 == 0, Cout % 64 == 0, even H and W % 4 == 0 (_ragged_map: the kernel's own slot stores are
@@ -1394,7 +1431,8 @@ def _pre_act(entry, kind, two, cin_mult, xs, wq, Cout, save, out, a_amax, a, ext
     if pooled is not None and pooled[0] is None and pooled[1] is None:
         raise ValueError(f"{entry[len('onet_'):]}: a pooled destination is required (yP, y or both)")
     # (ragged = "anymap": the entries of include/onet_hip_anymap.h -- every map below 2^24 pixels)
-    map_ok = (0 < H * W < 2 ** 24) if ragged == "anymap" else _ragged_map(H, W) if ragged else full_tiles(H, W)
+    # (ragged = "pairs": the entry of include/onet_hip_pairs.h -- any H on 0 < W <= 16)
+    map_ok = (0 < H * W < 2 ** 24 and (ragged == "anymap" or W <= 16)) if ragged in ("anymap", "pairs") else _ragged_map(H, W) if ragged else full_tiles(H, W)
     if not map_ok or Cin % cin_mult or Cout % 64:
         return None
     if out is None:
@@ -1451,6 +1489,17 @@ def conv3x3_plain16_pre_act_anymap(xs, wq, Cout, save, out=None, a=None):
     if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
         raise TypeError("conv3x3_plain16_pre_act_anymap: xs and wq must be one-part bf16 packs on the GPU")
     return _pre_act("onet_conv3x3_plain16_fwd_pre_act_anymap", "conv3x3_pre16_act_kernel", 1, 32, xs, wq, Cout, save, out, None, a, (), (), ragged="anymap")
+
+
+def conv3x3_plain16_pre_act_pairs(xs, wq, Cout, save, out=None, a=None):
+    """conv3x3_plain16_pre_act_anymap on maps of 0 < W <= 16 and any H, on IMAGE-PAIR tiles (onet_conv3x3_plain16_fwd_pre_act_pairs): two
+    images of the batch side by side in a tile's 32 columns; the same values.  Any batch size (an odd one: the last tile holds one
+    image).  -> aP, or None where the kernel does not take the shape (nothing launched)."""
+    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
+        raise TypeError("conv3x3_plain16_pre_act_pairs: xs and wq must be one-part bf16 packs on the GPU")
+    if PAIRS_SINGLE:
+        return conv3x3_plain16_pre_act_anymap(xs, wq, Cout, save, out=out, a=a)
+    return _pre_act("onet_conv3x3_plain16_fwd_pre_act_pairs", "conv3x3_pre16_act_pairs_kernel", 1, 32, xs, wq, Cout, save, out, None, a, (), (), ragged="pairs")
 
 
 def conv3x3_plain16_pre_act_pool_anymap(xs, wq, Cout, save, out=None, a=None, yP=None, y=None):
