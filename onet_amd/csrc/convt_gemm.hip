@@ -25,6 +25,7 @@
 #include "common.hpp"
 #include "../../include/onet_hip_ragged.h"
 #include "../../include/onet_hip_ragged_split.h"
+#include "../../include/onet_hip_upmap.h"
 
 using namespace onet;
 
@@ -558,6 +559,7 @@ struct SArgs {
     const unsigned* x_slots;       // NP = 2: the magnitude slots x's producer scaled it by (guard rule; NULL: unscaled)
     const unsigned* y_slots;       // NP = 2: ... and those the output is scaled by (guard rule; NULL: unscaled)
     int B, Cin, Ct, h, w, mTiles, nTiles;
+    int Ho, Wo;                    // the output map per channel group in slots: 2h x 2w; ANY: up to one row / one column more
 };
 
 template <int NP>
@@ -580,10 +582,17 @@ __device__ __forceinline__ void slot_wait() {
 // own values are those of the full-tile instance on the map with zero rows appended.  NP = 2 (round 14:
 // onet_convT2x2_fwd_slots_split_ragged): the same three rules on both parts of a slot -- the offset of a pixel p >= h w is out of range
 // whatever its part, and the magnitude slots of input and output apply as in the full-tile instance.
+// ANY (round 17: onet_convT2x2_fwd_slots_anymap, NP = 1 and RAG only): w may be odd -- the staging divides p by w per slot and a slot is
+// 16 bytes whatever w is -- and the output map is Ho x Wo slots per channel group, Ho in {2h, 2h + 1}, Wo in {2w, 2w + 1}: the concat
+// map of a floor-pooled level, the up-sampled block in its top-left corner (the reference's F.pad offsets diff // 2 are 0).  The pad
+// strip -- column 2w, row 2h -- is written here as all-zero slots: the lane that owns input column w - 1 adds column 2w of its output
+// row, the lane that owns input row h - 1 and output row di = 1 adds its two columns of row 2h (and the corner).  Every (channel
+// group, pixel, di) belongs to exactly one lane behind the lane exchange, so each slot of the strip is stored once.
 constexpr unsigned SLOT_OOB = 0x80000000u;        // beyond every resource (< 2 GiB, host-checked), chunk steps included
-template <int NP, bool RAG = false>
+template <int NP, bool RAG = false, bool ANY = false>
 __global__ __launch_bounds__(256, SLOT_OCC) void convt_slot_fwd_kernel(SArgs g) {
-    constexpr int KS = 4 / NP;                     // slots (8 channels each) per chunk: 16 channels (NP = 2) / 32 (NP = 1)
+    static_assert(!ANY || (NP == 1 && RAG), "the any-map output geometry exists on the one-part ragged instance alone");
+    constexpr int KS = 4 / NP;                    // slots (8 channels each) per chunk: 16 channels (NP = 2) / 32 (NP = 1)
     constexpr int TILE = KS * NP * 128;            // slots of one operand tile: [slot of the chunk][part][row / pixel] = 8 KB
     constexpr int NPC = TILE / 256;                // DMA pieces (64 slots) per wave, operand and chunk
     constexpr int NST = SLOT_NST;                  // ring of chunk buffers, the DMA NST - 1 chunks ahead.  A block lives for 8 .. 64 chunks of
@@ -723,8 +732,19 @@ __global__ __launch_bounds__(256, SLOT_OCC) void convt_slot_fwd_kernel(SArgs g) 
             if constexpr (RAG) {
                 if (p >= hw) continue;              // (behind the lane exchange: both partners hold the same pixel)
             }
+            const int Ho = ANY ? g.Ho : 2 * g.h, Wo = ANY ? g.Wo : 2 * g.w;
             u32x4g* dst = reinterpret_cast<u32x4g*>(reinterpret_cast<unsigned*>(g.yP) + (int64_t)b * g.y_bs) +
-                          ((int64_t)(c8 * (2 * g.h) + 2 * y + kh) * NP) * (2 * g.w) + 2 * x;
+                          ((int64_t)(c8 * Ho + 2 * y + kh) * NP) * Wo + 2 * x;
+            if constexpr (ANY) {
+                const u32x4g zero = {0u, 0u, 0u, 0u};
+                const bool last_col = Wo > 2 * g.w && x == g.w - 1, last_row = Ho > 2 * g.h && y == g.h - 1 && kh == 1;
+                if (last_col) dst[2] = zero;                        // (2y + kh, 2w)
+                if (last_row) {
+                    dst[Wo] = zero;                                 // (2h, 2x), (2h, 2x + 1)
+                    dst[Wo + 1] = zero;
+                    if (last_col) dst[Wo + 2] = zero;               // (2h, 2w)
+                }
+            }
 #pragma unroll
             for (int dj = 0; dj < 2; ++dj) {
                 u32x4g hi, mid;
@@ -740,7 +760,7 @@ __global__ __launch_bounds__(256, SLOT_OCC) void convt_slot_fwd_kernel(SArgs g) 
                     }
                 }
                 dst[dj] = hi;
-                if constexpr (NP == 2) dst[2 * g.w + dj] = mid;
+                if constexpr (NP == 2) dst[Wo + dj] = mid;
             }
         }
 }
@@ -1422,7 +1442,7 @@ int onet_convT2x2_fwd_slots(const void* xP, int64_t xP_bs, const void* x_amax, c
         (int64_t)Cin * hw * 2 * nparts >= (1ll << 31) || (int64_t)Cin * 4 * Ct * 2 * nparts >= (1ll << 31))
         return 1;                                              // shape outside the fast path: nothing done
     ONET_REQUIRE(xP_bs >= (int64_t)Cin * hw * nparts / 2 && yP_bs >= (int64_t)Ct * 4 * hw * nparts / 2, "convT2x2_fwd_slots: batch stride too small");
-    SArgs g{wP, xP, xP_bs, bias, yP, yP_bs, (const unsigned*)x_amax, (const unsigned*)y_amax, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)(B * hw / 128)};
+    SArgs g{wP, xP, xP_bs, bias, yP, yP_bs, (const unsigned*)x_amax, (const unsigned*)y_amax, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)(B * hw / 128), 2 * h, 2 * w};
     const int64_t blocks = (int64_t)g.mTiles * g.nTiles;
     ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "convT2x2_fwd_slots: grid too large");
     if (nparts == 2) hipLaunchKernelGGL(convt_slot_fwd_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
@@ -1442,7 +1462,7 @@ int onet_convT2x2_fwd_slots_ragged(const void* xP, int64_t xP_bs, const void* wP
     ONET_REQUIRE(xP_bs >= (int64_t)Cin * hw / 2 && yP_bs >= (int64_t)Ct * 4 * hw / 2, "convT2x2_fwd_slots_ragged: batch stride too small");
     const int64_t ntiles = (int64_t)B * ((hw + 127) / 128);
     ONET_REQUIRE(ntiles < (1ll << 24), "convT2x2_fwd_slots_ragged: grid too large");
-    SArgs g{wP, xP, xP_bs, bias, yP, yP_bs, nullptr, nullptr, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)ntiles};
+    SArgs g{wP, xP, xP_bs, bias, yP, yP_bs, nullptr, nullptr, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)ntiles, 2 * h, 2 * w};
     const int64_t blocks = (int64_t)g.mTiles * g.nTiles;
     ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "convT2x2_fwd_slots_ragged: grid too large");
     hipLaunchKernelGGL((convt_slot_fwd_kernel<1, true>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
@@ -1463,10 +1483,32 @@ int onet_convT2x2_fwd_slots_split_ragged(const void* xP, int64_t xP_bs, const vo
     if ((hw % 128) == 0) return onet_convT2x2_fwd_slots(xP, xP_bs, x_amax, wP, bias, yP, yP_bs, y_amax, 2, B, Cin, Ct, h, w, stream);
     const int64_t ntiles = (int64_t)B * ((hw + 127) / 128);
     ONET_REQUIRE(ntiles < (1ll << 24), "convT2x2_fwd_slots_split_ragged: grid too large");
-    SArgs g{wP, xP, xP_bs, bias, yP, yP_bs, (const unsigned*)x_amax, (const unsigned*)y_amax, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)ntiles};
+    SArgs g{wP, xP, xP_bs, bias, yP, yP_bs, (const unsigned*)x_amax, (const unsigned*)y_amax, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)ntiles, 2 * h, 2 * w};
     const int64_t blocks = (int64_t)g.mTiles * g.nTiles;
     ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "convT2x2_fwd_slots_split_ragged: grid too large");
     hipLaunchKernelGGL((convt_slot_fwd_kernel<2, true>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
+    return check_launch("convt_slot_fwd_kernel");
+}
+
+// onet_convT2x2_fwd_slots_ragged on a map of ANY w, odd included, into an output map of Ho x Wo slots per channel group
+// (include/onet_hip_upmap.h): the up-sampled 2h x 2w block in the top-left corner, the pad strip -- Ho - 2h, Wo - 2w in {0, 1} --
+// written as zero slots by the same launch.  Returns 1 (nothing launched) outside the domain.  Even w without a pad strip: the launch of
+// onet_convT2x2_fwd_slots_ragged.
+int onet_convT2x2_fwd_slots_anymap(const void* xP, int64_t xP_bs, const void* wP, const float* bias, void* yP, int64_t yP_bs, int B, int Cin, int Ct,
+                                   int h, int w, int Ho, int Wo, void* stream) {
+    ONET_REQUIRE(xP && wP && yP && B > 0 && Cin > 0 && Ct > 0 && h > 0 && w > 0 && Ho > 0 && Wo > 0, "convT2x2_fwd_slots_anymap: bad args");
+    const int64_t hw = (int64_t)h * w, ph = (int64_t)Ho - 2ll * h, pw = (int64_t)Wo - 2ll * w;
+    if ((Cin % 32) || Cin < 128 || (Ct % 32) || ph < 0 || ph > 1 || pw < 0 || pw > 1 || !aligned16(xP) || !aligned16(wP) || !aligned16(yP) ||
+        (xP_bs & 3) || (yP_bs & 3) || (int64_t)Cin * hw * 2 >= (1ll << 31) || (int64_t)Cin * 4 * Ct * 2 >= (1ll << 31))
+        return 1;
+    ONET_REQUIRE(xP_bs >= (int64_t)Cin * hw / 2 && yP_bs >= (int64_t)(Ct / 8) * Ho * Wo * 4, "convT2x2_fwd_slots_anymap: batch stride too small");
+    if (!(w & 1) && !ph && !pw) return onet_convT2x2_fwd_slots_ragged(xP, xP_bs, wP, bias, yP, yP_bs, B, Cin, Ct, h, w, stream);
+    const int64_t ntiles = (int64_t)B * ((hw + 127) / 128);
+    ONET_REQUIRE(ntiles < (1ll << 24), "convT2x2_fwd_slots_anymap: grid too large");
+    SArgs g{wP, xP, xP_bs, bias, yP, yP_bs, nullptr, nullptr, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)ntiles, Ho, Wo};
+    const int64_t blocks = (int64_t)g.mTiles * g.nTiles;
+    ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "convT2x2_fwd_slots_anymap: grid too large");
+    hipLaunchKernelGGL((convt_slot_fwd_kernel<1, true, true>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
     return check_launch("convt_slot_fwd_kernel");
 }
 

@@ -69,6 +69,17 @@ ConvTranspose2d by the routes above (slots where h w % 128 == 0, the ragged slot
 level k < 4 whose map is 16 pixels wide or narrower stays a fall-back level (its pooled unit would need a pooled pair launch), so an
 input whose level 4 is wider than 16 pixels or narrower than the floor launches what "bf16+pool+anymap" launches: the same bits.
 
+Settings.fused_eval = "bf16+pool+anymap+pairs+up" (ops.fused_eval_upmap()): the plan of "bf16+pool+anymap+pairs" without its `pack` route
+between fused levels.  A ConvTranspose2d edge whose input map has odd w or whose output is padded into an odd concat map -- at 200 x 200
+up1 (12 -> 24, placed in 25) and up2 (25 -> 50) -- takes route "slots_anymap" where ops.convt_slots_ok_anymap holds: ONE launch of the
+slot-operand GEMM (ops.convT2x2_fwd_slots_anymap, include/onet_hip_upmap.h) that reads the slots of the level below, puts the 2h x 2w
+block at the top-left corner of the concat map (floor pooling leaves at most one row and one column over, so the reference's F.pad
+offsets are 0) and writes the pad strip as zero slots itself -- no memset, no general kernel, no conversion pass.  Its `convt` is "slots",
+so the level below keeps no fp32 copy (keep_fp32 is empty: the pair launch of down4.c2 and the any-map launch below an odd level write
+slots alone).  The edge now reads bf16-rounded slots where `pack` read the unrounded fp32 activation: its results differ in the last
+bf16 digit, which is why this is a value of its own.  An edge from a fall-back level keeps `pack`; whole-tile and ragged even-w edges
+keep their routes: an input without such an edge (224 x 224, 256 x 256) launches what "bf16+pool+anymap+pairs" launches, the same bits.
+
 The validation step (validate, EvalCounts): the scores of a batch -- by the labels-only plan where it applies, the ordinary forward
 elsewhere -- then ONE launch (ops.score_counts) that forms the labels and adds each image's confusion counts against the ground truth
 into a device tensor; nothing synchronises, and metrics.epoch_metrics turns an epoch's rows into the reference's metrics on the host.
@@ -110,9 +121,11 @@ def _units(blk):
 _Format = namedtuple("_Format", "operands parts pack layer_ok act act_pool head magnitude trace_pool ragged anymap", defaults=(None, None))
 _Ragged = namedtuple("_Ragged", "act act_pool head plain")
 # (pairs_ok, pairs_act: the layer predicate and the launch of level 4 on maps no wider than 16 pixels -- None: such a level is not fused)
-_AnyMap = namedtuple("_AnyMap", "layer_ok act act_pool pairs_ok pairs_act", defaults=(None, None))
+# (upmap: a ConvTranspose2d edge with an odd-w input map or a padded output takes the any-map slot GEMM where its predicate holds)
+_AnyMap = namedtuple("_AnyMap", "layer_ok act act_pool pairs_ok pairs_act upmap", defaults=(None, None, False))
 _ANYMAP = _AnyMap(ops.eval_layer_ok_anymap, ops.conv3x3_plain16_pre_act_anymap, ops.conv3x3_plain16_pre_act_pool_anymap)
 _ANYMAP_PAIRS = _ANYMAP._replace(pairs_ok=ops.eval_layer_ok_pairs, pairs_act=ops.conv3x3_plain16_pre_act_pairs)
+_ANYMAP_UP = _ANYMAP_PAIRS._replace(upmap=True)
 _RAGGED = _Ragged(ops.conv3x3_plain16_pre_act_ragged, ops.conv3x3_plain16_pre_act_pool_ragged, ops.conv3x3_plain16_pre_head_ragged,
                   ops.conv3x3_plain16_pre_plain_ragged)
 _RAGGED_FP16 = _Ragged(ops.conv3x3_split_pre_act_ragged, ops.conv3x3_split_pre_act_pool_ragged, ops.conv3x3_split_pre_head_ragged,
@@ -128,7 +141,8 @@ def _format():
         # (trace_pool: the one-part plan's trace is complete -- every convolution's exact input can be rebuilt)
         return _Format(name, 1, "plain16", ops.eval_layer_ok_ragged if rag else ops.eval_layer_ok_bf16, ops.conv3x3_plain16_pre_act,
                        ops.conv3x3_plain16_pre_act_pool, ops.conv3x3_plain16_pre_head, False, True, _RAGGED if rag else None,
-                       (_ANYMAP_PAIRS if ops.fused_eval_pairs() else _ANYMAP) if ops.fused_eval_anymap() else None)
+                       (_ANYMAP_UP if ops.fused_eval_upmap() else _ANYMAP_PAIRS if ops.fused_eval_pairs() else _ANYMAP)
+                       if ops.fused_eval_anymap() else None)
     return _Format(name, 2, "split", ops.eval_layer_ok_ragged_fp16 if rag else ops.eval_layer_ok, ops.conv3x3_split_pre_act,
                    ops.conv3x3_split_pre_act_pool, ops.conv3x3_split_pre_head, True, False, _RAGGED_FP16 if rag else None)
 
@@ -228,7 +242,8 @@ _Unit = namedtuple("_Unit", "name conv bn kind keep_fp32")
 # no wider than 16 pixels, its units take the image-pair launch); route: the launch(es)
 # behind `convt` -- "slots" / "slots_ragged" (the slot-operand GEMM, on maps with h w % 128 != 0 its ragged entry), "gemm" (the fp32-operand GEMM that writes slots) / "pack" (where that GEMM does not take the map, h w % 128 != 0: the general
 # ConvTranspose2d into an fp32 tensor, then one conversion pass into the concat buffer's up-sampled groups; also wherever the output must be
-# padded into the concat buffer or the input map has odd w -- any-map levels)
+# padded into the concat buffer or the input map has odd w -- any-map levels) / "slots_anymap" (the slot-operand GEMM's any-map entry on
+# exactly those edges, under "bf16+pool+anymap+pairs+up")
 _Level = namedtuple("_Level", "enc dec up convt pooled_slots ragged route", defaults=(False, None))
 # One U-Net pass.  reason: why the plan does not run (None: it runs); static: the part of it that holds whatever the input;
 # levels 0 .. depth - 1 are fused, fallback_reason says why level `depth` is not; head: the last unit ends in the head-epilogue launch
@@ -260,7 +275,9 @@ def _build_plan(unet, shape, head=None):
             return "fallback", None
         if fmt.anymap and ((H >> k, W >> k) != (2 * h, 2 * w) or w % 2):
             # (any-map levels: the output is padded into the concat buffer -- level k is odd -- or the input map has odd w; the slot
-            # GEMMs keep their dense 2h x 2w, even-w domain)
+            # GEMMs keep their dense 2h x 2w, even-w domain -- but for the any-map entry, which takes both and writes the pad strip)
+            if fmt.anymap.upmap and k + 1 < d and ops.convt_slots_ok_anymap(N, cin, ct, h, w, H >> k, W >> k):
+                return "slots", "slots_anymap"
             return "fp32->slots", "pack"
         if k + 1 < d and ops.convt_slots_ok(N, cin, ct, h, w, parts=fmt.parts):
             return "slots", "slots"
@@ -518,6 +535,12 @@ def _conv_t(fmt, lv, t, catP, C2):
             done = ops.convT2x2_fwd_slots_ragged(t.P, packed.slots(fmt.parts), up.bias, dst, Ct)
         if not done:
             raise RuntimeError("onet_amd: the ragged slot-operand ConvTranspose2d refused a shape ops.convt_slots_ok_ragged accepted")
+        return s_up
+    if lv.route == "slots_anymap":
+        # (one-part format alone: an odd-w input map and / or an output one row, one column short of the concat map -- the launch
+        # writes the pad strip as zero slots itself)
+        if not ops.convT2x2_fwd_slots_anymap(t.P, packed.slots(1), up.bias, dst, Ct):
+            raise RuntimeError("onet_amd: the any-map slot-operand ConvTranspose2d refused a shape ops.convt_slots_ok_anymap accepted")
         return s_up
     if lv.route == "pack":
         # (the smallest maps of the pass: the general kernel into an fp32 tensor, then one conversion pass -- what the training forward

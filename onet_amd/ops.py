@@ -79,6 +79,12 @@ class Settings:
                     of up1) is fused too where its map is 16 pixels wide or narrower (fused_eval_pairs(), eval_layer_ok_pairs: 256 x 256,
                     224 x 224 and 200 x 200 at full depth), two images per tile (include/onet_hip_pairs.h); elsewhere the launches
                     and bits of "bf16+pool+anymap".
+                    "bf16+pool+anymap+pairs+up": the plan of "bf16+pool+anymap+pairs" whose ConvTranspose2d edges with an odd-w input map
+                    or an output padded into an odd concat map (200 x 200: 12 -> 25 and 25 -> 50) run the slot-operand GEMM too
+                    (fused_eval_upmap(), convt_slots_ok_anymap; include/onet_hip_upmap.h): one launch that writes the pad strip itself
+                    where "bf16+pool+anymap+pairs" takes the general kernel and a conversion pass, and the level below stops writing
+                    fp32.  Such an edge then reads the bf16 slots of the level below, not its unrounded fp32 activation: other bits
+                    there; on every input without such an edge (224 x 224, 256 x 256) the launches and bits of "bf16+pool+anymap+pairs".
                     Any other string is a ValueError where the setting is read"""
     __slots__ = ("conv", "twin", "convt_bf16", "lazy_nan", "split", "bn_on_load", "split_f16", "grad_f16", "split_dgrad",
                  "stem_fused", "sync_bn", "presplit", "z_bf16", "fused_eval")
@@ -179,11 +185,13 @@ def presplit():
 # The string values of Settings.fused_eval -> (slot format, pooled units in one launch[, ragged levels]); True is ("fp16x2", False)
 _FUSED_EVAL_VALUES = {"bf16": ("bf16", False), "fp16x2+pool": ("fp16x2", True), "bf16+pool": ("bf16", True),
                       "bf16+pool+ragged": ("bf16", True, True), "fp16x2+ragged": ("fp16x2", True, True),
-                      "bf16+pool+anymap": ("bf16", True, True, True), "bf16+pool+anymap+pairs": ("bf16", True, True, True, True)}
+                      "bf16+pool+anymap": ("bf16", True, True, True), "bf16+pool+anymap+pairs": ("bf16", True, True, True, True),
+                      "bf16+pool+anymap+pairs+up": ("bf16", True, True, True, True, True)}
 # 1: eval forwards under no_grad take the fused inference plan (Settings.fused_eval); bf16: its one-part plain-bf16 form; either with
 # "+pool" ("fp16x2+pool", "bf16+pool"): the pooled units in one launch; "bf16+pool+ragged" / "fp16x2+ragged" ("+pool" implied): ... on
 # maps not made of full tiles too; "bf16+pool+anymap": the plan of "bf16+pool+ragged" whose levels below the first take maps of any H and W;
 # "bf16+pool+anymap+pairs": the plan of "bf16+pool+anymap" with level 4 fused on image-pair tiles where its map is at most 16 pixels wide
+# "bf16+pool+anymap+pairs+up": ... whose ConvTranspose2d edges with an odd-w input or a padded output take the slot-operand GEMM too
 #   value                format    pooled units    ragged levels    layer predicate
 #   True                 fp16x2    two passes      no               eval_layer_ok
 #   "fp16x2+pool"        fp16x2    one launch      no               eval_layer_ok
@@ -193,6 +201,7 @@ _FUSED_EVAL_VALUES = {"bf16": ("bf16", False), "fp16x2+pool": ("fp16x2", True), 
 #   "bf16+pool+ragged"   bf16      one launch      yes              eval_layer_ok_ragged
 #   "bf16+pool+anymap"   bf16      one launch      yes, any map     eval_layer_ok_ragged (level 0), eval_layer_ok_anymap (below)
 #   "bf16+pool+anymap+pairs"  bf16  one launch     yes, any map     ... and eval_layer_ok_pairs (level 4)
+#   "bf16+pool+anymap+pairs+up"  bf16  one launch  yes, any map     ... and convt_slots_ok_anymap (ConvTranspose2d edges)
 FUSED_EVAL = _FLAGS["FUSED_EVAL"] if _FLAGS.get("FUSED_EVAL") in _FUSED_EVAL_VALUES else _flag("FUSED_EVAL", False)
 
 
@@ -241,6 +250,13 @@ def fused_eval_pairs():
     (Settings.fused_eval = "bf16+pool+anymap+pairs": the entry point of include/onet_hip_pairs.h, layer predicate eval_layer_ok_pairs)?
     Implies fused_eval_anymap(): every other level runs what "bf16+pool+anymap" runs."""
     return len(_fused_eval_value()) > 4
+
+
+def fused_eval_upmap():
+    """Do the fused eval plan's ConvTranspose2d edges whose input map has odd w or whose output is padded into an odd concat map take the
+    slot-operand GEMM (Settings.fused_eval = "bf16+pool+anymap+pairs+up": the entry point of include/onet_hip_upmap.h, predicate
+    convt_slots_ok_anymap)?  Implies fused_eval_pairs(): every other launch is what "bf16+pool+anymap+pairs" runs."""
+    return len(_fused_eval_value()) > 5
 
 
 Z_BF16 = _flag("Z_BF16", True)       # BASELINE configs[2] (conv == "bf16", pre-split operands): conv outputs stored as bf16 (Settings.z_bf16)
@@ -698,6 +714,31 @@ def convT2x2_fwd_slots_ragged(xP, wP, bias, outP, Ct, kind="convt_slot_fwd_kerne
     _prof_end(kind, flops if rc == 0 else 0.0, e0, nb if rc == 0 else 0.0)
     if rc < 0:
         raise _lib.OnetHipError(f"onet_convT2x2_fwd_slots_ragged failed ({rc}): {_lib.last_error()}")
+    return rc == 0
+
+
+def convt_slots_ok_anymap(B, Cin, Ct, h, w, Ho, Wo):
+    """convt_slots_ok_ragged (one part) without even w, into an output map of Ho x Wo: the predicate of onet_convT2x2_fwd_slots_anymap --
+    any w, Ho - 2h and Wo - 2w in {0, 1} (the concat map of a floor-pooled level)."""
+    return bool(CONVT_SLOTS and presplit() and CONVT_BF16 and Cin % 32 == 0 and Cin >= 128 and Ct % 32 == 0 and h > 0 and w > 0
+                and Ho - 2 * h in (0, 1) and Wo - 2 * w in (0, 1) and Cin * h * w * 2 < 2 ** 31)
+
+
+def convT2x2_fwd_slots_anymap(xP, wP, bias, outP, Ct, kind="convt_slot_fwd_kernel"):
+    """convT2x2_fwd_slots_ragged on one-part bf16 slots of a map of ANY w, into outP [B, Ct/8, Ho, 1, Wo, 8] with Ho - 2h, Wo - 2w in
+    {0, 1}: the up-sampled 2h x 2w block in the top-left corner, value for value what convT2x2_fwd_slots_ragged writes for those pixels,
+    and the pad strip (row 2h, column 2w) as zero slots, all in one launch.  -> False where the kernel does not take the shape (nothing
+    written)."""
+    B, C8, h, parts, w, _ = xP.shape
+    Ho, Wo = outP.shape[2], outP.shape[4]
+    assert parts == 1 and outP.shape[3] == 1 and outP.shape[1] * 8 == Ct and xP.dtype == wP.dtype == outP.dtype == BF
+    Cin = C8 * 8
+    e0 = _prof_begin(kind)
+    rc = _lib.load().onet_convT2x2_fwd_slots_anymap(_p(xP), _pbs(xP), _p(wP), _p(bias), _p(outP), _pbs(outP), B, Cin, Ct, h, w, Ho, Wo, _stream())
+    flops, nb = 2.0 * B * h * w * Cin * 4 * Ct, 2.0 * (B * (h * w * Cin + Ho * Wo * Ct) + 4 * Cin * Ct)
+    _prof_end(kind, flops if rc == 0 else 0.0, e0, nb if rc == 0 else 0.0)
+    if rc < 0:
+        raise _lib.OnetHipError(f"onet_convT2x2_fwd_slots_anymap failed ({rc}): {_lib.last_error()}")
     return rc == 0
 
 
