@@ -1,7 +1,8 @@
 """ctypes binding of libonet_hip.so (C ABI: include/onet_hip.h, include/onet_hip_eval.h for the validation step and
 include/onet_hip_ragged.h / include/onet_hip_ragged_split.h for the one-part / fp16 two-part eval plan on ragged maps,
 include/onet_hip_anymap.h for the one-part plan's levels on maps of any size, include/onet_hip_pairs.h for its bottom level on
-image-pair tiles, include/onet_hip_upmap.h for its ConvTranspose2d edges on maps of any size).
+image-pair tiles, include/onet_hip_upmap.h for its ConvTranspose2d edges on maps of any size, include/onet_hip_split_pairs.h for the
+fp16 two-part plan's bottom level on image-pair tiles).
 
 The prototypes are PARSED from the header, so the Python side cannot drift from
 the ABI.  There is no CPU fallback: if the library cannot be loaded (or built),
@@ -27,6 +28,8 @@ ANYMAP_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_anymap.
 PAIRS_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_pairs.h")
 # ... and of its ConvTranspose2d edges with an odd-w input or a padded output (Settings.fused_eval = "bf16+pool+anymap+pairs+up")
 UPMAP_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_upmap.h")
+# ... and of the fp16 (hi | mid) plan's bottom level on image-pair tiles (Settings.fused_eval = "fp16x2+ragged+pairs")
+SPLIT_PAIRS_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_split_pairs.h")
 LIBPATH = os.environ.get("ONET_HIP_LIB") or os.path.join(HERE, "libonet_hip.so")
 
 _CT = {
@@ -85,7 +88,7 @@ def load(build_if_missing: bool = True):
         _build.build()
     lib = ctypes.CDLL(LIBPATH)
     _protos = {}
-    for header in (HEADER, EVAL_HEADER, RAGGED_HEADER, RAGGED_SPLIT_HEADER, ANYMAP_HEADER, PAIRS_HEADER, UPMAP_HEADER):
+    for header in (HEADER, EVAL_HEADER, RAGGED_HEADER, RAGGED_SPLIT_HEADER, ANYMAP_HEADER, PAIRS_HEADER, UPMAP_HEADER, SPLIT_PAIRS_HEADER):
         protos = parse_header(header)
         for name, (restype, argtypes, _) in protos.items():
             try:

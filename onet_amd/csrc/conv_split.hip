@@ -27,6 +27,7 @@
 #include "../../include/onet_hip_ragged_split.h"
 #include "../../include/onet_hip_anymap.h"
 #include "../../include/onet_hip_pairs.h"
+#include "../../include/onet_hip_split_pairs.h"
 
 using namespace onet;
 
@@ -693,6 +694,8 @@ struct SpPreArgs {
     // of any H and 0 < W <= 16): the activation epilogue on image-pair tiles.  B counts the cdiv(n_img, 2) pairs and n_img (the storage
     // of rd_gimg: RD and ACT exclude each other) the images -- with an odd count the last tile holds ONE image: its second half stages
     // the out-of-range offset, stores nothing, and the tile's buffer resource ends with the first image
+    // conv3x3_split_pre_kernel<false, 1, W16 = true, ACT = true, false, RAG = true> (round 18, include/onet_hip_split_pairs.h): the same
+    // on fp16 (hi | mid) parts -- B and n_img as above, zP_slots / act_amax as on the ragged instance (the record masks absent images too)
 };
 
 // PM: 0 = bf16 (hi | mid) parts, 1 = fp16 (hi | mid) parts -- three MFMAs per term on 16-channel chunks; 2 = PLAIN bf16 operands
@@ -725,9 +728,11 @@ template <bool ST, int PM, bool W16, bool ACT = false, bool POOL = false, bool R
 __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void conv3x3_split_pre_kernel(SpPreArgs a) {
     constexpr bool F16 = PM == 1;
     static_assert(!RAG || ACT, "conv3x3_split_pre_kernel: the ragged instance is the activation epilogue's (masked exact maximum)");
-    static_assert(!ACT || (PM == 1 && !ST && !W16), "conv3x3_split_pre_kernel: the activation epilogue goes with the fp16 slot store");
+    static_assert(!ACT || (PM == 1 && !ST && (!W16 || (RAG && !POOL))),
+                  "conv3x3_split_pre_kernel: the activation epilogue goes with the fp16 slot store; on image-pair tiles: the masked record, no pooled twin");
     static_assert(!POOL || ACT, "conv3x3_split_pre_kernel: the pooled stores ride on the activation epilogue");
     using C = SpPreCfg<W16>;
+    constexpr bool PAIRS = W16 && ACT;                                 // the activation epilogue on image-pair tiles (SpPreArgs::n_img)
     constexpr int NT = C::NT, IN_COLS = C::IN_COLS, NWI = C::NWI, CO_T = C::CO_T, NPIXP = C::NPIXP, NB = C::NB;
     constexpr int BUF = C::BUF_SLOTS, W_PART = C::W_PART, IN_PART = C::IN_PART;
     constexpr int NWV = C::NW, NTH = NWV * 64;
@@ -766,8 +771,10 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
         const bool live = st_tile < t_end;
         const auto [co0, tx, ty, b, y0, x0] = sp_tile(live ? st_tile : t_first, a.coTiles, a.tilesX, a.tilesY);
         // (W16: b is the image PAIR; the resource spans both images, the second one's offset rides in the lane's byte offset)
+        // (PAIRS: the last tile of an odd image count holds one image -- the resource ends with it, its second half is out of range)
+        const bool img1 = !PAIRS || 2 * b + 1 < a.n_img;
         xr = sp_rsrc4(reinterpret_cast<const unsigned*>(a.xs) + (int64_t)(W16 ? 2 * b : b) * a.xs_bs,
-                      (W16 ? a.xs_bs * 4 : 0) + (int64_t)a.Cin * HW * (PM == 2 ? 2 : 4));
+                      (W16 && img1 ? a.xs_bs * 4 : 0) + (int64_t)a.Cin * HW * (PM == 2 ? 2 : 4));
 #pragma unroll
         for (int k = 0; k < NII; ++k) {
             const int i = (wn + NWV * k) * 64 + lane;
@@ -775,7 +782,7 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
             const int r = pix / IN_COLS, c = pix % IN_COLS;
             const int img = W16 ? c / 18 : 0;
             const int yy = y0 - 1 + r, xx = W16 ? c % 18 - 1 : x0 - 1 + c;
-            const bool ok = live && i < 2 * IN_PART && pix < C::NPIX && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
+            const bool ok = live && i < 2 * IN_PART && pix < C::NPIX && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W && (!PAIRS || img == 0 || img1);
             const unsigned io = W16 ? (unsigned)(img * a.xs_bs * 4) : 0u;
             in_off[k] = !ok ? OOB_S : PM == 2 ? io + (unsigned)(((ph * a.H + yy) * a.W + xx) * 16)
                                               : io + (unsigned)(((((ph & 1) * a.H + yy) * 2 + (ph >> 1)) * a.W + xx) * 16);
@@ -821,7 +828,7 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
     __syncthreads();
     int buf = 0;
     float zP_scale = 1.f;
-    if constexpr (PM == 1 && !ST && !W16) {
+    if constexpr (PM == 1 && !ST && (!W16 || ACT)) {
         float zinv;
         if (a.zP) zP_scale = amax_scale(amax_read(a.zP_slots), !ACT, zinv);
     }
@@ -995,6 +1002,9 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
         }
         float* zb = a.z + (int64_t)(W16 ? 2 * b + (l31 >> 4) : b) * a.z_bs;      // (W16: b is the image pair, lanes 16-31 hold the second image)
         const int xo = W16 ? (l31 & 15) : x0 + l31;
+        // (PAIRS: a lane's image of the pair -- lanes 16-31 of a half-wave hold the second one, absent in the last tile of an odd count)
+        [[maybe_unused]] const int img = PAIRS ? 2 * b + (l31 >> 4) : b;
+        [[maybe_unused]] const bool img_ok = !PAIRS || img < a.n_img;
         if constexpr (ACT) {
             // BatchNorm (fixed coefficients) + ReLU on the accumulators, bn_relu_apply_split_kernel's expression; register r of
             // acc[m][n] is channel m 32 + 8 (r / 4) + 4 kh + r % 4 of the tile: four consecutive floats per coefficient and group
@@ -1024,10 +1034,11 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
                         }
                 }
             if constexpr (RAG) {
-                // only the map's own pixels: one predicate per row (a.act_a's and the slot stores' guard)
+                // only the map's own pixels: one predicate per row (a.act_a's and the slot stores' guard; PAIRS: of real images only --
+                // an absent image's accumulators are relu(sh - mean sc))
 #pragma unroll
                 for (int n = 0; n < NT; ++n)
-                    if (y0 + wn * NT + n < a.H && xo < a.W) vmax = fmaxf(vmax, vrow[n]);
+                    if (img_ok && y0 + wn * NT + n < a.H && xo < a.W) vmax = fmaxf(vmax, vrow[n]);
             }
             if (a.act_amax) {
                 // the exact maximum of what this wave wrote: one atomicMax on the fp32 bit pattern per wave and tile
@@ -1037,13 +1048,13 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
                     atomicMax(a.act_amax + ((tile * NWV + wn) & (AMAX_SLOTS - 1)) * AMAX_STRIDE, __builtin_bit_cast(unsigned, vmax));
             }
             if (a.act_a) {
-                float* ab = a.act_a + (int64_t)b * a.act_a_bs;
+                float* ab = a.act_a + (int64_t)img * a.act_a_bs;
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
 #pragma unroll
                     for (int n = 0; n < NT; ++n) {
                         const int yo = y0 + wn * NT + n;
-                        if (yo < a.H && xo < a.W) {
+                        if (img_ok && yo < a.H && xo < a.W) {
 #pragma unroll
                             for (int r = 0; r < 16; ++r) {
                                 const int co = co0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
@@ -1053,13 +1064,14 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
                     }
             }
         }
-        if constexpr (PM == 1 && !ST && !W16) {
+        if constexpr (PM == 1 && !ST && (!W16 || ACT)) {
             if (ACT || (a.zP && co0 >= a.zP_ch0)) {
                 // Pre-split output (SpPreArgs::zP).  A lane holds channels 8 g + 4 kh + {0 .. 3} of its pixel for the four groups g of a
                 // 32-row accumulator; v_permlane32_swap trades halves with the partner lane (kh ^ 1): afterwards a kh = 0 lane owns all
                 // 8 channels of groups 0 and 2, a kh = 1 lane those of groups 1 and 3 -- whole slots, 512 contiguous bytes per half-wave
                 const float zs = zP_scale;
-                u32x4s* zp = reinterpret_cast<u32x4s*>(reinterpret_cast<unsigned*>(a.zP) + (int64_t)b * a.zP_bs);
+                // (PAIRS: the slots go to the lane's image of the pair; the exchange partner, lane ^ 32, is in the same image half)
+                u32x4s* zp = reinterpret_cast<u32x4s*>(reinterpret_cast<unsigned*>(a.zP) + (int64_t)img * a.zP_bs);
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -1087,7 +1099,7 @@ __global__ __launch_bounds__(SpPreCfg<W16>::NW * 64, SpPreCfg<W16>::NW / 4) void
                                 hi[k] = hh;
                                 mid[k] = mm;
                             }
-                            if (yo < a.H && xo < a.W) {
+                            if (img_ok && yo < a.H && xo < a.W) {
                                 const int c8 = ((co0 - a.zP_ch0 + m * 32) >> 3) + 2 * e + kh;
                                 u32x4s* d = zp + ((int64_t)(c8 * a.H + yo) * 2) * a.W + xo;
                                 d[0] = hi;
@@ -1859,7 +1871,8 @@ int launch_split_pre(SpPreArgs a, hipStream_t st) {
     return sp_launch_persistent(kern, attr_once, LDS_BYTES, tiles, C::NW * 64,
                                 HEAD   ? (PM == 2 ? "conv3x3_pre16_head_kernel" : "conv3x3_split_pre_head_kernel")
                                 : POOL ? (PM == 2 ? "conv3x3_pre16_act_pool_kernel" : "conv3x3_split_pre_act_pool_kernel")
-                                : ACT  ? (W16 ? "conv3x3_pre16_act_pairs_kernel" : PM == 2 ? "conv3x3_pre16_act_kernel" : "conv3x3_split_pre_act_kernel")
+                                : ACT  ? (W16 ? (PM == 2 ? "conv3x3_pre16_act_pairs_kernel" : "conv3x3_split_pre_act_pairs_kernel")
+                                              : PM == 2 ? "conv3x3_pre16_act_kernel" : "conv3x3_split_pre_act_kernel")
                                       : "conv3x3_split_pre_kernel", a, st);
 }
 
@@ -2824,6 +2837,40 @@ int onet_conv3x3_split_fwd_pre_act_ragged(const void* xs, int64_t xs_bs, const v
                                           int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
     return split_pre_act_impl("conv3x3_split_fwd_pre_act_ragged", true, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, aP, aP_bs,
                               aP_slots, a_amax, a, a_bs, B, Cin, Cout, H, W, stream);
+}
+
+// ... on IMAGE-PAIR tiles (include/onet_hip_split_pairs.h, round 18): maps of any H and 0 < W <= 16 -- the bottom level of the fp32-level
+// eval plan (16 x 16, 14 x 14) -- two images side by side in a tile's 32 columns, each with its own halo columns (SpPreCfg<true>), where
+// the ragged entry walks one half-empty tile per image.  On the map, value for value, what that entry writes (on the map zero-padded to
+// its domain): the same chunks and taps in the same order per pixel, the same epilogue expressions, the same 2^k.  a_amax receives the
+// maximum over the map's pixels of the batch's own images.  Any batch size: the last tile of an odd one holds one image.  Returns 1
+// (nothing launched, nothing written) for W > 16, Cin % 16, Cout % 64 or an image pair beyond the buffer-resource range.
+int onet_conv3x3_split_fwd_pre_act_pairs(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
+                                         const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
+                                         int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    const char* entry = "conv3x3_split_fwd_pre_act_pairs";
+    ONET_REQUIRE(xs && wq && save && aP && aP_slots, "%s: null pointer", entry);
+    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
+    if (W > 16 || (Cin % 16) || (Cout % 64)) return 1;
+    // a tile's buffer resource spans an image pair: the batch stride, then one image and the chunk the staging runs ahead by
+    if ((int64_t)(Cin + 32) * 2 * 9 * Cout * 2 >= (1ll << 31) || xs_bs > (1ll << 29) || xs_bs * 4 + (int64_t)(Cin + 32) * H * W * 4 >= (1ll << 31))
+        return 1;
+    ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
+    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 1, Cin, Cout, H, W)) return rc;
+    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "%s: 16-byte aligned slots required", entry);
+    ONET_REQUIRE(!a || (reinterpret_cast<uintptr_t>(a) & 3) == 0, "%s: 4-byte aligned floats required", entry);
+    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W && (!a || a_bs >= (int64_t)Cout * H * W), "%s: batch stride too small", entry);
+    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)x_amax, scale_always,
+                (const unsigned*)x_amax2, split_ch};
+    p.zP = aP;
+    p.zP_bs = aP_bs;
+    p.zP_ch0 = 0;
+    p.zP_slots = (const unsigned*)aP_slots;
+    p.act_save = save;
+    p.act_amax = (unsigned*)a_amax;
+    p.act_a = a;
+    p.act_a_bs = a_bs;
+    return launch_split_pre<false, 1, true, false, true, false, false, true>(p, as_stream(stream));
 }
 
 // The plain forward of onet_conv3x3_split_fwd_pre(wq_f16 = 1, fp32 z, no statistics) on a ragged map: the fp16 plan's last unit where

@@ -80,6 +80,20 @@ slots alone).  The edge now reads bf16-rounded slots where `pack` read the unrou
 bf16 digit, which is why this is a value of its own.  An edge from a fall-back level keeps `pack`; whole-tile and ragged even-w edges
 keep their routes: an input without such an edge (224 x 224, 256 x 256) launches what "bf16+pool+anymap+pairs" launches, the same bits.
 
+Settings.fused_eval = "fp16x2+ragged+pairs" (ops.fused_eval_pairs_fp16()): the plan of "fp16x2+ragged" at FULL depth where level 4 is
+ops.PAIRS_MIN_W .. 16 pixels wide (256 x 256: 16 x 16, 224 x 224: 14 x 14).  Level 4, and level 4 alone, takes
+ops.eval_layer_ok_pairs_fp16: its two units run ops.conv3x3_split_pre_act_pairs (include/onet_hip_split_pairs.h), TWO images side by side
+per tile, and the level is marked _Level.ragged = "pairs".  The magnitude slots are a ragged level's: the launch scales by the unit's
+bound and records the EXACT maximum over the map's pixels of the batch's own images (an absent image of an odd batch's last tile is
+masked like an out-of-map pixel).  Its input is the pooled slots of down3.c2, and that one pooled unit also records the exact maximum of
+its activation and hands it on with the pooled tensor (_pooled_unit(record=True)): otherwise down4.c1's bound would chain two bounds
+over its 4608-term sums (measured: 1.45e4 - 1.70e4 x the exact maximum on small maps, above the full-tile plan's 1.4e4 x); down3.c2's
+skip tensor keeps the bound, as every other pooled unit's tensors do.  Level 4's output goes to the ConvTranspose2d of up1 by the routes
+above ("slots" where h w % 128 == 0, "slots_ragged" with two parts elsewhere -- w is even, since level 3 has W % 4 == 0 -- and
+`pack` with keep_fp32 where ops.convt_slots_ok_ragged says no).  No any-map rules come with it: H and W must still be multiples of 16
+at the input and levels 0 .. 3 keep ops.eval_layer_ok_ragged_fp16, so an input whose level 4 is wider than 16 pixels or narrower than
+the floor, and an odd-sized one (200 x 200 stays at depth 2), launch what "fp16x2+ragged" launches: the same bits.
+
 The validation step (validate, EvalCounts): the scores of a batch -- by the labels-only plan where it applies, the ordinary forward
 elsewhere -- then ONE launch (ops.score_counts) that forms the labels and adds each image's confusion counts against the ground truth
 into a device tensor; nothing synchronises, and metrics.epoch_metrics turns an epoch's rows into the reference's metrics on the host.
@@ -118,7 +132,11 @@ def _units(blk):
 # None everywhere, no bound launches) and whether the pooled tensors are traced
 # (ragged: the launches of a level whose maps are not made of full 16 x 32 tiles -- None: the format takes no such level)
 # (anymap: the layer predicate and the launches of a level k >= 1 whose map lies outside the ragged domain -- None: no such level)
-_Format = namedtuple("_Format", "operands parts pack layer_ok act act_pool head magnitude trace_pool ragged anymap", defaults=(None, None))
+# (pairs: the layer predicate and the launch of level 4 on maps no wider than 16 pixels of a format WITHOUT any-map levels -- None: such
+# a level is not fused; the one-part format carries its own in `anymap`)
+_Format = namedtuple("_Format", "operands parts pack layer_ok act act_pool head magnitude trace_pool ragged anymap pairs",
+                     defaults=(None, None, None))
+_Pairs = namedtuple("_Pairs", "layer_ok act")
 _Ragged = namedtuple("_Ragged", "act act_pool head plain")
 # (pairs_ok, pairs_act: the layer predicate and the launch of level 4 on maps no wider than 16 pixels -- None: such a level is not fused)
 # (upmap: a ConvTranspose2d edge with an odd-w input map or a padded output takes the any-map slot GEMM where its predicate holds)
@@ -130,6 +148,7 @@ _RAGGED = _Ragged(ops.conv3x3_plain16_pre_act_ragged, ops.conv3x3_plain16_pre_ac
                   ops.conv3x3_plain16_pre_plain_ragged)
 _RAGGED_FP16 = _Ragged(ops.conv3x3_split_pre_act_ragged, ops.conv3x3_split_pre_act_pool_ragged, ops.conv3x3_split_pre_head_ragged,
                        ops.conv3x3_split_pre_plain_ragged)
+_PAIRS_FP16 = _Pairs(ops.eval_layer_ok_pairs_fp16, ops.conv3x3_split_pre_act_pairs)
 
 
 def _format():
@@ -144,7 +163,15 @@ def _format():
                        (_ANYMAP_UP if ops.fused_eval_upmap() else _ANYMAP_PAIRS if ops.fused_eval_pairs() else _ANYMAP)
                        if ops.fused_eval_anymap() else None)
     return _Format(name, 2, "split", ops.eval_layer_ok_ragged_fp16 if rag else ops.eval_layer_ok, ops.conv3x3_split_pre_act,
-                   ops.conv3x3_split_pre_act_pool, ops.conv3x3_split_pre_head, True, False, _RAGGED_FP16 if rag else None)
+                   ops.conv3x3_split_pre_act_pool, ops.conv3x3_split_pre_head, True, False, _RAGGED_FP16 if rag else None,
+                   pairs=_PAIRS_FP16 if ops.fused_eval_pairs_fp16() else None)
+
+
+def _pairs(fmt):
+    """-> (layer predicate, launch) of level 4 on maps no wider than 16 pixels, (None, None) where the plan does not fuse such a level"""
+    if fmt.anymap is not None:
+        return fmt.anymap.pairs_ok, fmt.anymap.pairs_act
+    return (fmt.pairs.layer_ok, fmt.pairs.act) if fmt.pairs is not None else (None, None)
 
 
 def _static_reason(unet, fmt):
@@ -187,7 +214,8 @@ def _level_layers(unet):
 def _depth(units, ups, layer_ok, N, H, W, anymap_ok=None, pairs_ok=None):
     """-> (d, why level d is not fused | None): levels 0 .. d - 1 are fused.  anymap_ok: the predicate of the levels k >= 1 of a plan
     that takes maps of any size there -- level k is then H >> k x W >> k (floor pooling) whatever the input's divisibility;
-    pairs_ok: the predicate of level 4 of such a plan where that level's map is 16 pixels wide or narrower"""
+    pairs_ok: the predicate of level 4 where that level's map is 16 pixels wide or narrower -- with anymap_ok on top of the any-map
+    rules, without it on top of the rule above (the input size a multiple of 16, levels 0 .. 3 by layer_ok)"""
     level0_ok = layer_ok
     for k, (e, d) in enumerate(units):
         if anymap_ok is None and ((H % (1 << k)) or (W % (1 << k))):
@@ -199,6 +227,8 @@ def _depth(units, ups, layer_ok, N, H, W, anymap_ok=None, pairs_ok=None):
             layer_ok = anymap_ok if k else level0_ok
             if pairs_ok is not None and k == 4 and w <= 16:
                 layer_ok = pairs_ok
+        elif pairs_ok is not None and k == 4 and w <= 16:
+            layer_ok = pairs_ok
         for name, conv, _ in e + d:
             if not layer_ok(N, conv.in_channels, conv.out_channels, h, w):
                 if layer_ok is pairs_ok:
@@ -264,7 +294,7 @@ def _build_plan(unet, shape, head=None):
     if C != unet.inc.double_conv[0].in_channels:
         return _Plan(fmt, N, _WHY_CHANNELS)
     units, ups = _level_units(unet), _blocks(unet)[2]
-    d, why_d = _depth(units, ups, fmt.layer_ok, N, H, W, fmt.anymap.layer_ok if fmt.anymap else None, fmt.anymap.pairs_ok if fmt.anymap else None)
+    d, why_d = _depth(units, ups, fmt.layer_ok, N, H, W, fmt.anymap.layer_ok if fmt.anymap else None, _pairs(fmt)[0])
     if d == 0:
         return _Plan(fmt, N, why_d, None, 0, why_d)
     # the ConvTranspose2d of level k reads the output of level k + 1: slots where that level is fused and the slot-operand kernel takes
@@ -301,7 +331,7 @@ def _build_plan(unet, shape, head=None):
         keep = {(dec or e)[-1][0]} if 0 < k < d and convt[k - 1] == "fp32->slots" else ()
         enc_u, dec_u = ([_Unit(name, conv, bn, kind[name], name in keep) for name, conv, bn in us] for us in (e, dec))
         levels.append(_Level(enc_u, dec_u, ups[k].up if k < 4 else None, convt[k] if k < 4 else None, k + 1 < d,
-                             _level_ragged(k < d, H >> k, W >> k, k == 4 and fmt.anymap is not None and fmt.anymap.pairs_ok is not None),
+                             _level_ragged(k < d, H >> k, W >> k, k == 4 and _pairs(fmt)[0] is not None),
                              edges[k][1] if k < 4 else None))
     return _Plan(fmt, N, None, None, d, why_d, unet, tuple(levels), with_head)
 
@@ -475,7 +505,8 @@ def _fused_unit(fmt, u, t, ragged=False):
     amax = ops.new_amax(t.P.device) if fmt.magnitude else None
     a = torch.empty((B, conv.out_channels, H, W), dtype=torch.float32, device=t.P.device) if u.keep_fp32 else None
     # (a ragged launch takes its sibling's magnitude-slot arguments: none on the one-part format, whose ragged entries record no maximum)
-    launch = fmt.anymap.pairs_act if ragged == "pairs" else fmt.anymap.act if ragged == "anymap" else fmt.ragged.act if ragged else fmt.act
+    # (a pair launch likewise: the fp16 one takes aP_slots = the bound and a_amax = a fresh record, exactly as on a ragged level)
+    launch = _pairs(fmt)[1] if ragged == "pairs" else fmt.anymap.act if ragged == "anymap" else fmt.ragged.act if ragged else fmt.act
     aP = launch(t.P, _wq(fmt, conv), conv.out_channels, save, a=a, **_slot_kw(fmt, t, aP_slots=scale, a_amax=amax))
     if aP is None:
         raise RuntimeError(f"onet_amd: the fused eval kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
@@ -491,11 +522,15 @@ def _plain_conv(fmt, conv, t, ragged=False):
     return ops.conv3x3_split_pre(t.P, _wq(fmt, conv), conv.out_channels, **_slot_kw(fmt, t))
 
 
-def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots, ragged=False):
+def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots, ragged=False, record=False):
     """An encoder block's second unit, which writes the skip slots into the concat buffer, the pooled tensor (slots, or fp32 for a
     fall-back level) and -- level 0 -- the fp32 tensor the caller receives.  "two-pass": plain convolution, then ONE BatchNorm + ReLU +
     2 x 2 max-pooling pass; "fused+pool": all of it in the convolution's launch, the same bits (no exact maximum is taken from it: the
-    unit hands on its bound either way, so every later launch sees the same magnitude slots).  -> (skip, pooled, L | None)"""
+    unit hands on its bound either way, so every later launch sees the same magnitude slots).  -> (skip, pooled, L | None)
+    record (the unit in front of a pair level of a format with magnitude slots, "fused+pool"): the launch also records the exact
+    maximum of its activation -- which is the maximum of the pooled tensor -- and the POOLED tensor hands that on as its amax, so the
+    bound of the pair level's first unit starts from an exact maximum instead of chaining two bounds; the skip tensor, and with it
+    every launch of this level and above, keeps the bound"""
     save = _coeffs(u.bn)
     scale = _bound(fmt, u.conv, save, t)
     B, _, H, _, W, _ = t.P.shape
@@ -504,18 +539,20 @@ def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots, ragged=False):
     L = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if want_L else None
     yP = ops.p16_empty(B, C, H // 2, W // 2, dev, parts=fmt.parts) if pooled_slots else None
     yF = None if pooled_slots else torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=dev)
+    amax = ops.new_amax(dev) if record and fmt.magnitude and z is None and pooled_slots else None
+    out_kw = dict(aP_slots=scale) if amax is None else dict(aP_slots=scale, a_amax=amax)
     if z is None and ragged:
         act_pool = fmt.anymap.act_pool if ragged == "anymap" else fmt.ragged.act_pool
-        if act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, aP_slots=scale)) is None:
+        if act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, **out_kw)) is None:
             raise RuntimeError(f"onet_amd: the ragged pooling kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
     elif z is None:
-        if fmt.act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, aP_slots=scale)) is None:
+        if fmt.act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, **out_kw)) is None:
             raise RuntimeError(f"onet_amd: the fused pooling kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
     elif not ops.bn_relu_apply_pool_split(z, save, skipP, L, yP, yF, slots=scale):
         raise RuntimeError("onet_amd: the BatchNorm + pooling pass refused a shape ops.eval_layer_ok accepted")
     if yF is not None and fmt.magnitude:
         ops.tag_amax(yF, scale)           # (max-pooling keeps the bound: the in-staging kernel below takes it as its range guard)
-    return _T(skipP, None, scale, scale), _T(yP, yF, scale, scale), L
+    return _T(skipP, None, scale, scale), _T(yP, yF, scale, scale if amax is None else amax), L
 
 
 def _conv_t(fmt, lv, t, catP, C2):
@@ -608,7 +645,9 @@ def _unet_pass_L(plan, x):
             else:
                 C = u.conv.out_channels
                 catP[k] = ops.p16_empty(N, C + lv.up.out_channels, H >> k, W >> k, x.device, parts=fmt.parts)
-                skips[k], t, Lk = _pooled_unit(fmt, u, t, catP[k][:, :C // 8], k == 0, lv.pooled_slots, lv.ragged)
+                # (fp16 pair level below: its first unit's bound starts from this unit's exact record, see _pooled_unit)
+                record = fmt.pairs is not None and k + 1 < len(fused) and fused[k + 1].ragged == "pairs"
+                skips[k], t, Lk = _pooled_unit(fmt, u, t, catP[k][:, :C // 8], k == 0, lv.pooled_slots, lv.ragged, record)
                 _note(u.name, skips[k])
                 if fmt.trace_pool and lv.pooled_slots:
                     _note(_ENC[k] + ".pool", t)

@@ -85,6 +85,10 @@ class Settings:
                     where "bf16+pool+anymap+pairs" takes the general kernel and a conversion pass, and the level below stops writing
                     fp32.  Such an edge then reads the bf16 slots of the level below, not its unrounded fp32 activation: other bits
                     there; on every input without such an edge (224 x 224, 256 x 256) the launches and bits of "bf16+pool+anymap+pairs".
+                    "fp16x2+ragged+pairs": the plan of "fp16x2+ragged" whose BOTTOM level (level 4: down4 and the ConvTranspose2d of
+                    up1) is fused too where its map is PAIRS_MIN_W .. 16 pixels wide (fused_eval_pairs_fp16(), eval_layer_ok_pairs_fp16:
+                    224 x 224 and 256 x 256 at full depth, at fp32 level), two images per tile (include/onet_hip_split_pairs.h);
+                    elsewhere -- 200 x 200 included -- the launches and bits of "fp16x2+ragged".
                     Any other string is a ValueError where the setting is read"""
     __slots__ = ("conv", "twin", "convt_bf16", "lazy_nan", "split", "bn_on_load", "split_f16", "grad_f16", "split_dgrad",
                  "stem_fused", "sync_bn", "presplit", "z_bf16", "fused_eval")
@@ -186,7 +190,9 @@ def presplit():
 _FUSED_EVAL_VALUES = {"bf16": ("bf16", False), "fp16x2+pool": ("fp16x2", True), "bf16+pool": ("bf16", True),
                       "bf16+pool+ragged": ("bf16", True, True), "fp16x2+ragged": ("fp16x2", True, True),
                       "bf16+pool+anymap": ("bf16", True, True, True), "bf16+pool+anymap+pairs": ("bf16", True, True, True, True),
-                      "bf16+pool+anymap+pairs+up": ("bf16", True, True, True, True, True)}
+                      "bf16+pool+anymap+pairs+up": ("bf16", True, True, True, True, True),
+                      # (positions 3 .. 5 -- any map, pairs, any-map ConvTranspose2d -- are the one-part plan's; 6: the fp16 plan's pair level)
+                      "fp16x2+ragged+pairs": ("fp16x2", True, True, False, False, False, True)}
 # 1: eval forwards under no_grad take the fused inference plan (Settings.fused_eval); bf16: its one-part plain-bf16 form; either with
 # "+pool" ("fp16x2+pool", "bf16+pool"): the pooled units in one launch; "bf16+pool+ragged" / "fp16x2+ragged" ("+pool" implied): ... on
 # maps not made of full tiles too; "bf16+pool+anymap": the plan of "bf16+pool+ragged" whose levels below the first take maps of any H and W;
@@ -202,6 +208,7 @@ _FUSED_EVAL_VALUES = {"bf16": ("bf16", False), "fp16x2+pool": ("fp16x2", True), 
 #   "bf16+pool+anymap"   bf16      one launch      yes, any map     eval_layer_ok_ragged (level 0), eval_layer_ok_anymap (below)
 #   "bf16+pool+anymap+pairs"  bf16  one launch     yes, any map     ... and eval_layer_ok_pairs (level 4)
 #   "bf16+pool+anymap+pairs+up"  bf16  one launch  yes, any map     ... and convt_slots_ok_anymap (ConvTranspose2d edges)
+#   "fp16x2+ragged+pairs"  fp16x2  one launch      yes              eval_layer_ok_ragged_fp16, eval_layer_ok_pairs_fp16 (level 4)
 FUSED_EVAL = _FLAGS["FUSED_EVAL"] if _FLAGS.get("FUSED_EVAL") in _FUSED_EVAL_VALUES else _flag("FUSED_EVAL", False)
 
 
@@ -242,21 +249,33 @@ def fused_eval_anymap():
     """Does the fused eval plan take, at its levels below the first, maps of ANY H and W above the width floor (Settings.fused_eval =
     "bf16+pool+anymap": the entry points of include/onet_hip_anymap.h, layer predicate eval_layer_ok_anymap)?  Implies
     fused_eval_ragged(): level 0 and every map of even H and W % 4 == 0 run what "bf16+pool+ragged" runs."""
-    return len(_fused_eval_value()) > 3
+    v = _fused_eval_value()
+    return len(v) > 3 and bool(v[3])
 
 
 def fused_eval_pairs():
     """Does the fused eval plan take its bottom level (level 4) on image-pair tiles where that level's map is 16 pixels wide or narrower
     (Settings.fused_eval = "bf16+pool+anymap+pairs": the entry point of include/onet_hip_pairs.h, layer predicate eval_layer_ok_pairs)?
     Implies fused_eval_anymap(): every other level runs what "bf16+pool+anymap" runs."""
-    return len(_fused_eval_value()) > 4
+    v = _fused_eval_value()
+    return len(v) > 4 and bool(v[4])
 
 
 def fused_eval_upmap():
     """Do the fused eval plan's ConvTranspose2d edges whose input map has odd w or whose output is padded into an odd concat map take the
     slot-operand GEMM (Settings.fused_eval = "bf16+pool+anymap+pairs+up": the entry point of include/onet_hip_upmap.h, predicate
     convt_slots_ok_anymap)?  Implies fused_eval_pairs(): every other launch is what "bf16+pool+anymap+pairs" runs."""
-    return len(_fused_eval_value()) > 5
+    v = _fused_eval_value()
+    return len(v) > 5 and bool(v[5])
+
+
+def fused_eval_pairs_fp16():
+    """Does the fp32-level (fp16 hi | mid) fused eval plan take its bottom level (level 4) on image-pair tiles where that level's map is
+    16 pixels wide or narrower (Settings.fused_eval = "fp16x2+ragged+pairs": the entry point of include/onet_hip_split_pairs.h, layer
+    predicate eval_layer_ok_pairs_fp16)?  Implies fused_eval_ragged() on fp16x2 operands: every other level runs what "fp16x2+ragged"
+    runs.  The one-part plan's queries (fused_eval_anymap(), fused_eval_pairs(), fused_eval_upmap()) answer False under it."""
+    v = _fused_eval_value()
+    return len(v) > 6 and bool(v[6])
 
 
 Z_BF16 = _flag("Z_BF16", True)       # BASELINE configs[2] (conv == "bf16", pre-split operands): conv outputs stored as bf16 (Settings.z_bf16)
@@ -1465,6 +1484,22 @@ def eval_layer_ok_ragged_fp16(B, Cin, Cout, H, W):
     return conv3x3_algo(B, Cin, Cout, H, W) == "split"
 
 
+def eval_layer_ok_pairs_fp16(B, Cin, Cout, H, W):
+    """eval_layer_ok_ragged_fp16 for level 4 of Settings.fused_eval = "fp16x2+ragged+pairs": on W > 16 that predicate's answer; on
+    PAIRS_MIN_W <= W <= 16 the domain of onet_conv3x3_split_fwd_pre_act_pairs -- fp16 (hi | mid) parts with pre-split storage, any H > 0,
+    Cin % 16 == 0, Cout % 64 == 0, inside the buffer-resource range.  conv == "split": every such layer; otherwise the fill rule on the
+    tiles the kernel walks, which hold two images each: cdiv(B, 2) cdiv(H, 16) Cout / 64 >= 3/4 n_cu."""
+    if W > 16:
+        return eval_layer_ok_ragged_fp16(B, Cin, Cout, H, W)
+    if not presplit() or p16_parts() != 2:
+        return False
+    if Cin % 16 or Cout % 64 or B <= 0 or H <= 0 or W < max(PAIRS_MIN_W, 1) or not _in_buffer_range(Cin, Cout, H, W):
+        return False
+    if conv_algo() == "split":
+        return True
+    return -(-B // 2) * -(-H // 16) * (Cout // 64) >= (n_cu() * 3) // 4
+
+
 def _pre_act(entry, kind, two, cin_mult, xs, wq, Cout, save, out, a_amax, a, extra_in, extra_out, pooled=None, ragged=False):
     """pooled: (yP, y) of the _pool entries -- the pooled slots and / or the pooled fp32 tensor, at least one"""
     B, C8, H, _, W, _ = xs.shape
@@ -1618,6 +1653,16 @@ def conv3x3_split_pre_act_ragged(xs, wq, Cout, save, aP_slots, out=None, slots=N
     _fp16_packs("conv3x3_split_pre_act_ragged", xs, wq)
     return _pre_act("onet_conv3x3_split_fwd_pre_act_ragged", "conv3x3_split_pre_act_kernel", 2, 16, xs, wq, Cout, save, out, a_amax, a,
                     (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)), (_p(aP_slots),), ragged=True)
+
+
+def conv3x3_split_pre_act_pairs(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None):
+    """conv3x3_split_pre_act_ragged on maps of 0 < W <= 16 and any H, on IMAGE-PAIR tiles (onet_conv3x3_split_fwd_pre_act_pairs): two
+    images of the batch side by side in a tile's 32 columns; the same values, a_amax the exact maximum over the map's pixels of the
+    batch's own images.  Any batch size (an odd one: the last tile holds one image).  -> aP, or None where the kernel does not take
+    the shape (nothing launched)."""
+    _fp16_packs("conv3x3_split_pre_act_pairs", xs, wq)
+    return _pre_act("onet_conv3x3_split_fwd_pre_act_pairs", "conv3x3_split_pre_act_pairs_kernel", 2, 16, xs, wq, Cout, save, out, a_amax, a,
+                    (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)), (_p(aP_slots),), ragged="pairs")
 
 
 def conv3x3_split_pre_head_ragged(xs, wq, Cout, save, L, out=None, slots=None, slots2=None, split_ch=0):
