@@ -591,7 +591,8 @@ int onet_confusion2(const int64_t* pred, const int64_t* target, int64_t* counts,
 int onet_flip_labels(const int64_t* pred, int64_t* out, int64_t n, void* stream);
 
 /* ---- "next" row f-1: fused Adam over a flat buffer (TS:181-182) ---------------- */
-/* torch.optim.Adam semantics (no amsgrad, L2 weight_decay): step is 1-based. */
+/* torch.optim.Adam semantics (no amsgrad, L2 weight_decay): step is 1-based.  (1 - beta is that of the float beta given here;
+ * onet_hip_optim.h takes the hyper-parameters as doubles and rounds 1 - beta once, as torch does.) */
 int onet_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                    float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream);
 

@@ -30,6 +30,8 @@ PAIRS_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_pairs.h"
 UPMAP_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_upmap.h")
 # ... and of the fp16 (hi | mid) plan's bottom level on image-pair tiles (Settings.fused_eval = "fp16x2+ragged+pairs")
 SPLIT_PAIRS_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_split_pairs.h")
+# ... and of the Adam step with its hyper-parameters in double (1 - beta rounded once, as torch.optim.Adam forms it)
+OPTIM_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_optim.h")
 LIBPATH = os.environ.get("ONET_HIP_LIB") or os.path.join(HERE, "libonet_hip.so")
 
 _CT = {
@@ -88,7 +90,7 @@ def load(build_if_missing: bool = True):
         _build.build()
     lib = ctypes.CDLL(LIBPATH)
     _protos = {}
-    for header in (HEADER, EVAL_HEADER, RAGGED_HEADER, RAGGED_SPLIT_HEADER, ANYMAP_HEADER, PAIRS_HEADER, UPMAP_HEADER, SPLIT_PAIRS_HEADER):
+    for header in (HEADER, EVAL_HEADER, RAGGED_HEADER, RAGGED_SPLIT_HEADER, ANYMAP_HEADER, PAIRS_HEADER, UPMAP_HEADER, SPLIT_PAIRS_HEADER, OPTIM_HEADER):
         protos = parse_header(header)
         for name, (restype, argtypes, _) in protos.items():
             try:

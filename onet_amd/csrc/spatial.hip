@@ -219,7 +219,10 @@ __global__ void copy_strided_kernel_s(const float* __restrict__ src, int64_t src
 
 // ---------------------------------------------------------------- bilinear x2 (align_corners=True)
 __device__ __forceinline__ void bil_src(int o, int in, int out, int& i0, int& i1, float& l1) {
-    // ATen area_pixel_compute_source_index(align_corners=True): src = o * (in-1)/(out-1)
+    // ATen area_pixel_compute_source_index(align_corners=True): src = o * (in-1)/(out-1), ROUNDED to float before its integer part is
+    // taken off (ATen's CPU operator, the reference here; a GPU build of ATen may contract it too).  Contracted into fma(scale, o, -i0) the fraction would come from the unrounded product instead: another function,
+    // up to in * 2^-23 away in the weight (56 times the rounding of the interpolation itself at in = 128)
+#pragma clang fp contract(off)
     const float scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
     const float s = scale * (float)o;
     i0 = (int)s;

@@ -2786,6 +2786,7 @@ def label_counts(pred, gt, counts, row=0):
 
 # ----------------------------------------------------------------------------- optimizer
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
+    """one torch.optim.Adam step over flat buffers; the hyper-parameters go down as doubles (include/onet_hip_optim.h)"""
     require_gpu(p, g, m, v)
-    _lib.call("onet_adam_step", _p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2),
+    _lib.call("onet_adam_step_f64", _p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2),
               float(eps), float(weight_decay), int(step), float(grad_scale), _stream(), nbytes=28 * p.numel())
