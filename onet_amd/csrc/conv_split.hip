@@ -2791,394 +2791,291 @@ int onet_conv3x3_split_dgrad_pre_slots(const void* dzs, int64_t dzs_bs, const vo
     return launch_split_pre<false, 1, false>(a, as_stream(stream));
 }
 
-// Eval-mode inference: the forward convolution of onet_conv3x3_split_fwd_pre (fp16 hi | mid parts) with a FIXED BatchNorm + ReLU in
-// the epilogue and the activation leaving as slots (SpPreArgs::act_*): aP [B][Cout/8][H][2][W][8] = parts of 2^k relu(bn(z)), k by the
-// guard rule from the bound aP_slots holds BEFORE the launch (onet_conv3x3_act_bound).  Bit for bit what the plain launch followed by
-// onet_bn_relu_apply_split(z, save, slots = aP_slots) writes; z itself is never stored.  Returns 1 (nothing launched) where the map is
-// not made of full 16 x 32 tiles or Cout is not a multiple of 64.
-static bool pre_map_ok(bool ragged, int H, int W);
-static int split_pre_act_impl(const char* entry, bool ragged, const void* xs, int64_t xs_bs, const void* x_amax, int scale_always,
-                              const void* x_amax2, int split_ch, const void* wq, const float* save, void* aP, int64_t aP_bs,
-                              const void* aP_slots, void* a_amax, float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
-    ONET_REQUIRE(xs && wq && save && aP && aP_slots, "%s: null pointer", entry);
+// ----------------------------------------------------------------------------- eval-mode inference (onet_amd/inference.py)
+// The eighteen entries below are points of one small space -- slot format x map mode x epilogue -- and share one checked launch path,
+// eval_conv: each entry is a descriptor row and its arguments.  A new format, mode or epilogue is a row here (and DESIGN.md, "The fused
+// eval table", names the other places).
+//
+// Slot format (EvalEntry::parts).  2: fp16 (hi | mid) parts, the forward convolution of onet_conv3x3_split_fwd_pre(wq_f16 = 1); the
+// activation leaves as aP [B][Cout/8][H][2][W][8] = parts of 2^k relu(bn(z)), k by the guard rule from the bound aP_slots holds BEFORE
+// the launch (onet_conv3x3_act_bound); x_amax / scale_always / x_amax2 / split_ch: the operand's magnitude slots, as there.  1: ONE part
+// of plain bf16 (wq_f16 = 2), unscaled -- bf16 has fp32's exponent range, so no magnitude slots, bound or guard: aP [B][Cout/8][H][W][8]
+// bf16 (round to nearest even).  Batch strides in 4-byte units (the leading channel groups of a concat buffer qualify).
+//
+// Map mode (EvMap): the maps an entry takes; outside them 1, nothing launched.
+//   Full    maps made of full 16 x 32 tiles.
+//   Ragged  any map of even H and W % 4 == 0 below 2^24 pixels (include/onet_hip_ragged.h, onet_hip_ragged_split.h): the tile counts are
+//           cdiv, the staging gives every out-of-map slot the out-of-range offset and every store is guarded per slot / float4 / pooled
+//           float2; with H and W even and tiles starting on even coordinates a 2 x 2 pooling window is wholly inside the map or wholly
+//           outside.  On the map, value for value, what the full-tile entry writes on the map zero-padded to whole tiles; nothing outside
+//           it is written.  A map of full tiles takes the full-tile instance: the same launch, the same bits.  The exact-maximum record
+//           of the one-part activation epilogue covers a tile's out-of-map accumulators too, so the one-part ragged entries take no
+//           a_amax (an error); the fp16 instances mask their record to the MAP's pixels and take it.
+//   AnyMap  ANY H and W (include/onet_hip_anymap.h; one-part operands): the levels below the first of an input such as 200 x 200 (50 x 50:
+//           W % 4 == 2; 25 x 25: odd).  Domain: H W < 2^24, Cin % 32 == 0, Cout % 64 == 0, inside the buffer-resource range, a_amax NULL.
+//           A map the ragged entry takes goes to that entry's path, under this entry's name; every other map to the ANY instance, whose
+//           fp32 side outputs are stored float by float (4-byte alignment of a / y is enough).  The pooled maps are H / 2 x W / 2 rounded
+//           DOWN (nn.MaxPool2d(2)), and the stride checks use those sizes.
+//   Pairs   IMAGE-PAIR tiles (include/onet_hip_pairs.h, onet_hip_split_pairs.h): maps of any H and 0 < W <= 16 -- the bottom level of the
+//           eval plan (16 x 16, 14 x 14, 12 x 12) -- two images side by side in a tile's 32 columns, each with its own halo columns
+//           (SpPreCfg<true>), where the any-map / ragged entry walks one half-empty tile per image.  On the map, value for value, what that
+//           entry writes: the same chunks and taps in the same order per pixel, the same epilogue expressions, the same 2^k.  Any batch
+//           size: the last tile of an odd one holds one image (masked in the fp16 instance's a_amax record like an out-of-map pixel).
+//           1 also for an image pair beyond the buffer-resource range (a tile's buffer resource spans the batch stride, then one image and
+//           the chunk the staging runs ahead by); the one-part entry: for a non-NULL a_amax too.
+//
+// Epilogue (EvEpi).
+//   Act    a FIXED BatchNorm + ReLU of `save` [4][Cout] (onet_bn_eval_coeffs) on the accumulators, the activation leaving as slots
+//          (SpPreArgs::act_*).  a_amax (may be NULL): magnitude slots that receive the exact max a; a (may be NULL): the activation as fp32
+//          NCHW too.  Bit for bit what the plain launch followed by onet_bn_relu_apply_split writes; z itself is never stored.
+//   Pool   an encoder block's second unit: Act with the 2 x 2 max-pooling of the activation in the same epilogue (SpPreArgs::pl_*).
+//          Everything Act writes is written as it writes it, plus the pooled tensor m = max over each 2 x 2 window of relu(bn(z)): as slots
+//          yP [B][Cout/8][H/2][parts][W/2][8] (fp16: the parts of 2^k m with aP's k), as fp32 y [B][Cout][H/2][W/2], or both; at least
+//          one.  Bit for bit what the plain launch followed by onet_bn_relu_apply_pool_split writes.
+//   Head   labels-only inference, the model's LAST unit (SpPreArgs::hd_*): h = max(0, fma(z - mean, sc, sh)) on the accumulators and
+//          V [B][H][W] = sum_c L[c] h[c] (L: fp32 NCHW, batch stride L_bs) -- nothing else is stored.  Cout == 64, else 1.
+//   Plain  the plain forward (fp32 z, no statistics) on a ragged map: the plan's last unit where no head epilogue follows.
+enum class EvMap { Full, Ragged, AnyMap, Pairs };
+enum class EvEpi { Act, Pool, Head, Plain };
+struct EvalEntry {
+    const char* name;      // what the messages start with
+    int parts;             // operand kind: 1 (plain bf16) or 2 (fp16 hi | mid)
+    EvMap map;
+    EvEpi epi;
+};
+// The arguments of an entry, grouped as the prototypes list them; a group the entry does not have stays empty
+struct EvSlots { const void* x_amax = nullptr; int scale_always = 0; const void* x_amax2 = nullptr; int split_ch = 0; };
+struct EvAct { void* aP = nullptr; int64_t aP_bs = 0; const void* aP_slots = nullptr; void* a_amax = nullptr; float* a = nullptr; int64_t a_bs = 0; };
+struct EvPool { void* yP = nullptr; int64_t yP_bs = 0; float* y = nullptr; int64_t y_bs = 0; };
+struct EvHead { const float* L = nullptr; int64_t L_bs = 0; float* V = nullptr; };
+struct EvPlain { float* z = nullptr; int64_t z_bs = 0; };
+struct EvalConv {
+    const void* xs;
+    int64_t xs_bs;
+    EvSlots in;
+    const void* wq;
+    const float* save;
+    EvAct act;
+    EvPool pool;
+    EvHead head;
+    EvPlain plain;
+    int B, Cin, Cout, H, W;
+    void* stream;
+};
+
+static bool pre_map_ok(bool ragged, int H, int W) {
+    if (ragged) return !((H & 1) || (W & 3) || (int64_t)H * W >= (1 << 24));
+    return !(W < 32 || (W % 32) || (H % 16));
+}
+
+// (p may be NULL; bs: its batch stride, a multiple of 4 where rows are read as vectors -- 0 where it does not matter)
+static bool aligned(const void* p, int64_t bs, int bytes) { return !p || ((bs & 3) == 0 && (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0); }
+
+static int eval_conv(const EvalEntry& e, const EvalConv& g) {
+    const char* entry = e.name;
+    const bool one = e.parts == 1, pool = e.epi == EvEpi::Pool, act = pool || e.epi == EvEpi::Act;
+    const int B = g.B, Cin = g.Cin, Cout = g.Cout, H = g.H, W = g.W;
+    // 1. null pointers
+    if (act) ONET_REQUIRE(g.xs && g.wq && g.save && g.act.aP && (g.act.aP_slots || one), "%s: null pointer", entry);
+    else if (e.epi == EvEpi::Head) ONET_REQUIRE(g.xs && g.wq && g.save && g.head.L && g.head.V, "%s: null pointer", entry);
+    else ONET_REQUIRE(g.xs && g.wq && g.plain.z, "%s: null pointer", entry);
+    ONET_REQUIRE(!pool || g.pool.yP || g.pool.y, "%s: a pooled destination is required (yP, y or both)", entry);
+    // 2. shape
     ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
-    if (!pre_map_ok(ragged, H, W) || (Cin % 16) || (Cout % 64)) return 1;
-    ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
-    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 1, Cin, Cout, H, W)) return rc;
-    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "%s: 16-byte aligned slots required", entry);
-    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W && (!a || a_bs >= (int64_t)Cout * H * W), "%s: batch stride too small", entry);
-    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)x_amax, scale_always,
-                (const unsigned*)x_amax2, split_ch};
-    p.zP = aP;
-    p.zP_bs = aP_bs;
-    p.zP_ch0 = 0;
-    p.zP_slots = (const unsigned*)aP_slots;
-    p.act_save = save;
-    p.act_amax = (unsigned*)a_amax;
-    p.act_a = a;
-    p.act_a_bs = a_bs;
-    // a map of full tiles takes the full-tile instance from either entry: the same launch, the same bits
-    if (ragged && !pre_map_ok(false, H, W)) return launch_split_pre<false, 1, false, false, true, false, false, true>(p, as_stream(stream));
-    return launch_split_pre<false, 1, false, false, true>(p, as_stream(stream));
+    // 3. domain: 1, nothing launched
+    const int64_t image = (int64_t)(Cin + 32) * H * W * 4, pack = (int64_t)(Cin + 32) * 2 * 9 * Cout * 2;      // bytes in a buffer resource
+    EvMap map = e.map;
+    if ((Cin % (one ? 32 : 16)) || (e.epi == EvEpi::Head ? Cout != 64 : (Cout % 64))) return 1;
+    if (map == EvMap::AnyMap || map == EvMap::Pairs) {
+        // (the other entries report an operand beyond the range as an error, pre_operand_checks; the fp16 pair entry: its image too)
+        if (pack >= (1ll << 31) || (one && (g.act.a_amax || (int64_t)H * W >= (1 << 24) || image >= (1ll << 31)))) return 1;
+        if (map == EvMap::Pairs && (W > 16 || g.xs_bs > (1ll << 29) || g.xs_bs * 4 + image >= (1ll << 31))) return 1;
+        if (map == EvMap::AnyMap && pre_map_ok(true, H, W)) map = EvMap::Ragged;
+    } else if (!pre_map_ok(map == EvMap::Ragged, H, W)) {
+        return 1;
+    }
+    // 4. argument checks
+    ONET_REQUIRE(!(one && map == EvMap::Ragged) || !g.act.a_amax, "%s: the ragged entry records no exact maximum (a_amax must be NULL)", entry);
+    ONET_REQUIRE(g.in.split_ch >= 0 && g.in.split_ch < Cin && (g.in.split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
+    if (const int rc = pre_operand_checks(entry, g.xs, g.xs_bs, one ? 2 : 1, Cin, Cout, H, W)) return rc;
+    const int64_t n = (int64_t)Cout * H * W, np = (int64_t)Cout * (H >> 1) * (W >> 1), per = one ? 2 : 1;      // per: slot elements per 4-byte unit
+    if (act) {
+        ONET_REQUIRE(aligned(g.act.aP, g.act.aP_bs, 16) && aligned(g.pool.yP, g.pool.yP_bs, 16), "%s: 16-byte aligned slots required", entry);
+        if (map == EvMap::AnyMap || map == EvMap::Pairs)
+            ONET_REQUIRE(aligned(g.act.a, 0, 4) && aligned(g.pool.y, 0, 4), "%s: 4-byte aligned floats required", entry);
+        else if (one || pool)      // (the fp16 Act entries on whole images have never asked this of `a`)
+            ONET_REQUIRE(aligned(g.act.a, g.act.a_bs, 16) && aligned(g.pool.y, g.pool.y_bs, 16), "%s: 16-byte aligned rows required", entry);
+        ONET_REQUIRE(g.act.aP_bs >= n / per && (!g.act.a || g.act.a_bs >= n) && (!g.pool.yP || g.pool.yP_bs >= np / per) && (!g.pool.y || g.pool.y_bs >= np),
+                     "%s: batch stride too small", entry);
+    } else if (e.epi == EvEpi::Head) {
+        ONET_REQUIRE(aligned(g.head.L, g.head.L_bs, 16) && aligned(g.head.V, 0, 16), "%s: 16-byte aligned rows required", entry);
+        ONET_REQUIRE(g.head.L_bs >= n, "%s: batch stride too small", entry);
+    } else {
+        ONET_REQUIRE(aligned(g.plain.z, g.plain.z_bs, 16), "%s: 16-byte aligned rows required", entry);
+        ONET_REQUIRE(g.plain.z_bs >= n, "%s: batch stride too small", entry);
+    }
+    SpPreArgs p{g.xs, g.xs_bs, (const __bf16*)g.wq, g.plain.z, g.plain.z_bs, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)g.in.x_amax,
+                g.in.scale_always, (const unsigned*)g.in.x_amax2, g.in.split_ch};
+    p.act_save = g.save;
+    if (act) {
+        p.zP = g.act.aP;
+        p.zP_bs = g.act.aP_bs;
+        p.zP_ch0 = 0;
+        p.zP_slots = (const unsigned*)g.act.aP_slots;
+        p.act_amax = (unsigned*)g.act.a_amax;
+        p.act_a = g.act.a;
+        p.act_a_bs = g.act.a_bs;
+    }
+    if (pool) {
+        p.pl_P = g.pool.yP;
+        p.pl_P_bs = g.pool.yP_bs;
+        p.pl_y = g.pool.y;
+        p.pl_y_bs = g.pool.y_bs;
+    } else if (e.epi == EvEpi::Head) {
+        p.hd_L = g.head.L;
+        p.hd_L_bs = g.head.L_bs;
+        p.hd_V = g.head.V;
+    }
+    // the instances that exist: <ST, PM, W16, RD, ACT, HEAD, POOL, RAG, ANY>.  A map of full tiles takes the full-tile instance from every entry
+    hipStream_t st = as_stream(g.stream);
+    const bool pairs = map == EvMap::Pairs, any = map == EvMap::AnyMap, rag = map == EvMap::Ragged && !pre_map_ok(false, H, W);
+    if (one) {
+        if (e.epi == EvEpi::Plain) return launch_split_pre<false, 2, false>(p, st);
+        if (e.epi == EvEpi::Head) return launch_split_pre<false, 2, false, false, false, true>(p, st);
+        if (pool && any) return launch_split_pre<false, 2, false, false, true, false, true, false, true>(p, st);
+        if (pool && rag) return launch_split_pre<false, 2, false, false, true, false, true, true>(p, st);
+        if (pool) return launch_split_pre<false, 2, false, false, true, false, true>(p, st);
+        if (pairs) return launch_split_pre<false, 2, true, false, true>(p, st);
+        if (any) return launch_split_pre<false, 2, false, false, true, false, false, false, true>(p, st);
+        return launch_split_pre<false, 2, false, false, true>(p, st);       // (Act: one instance on full tiles and ragged maps)
+    }
+    if (e.epi == EvEpi::Plain) return launch_split_pre<false, 1, false>(p, st);
+    if (e.epi == EvEpi::Head) return launch_split_pre<false, 1, false, false, false, true>(p, st);
+    if (pool && rag) return launch_split_pre<false, 1, false, false, true, false, true, true>(p, st);
+    if (pool) return launch_split_pre<false, 1, false, false, true, false, true>(p, st);
+    if (pairs) return launch_split_pre<false, 1, true, false, true, false, false, true>(p, st);
+    if (rag) return launch_split_pre<false, 1, false, false, true, false, false, true>(p, st);
+    return launch_split_pre<false, 1, false, false, true>(p, st);
 }
 
 int onet_conv3x3_split_fwd_pre_act(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
                                    const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
                                    int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
-    return split_pre_act_impl("conv3x3_split_fwd_pre_act", false, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, aP, aP_bs, aP_slots,
-                              a_amax, a, a_bs, B, Cin, Cout, H, W, stream);
+    return eval_conv({"conv3x3_split_fwd_pre_act", 2, EvMap::Full, EvEpi::Act}, {xs, xs_bs, {x_amax, scale_always, x_amax2, split_ch}, wq, save,
+                     {aP, aP_bs, aP_slots, a_amax, a, a_bs}, {}, {}, {}, B, Cin, Cout, H, W, stream});
 }
 
-// ... on a ragged map (pre_map_ok; include/onet_hip_ragged_split.h): the full-tile entry on the map zero-padded to whole tiles, value for
-// value on the map, nothing written outside it; a_amax receives the maximum over the MAP's pixels (the RAG instance's masked record).
-// Returns 1 (nothing launched) for odd H, W % 4, Cin % 16 or Cout % 64.
 int onet_conv3x3_split_fwd_pre_act_ragged(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
                                           const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
                                           int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
-    return split_pre_act_impl("conv3x3_split_fwd_pre_act_ragged", true, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, aP, aP_bs,
-                              aP_slots, a_amax, a, a_bs, B, Cin, Cout, H, W, stream);
+    return eval_conv({"conv3x3_split_fwd_pre_act_ragged", 2, EvMap::Ragged, EvEpi::Act}, {xs, xs_bs, {x_amax, scale_always, x_amax2, split_ch}, wq, save,
+                     {aP, aP_bs, aP_slots, a_amax, a, a_bs}, {}, {}, {}, B, Cin, Cout, H, W, stream});
 }
 
-// ... on IMAGE-PAIR tiles (include/onet_hip_split_pairs.h, round 18): maps of any H and 0 < W <= 16 -- the bottom level of the fp32-level
-// eval plan (16 x 16, 14 x 14) -- two images side by side in a tile's 32 columns, each with its own halo columns (SpPreCfg<true>), where
-// the ragged entry walks one half-empty tile per image.  On the map, value for value, what that entry writes (on the map zero-padded to
-// its domain): the same chunks and taps in the same order per pixel, the same epilogue expressions, the same 2^k.  a_amax receives the
-// maximum over the map's pixels of the batch's own images.  Any batch size: the last tile of an odd one holds one image.  Returns 1
-// (nothing launched, nothing written) for W > 16, Cin % 16, Cout % 64 or an image pair beyond the buffer-resource range.
 int onet_conv3x3_split_fwd_pre_act_pairs(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
                                          const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
                                          int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
-    const char* entry = "conv3x3_split_fwd_pre_act_pairs";
-    ONET_REQUIRE(xs && wq && save && aP && aP_slots, "%s: null pointer", entry);
-    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
-    if (W > 16 || (Cin % 16) || (Cout % 64)) return 1;
-    // a tile's buffer resource spans an image pair: the batch stride, then one image and the chunk the staging runs ahead by
-    if ((int64_t)(Cin + 32) * 2 * 9 * Cout * 2 >= (1ll << 31) || xs_bs > (1ll << 29) || xs_bs * 4 + (int64_t)(Cin + 32) * H * W * 4 >= (1ll << 31))
-        return 1;
-    ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
-    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 1, Cin, Cout, H, W)) return rc;
-    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "%s: 16-byte aligned slots required", entry);
-    ONET_REQUIRE(!a || (reinterpret_cast<uintptr_t>(a) & 3) == 0, "%s: 4-byte aligned floats required", entry);
-    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W && (!a || a_bs >= (int64_t)Cout * H * W), "%s: batch stride too small", entry);
-    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)x_amax, scale_always,
-                (const unsigned*)x_amax2, split_ch};
-    p.zP = aP;
-    p.zP_bs = aP_bs;
-    p.zP_ch0 = 0;
-    p.zP_slots = (const unsigned*)aP_slots;
-    p.act_save = save;
-    p.act_amax = (unsigned*)a_amax;
-    p.act_a = a;
-    p.act_a_bs = a_bs;
-    return launch_split_pre<false, 1, true, false, true, false, false, true>(p, as_stream(stream));
+    return eval_conv({"conv3x3_split_fwd_pre_act_pairs", 2, EvMap::Pairs, EvEpi::Act}, {xs, xs_bs, {x_amax, scale_always, x_amax2, split_ch}, wq, save,
+                     {aP, aP_bs, aP_slots, a_amax, a, a_bs}, {}, {}, {}, B, Cin, Cout, H, W, stream});
 }
 
-// The plain forward of onet_conv3x3_split_fwd_pre(wq_f16 = 1, fp32 z, no statistics) on a ragged map: the fp16 plan's last unit where
-// no head epilogue follows.  x_amax / scale_always / x_amax2 / split_ch: the operand's magnitude slots, as there.  Returns 1 (nothing
-// launched) outside the ragged domain.
 int onet_conv3x3_split_fwd_pre_plain_ragged(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
                                             const void* wq, float* z, int64_t z_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
-    const char* entry = "conv3x3_split_fwd_pre_plain_ragged";
-    ONET_REQUIRE(xs && wq && z, "%s: null pointer", entry);
-    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
-    if (!pre_map_ok(true, H, W) || (Cin % 16) || (Cout % 64)) return 1;
-    ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
-    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 1, Cin, Cout, H, W)) return rc;
-    ONET_REQUIRE((z_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0, "%s: 16-byte aligned rows required", entry);
-    ONET_REQUIRE(z_bs >= (int64_t)Cout * H * W, "%s: batch stride too small", entry);
-    SpPreArgs a{xs, xs_bs, (const __bf16*)wq, z, z_bs, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)x_amax, scale_always,
-                (const unsigned*)x_amax2, split_ch};
-    return launch_split_pre<false, 1, false>(a, as_stream(stream));
-}
-
-// Eval-mode inference on PLAIN bf16 operands (one part, unscaled: bf16 has fp32's exponent range, so no magnitude slots, bound or guard):
-// the forward convolution of onet_conv3x3_split_fwd_pre (wq_f16 = 2) with the fixed BatchNorm + ReLU of `save` [4][Cout]
-// (onet_bn_eval_coeffs) in the epilogue and the activation leaving as slots: aP [B][Cout/8][H][W][8] bf16 (round to nearest even), batch
-// stride aP_bs in 4-byte units (the leading channel groups of a concat buffer qualify).  a_amax (may be NULL): magnitude slots that
-// receive the exact max a; a (may be NULL): the activation as fp32 NCHW too.  Bit for bit what the plain launch (fp32 z) followed by
-// onet_bn_relu_apply_split(nparts = 1) writes; z itself is never stored.  Returns 1 (nothing launched) where the map is not made of full
-// 16 x 32 tiles, Cin is not a multiple of 32 or Cout not one of 64.
-// The maps an eval-mode entry takes: made of full 16 x 32 tiles, or -- the _ragged entries of include/onet_hip_ragged.h (round 13,
-// one-part operands) and include/onet_hip_ragged_split.h (round 14, fp16 hi | mid parts) -- any map of even H and W % 4 == 0 below
-// 2^24 pixels: the tile counts are cdiv, the staging gives every
-// out-of-map slot the out-of-range offset and every store is guarded per slot / float4 / pooled float2.  With H and W even and tiles
-// starting on even coordinates a 2 x 2 pooling window is wholly inside the map or wholly outside.
-static bool pre_map_ok(bool ragged, int H, int W) {
-    if (ragged) return !((H & 1) || (W & 3) || (int64_t)H * W >= (1 << 24));
-    return !(W < 32 || (W % 32) || (H % 16));
-}
-// The exact-maximum record of the activation epilogue covers a tile's out-of-map accumulators too: the ragged entries do not take one
-#define ONET_RAGGED_NO_AMAX(entry, ragged, a_amax) \
-    ONET_REQUIRE(!(ragged) || !(a_amax), "%s: the ragged entry records no exact maximum (a_amax must be NULL)", entry)
-
-static int plain16_pre_act_impl(const char* entry, bool ragged, const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP,
-                                int64_t aP_bs, void* a_amax, float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
-    ONET_REQUIRE(xs && wq && save && aP, "%s: null pointer", entry);
-    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
-    if (!pre_map_ok(ragged, H, W) || (Cin % 32) || (Cout % 64)) return 1;
-    ONET_RAGGED_NO_AMAX(entry, ragged, a_amax);
-    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 2, Cin, Cout, H, W)) return rc;
-    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "%s: 16-byte aligned slots required", entry);
-    ONET_REQUIRE(!a || ((a_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0), "%s: 16-byte aligned rows required", entry);
-    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W / 2 && (!a || a_bs >= (int64_t)Cout * H * W), "%s: batch stride too small", entry);
-    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, nullptr, 0, nullptr, 0};
-    p.zP = aP;
-    p.zP_bs = aP_bs;
-    p.zP_ch0 = 0;
-    p.act_save = save;
-    p.act_amax = (unsigned*)a_amax;
-    p.act_a = a;
-    p.act_a_bs = a_bs;
-    return launch_split_pre<false, 2, false, false, true>(p, as_stream(stream));
-}
-
-int onet_conv3x3_plain16_fwd_pre_act(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs, void* a_amax,
-                                     float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
-    return plain16_pre_act_impl("conv3x3_plain16_fwd_pre_act", false, xs, xs_bs, wq, save, aP, aP_bs, a_amax, a, a_bs, B, Cin, Cout, H, W, stream);
-}
-
-// The same launch on a ragged map (pre_map_ok): the full-tile entry on the map zero-padded to whole tiles, value for value on the map,
-// nothing written outside it.  Returns 1 (nothing launched) for odd H, W % 4, Cin % 32 or Cout % 64.
-int onet_conv3x3_plain16_fwd_pre_act_ragged(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
-                                            void* a_amax, float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
-    return plain16_pre_act_impl("conv3x3_plain16_fwd_pre_act_ragged", true, xs, xs_bs, wq, save, aP, aP_bs, a_amax, a, a_bs, B, Cin, Cout, H, W,
-                                stream);
-}
-
-// The plain forward of onet_conv3x3_split_fwd_pre(wq_f16 = 2, fp32 z, no statistics) on a ragged map: the one-part plan's last unit
-// where no head epilogue follows.  Returns 1 (nothing launched) outside the ragged domain.
-int onet_conv3x3_plain16_fwd_pre_plain_ragged(const void* xs, int64_t xs_bs, const void* wq, float* z, int64_t z_bs, int B, int Cin, int Cout,
-                                              int H, int W, void* stream) {
-    const char* entry = "conv3x3_plain16_fwd_pre_plain_ragged";
-    ONET_REQUIRE(xs && wq && z, "%s: null pointer", entry);
-    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
-    if (!pre_map_ok(true, H, W) || (Cin % 32) || (Cout % 64)) return 1;
-    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 2, Cin, Cout, H, W)) return rc;
-    ONET_REQUIRE((z_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0, "%s: 16-byte aligned rows required", entry);
-    ONET_REQUIRE(z_bs >= (int64_t)Cout * H * W, "%s: batch stride too small", entry);
-    SpPreArgs a{xs, xs_bs, (const __bf16*)wq, z, z_bs, B, Cin, Cout, H, W, 0, 0, 0, nullptr, nullptr, 0, nullptr, 0};
-    return launch_split_pre<false, 2, false>(a, as_stream(stream));
-}
-
-// Eval-mode inference, an encoder block's second unit: the _act entries above with the 2 x 2 max-pooling of the activation in the same
-// epilogue (SpPreArgs::pl_*).  Everything the _act entry writes is written as it writes it -- aP (the leading channel groups of a concat
-// buffer qualify), a, a_amax -- plus the pooled tensor m = max over each 2 x 2 window of relu(bn(z)): as slots yP [B][Cout/8][H/2][parts]
-// [W/2][8] (fp16: the parts of 2^k m with aP's k; plain bf16: one part, unscaled; batch stride yP_bs in 4-byte units), as fp32 y
-// [B][Cout][H/2][W/2] (batch stride y_bs), or both; at least one.  Bit for bit what the plain launch followed by
-// onet_bn_relu_apply_pool_split writes.  Returns 1 (nothing launched) outside the _act entry's domain.
-static int pre_act_pool_impl(const char* entry, bool ragged, int wq_f16, const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2,
-                             int split_ch, const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
-                             int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
-    ONET_REQUIRE(xs && wq && save && aP && (aP_slots || wq_f16 == 2), "%s: null pointer", entry);
-    ONET_REQUIRE(yP || y, "%s: a pooled destination is required (yP, y or both)", entry);
-    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
-    if (!pre_map_ok(ragged, H, W) || (Cin % (wq_f16 == 2 ? 32 : 16)) || (Cout % 64)) return 1;
-    // (the one-part ragged instance records no maximum; the fp16 one -- round 14 -- masks its record to the map)
-    ONET_RAGGED_NO_AMAX(entry, ragged && wq_f16 == 2, a_amax);
-    ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
-    if (const int rc = pre_operand_checks(entry, xs, xs_bs, wq_f16, Cin, Cout, H, W)) return rc;
-    const int64_t n = (int64_t)Cout * H * W, per = wq_f16 == 2 ? 2 : 1;       // slot elements per 4-byte unit: one bf16 part / two fp16 parts
-    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0 && (!yP || ((yP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(yP) & 15) == 0)),
-                 "%s: 16-byte aligned slots required", entry);
-    ONET_REQUIRE((!a || ((a_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0)) && (!y || ((y_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0)),
-                 "%s: 16-byte aligned rows required", entry);
-    ONET_REQUIRE(aP_bs >= n / per && (!a || a_bs >= n) && (!yP || yP_bs >= n / 4 / per) && (!y || y_bs >= n / 4), "%s: batch stride too small", entry);
-    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)x_amax, scale_always,
-                (const unsigned*)x_amax2, split_ch};
-    p.zP = aP;
-    p.zP_bs = aP_bs;
-    p.zP_ch0 = 0;
-    p.zP_slots = (const unsigned*)aP_slots;
-    p.act_save = save;
-    p.act_amax = (unsigned*)a_amax;
-    p.act_a = a;
-    p.act_a_bs = a_bs;
-    p.pl_P = yP;
-    p.pl_P_bs = yP_bs;
-    p.pl_y = y;
-    p.pl_y_bs = y_bs;
-    // a map of full tiles takes the full-tile instance from either entry: the same launch, the same bits
-    if (ragged && !pre_map_ok(false, H, W)) {
-        if (wq_f16 == 2) return launch_split_pre<false, 2, false, false, true, false, true, true>(p, as_stream(stream));
-        return launch_split_pre<false, 1, false, false, true, false, true, true>(p, as_stream(stream));
-    }
-    if (wq_f16 == 2) return launch_split_pre<false, 2, false, false, true, false, true>(p, as_stream(stream));
-    return launch_split_pre<false, 1, false, false, true, false, true>(p, as_stream(stream));
-}
-
-int onet_conv3x3_plain16_fwd_pre_act_pool(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs, void* a_amax,
-                                          float* a, int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin, int Cout, int H,
-                                          int W, void* stream) {
-    return pre_act_pool_impl("conv3x3_plain16_fwd_pre_act_pool", false, 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, aP, aP_bs, nullptr, a_amax, a,
-                             a_bs, yP, yP_bs, y, y_bs, B, Cin, Cout, H, W, stream);
-}
-
-// ... on a ragged map (pre_map_ok; H / 2 x W / 2 pooled maps, pooled fp32 rows of W / 2 floats): see onet_conv3x3_plain16_fwd_pre_act_ragged
-int onet_conv3x3_plain16_fwd_pre_act_pool_ragged(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
-                                                 void* a_amax, float* a, int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B,
-                                                 int Cin, int Cout, int H, int W, void* stream) {
-    return pre_act_pool_impl("conv3x3_plain16_fwd_pre_act_pool_ragged", true, 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, aP, aP_bs, nullptr,
-                             a_amax, a, a_bs, yP, yP_bs, y, y_bs, B, Cin, Cout, H, W, stream);
-}
-
-// The one-part _act / _act_pool entries on maps of ANY H and W (include/onet_hip_anymap.h, round 15): the levels below the first of an
-// input such as 200 x 200 (50 x 50: W % 4 == 2; 25 x 25: odd).  Domain: H, W > 0, H W < 2^24, Cin % 32 == 0, Cout % 64 == 0, inside
-// the buffer-resource range, a_amax NULL; outside it 1, nothing launched.  A map the ragged entry takes goes to that entry's own
-// launch (on full tiles the full-tile instance); every other map to the ANY instance, whose fp32 side outputs are stored float by
-// float.  pool: the pooled maps are H / 2 x W / 2, rounded DOWN (nn.MaxPool2d(2)), and the stride checks use those sizes.
-static bool anymap_domain(const void* a_amax, int Cin, int Cout, int H, int W) {
-    return !a_amax && (int64_t)H * W < (1 << 24) && !(Cin % 32) && !(Cout % 64) && (int64_t)(Cin + 32) * H * W * 4 < (1ll << 31) &&
-           (int64_t)(Cin + 32) * 2 * 9 * Cout * 2 < (1ll << 31);
-}
-
-int onet_conv3x3_plain16_fwd_pre_act_anymap(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
-                                            void* a_amax, float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
-    const char* entry = "conv3x3_plain16_fwd_pre_act_anymap";
-    ONET_REQUIRE(xs && wq && save && aP, "%s: null pointer", entry);
-    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
-    if (!anymap_domain(a_amax, Cin, Cout, H, W)) return 1;
-    if (pre_map_ok(true, H, W)) return plain16_pre_act_impl(entry, true, xs, xs_bs, wq, save, aP, aP_bs, nullptr, a, a_bs, B, Cin, Cout, H, W, stream);
-    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 2, Cin, Cout, H, W)) return rc;
-    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "%s: 16-byte aligned slots required", entry);
-    ONET_REQUIRE(!a || (reinterpret_cast<uintptr_t>(a) & 3) == 0, "%s: 4-byte aligned floats required", entry);
-    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W / 2 && (!a || a_bs >= (int64_t)Cout * H * W), "%s: batch stride too small", entry);
-    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, nullptr, 0, nullptr, 0};
-    p.zP = aP;
-    p.zP_bs = aP_bs;
-    p.zP_ch0 = 0;
-    p.act_save = save;
-    p.act_a = a;
-    p.act_a_bs = a_bs;
-    return launch_split_pre<false, 2, false, false, true, false, false, false, true>(p, as_stream(stream));
-}
-
-int onet_conv3x3_plain16_fwd_pre_act_pool_anymap(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
-                                                 void* a_amax, float* a, int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B,
-                                                 int Cin, int Cout, int H, int W, void* stream) {
-    const char* entry = "conv3x3_plain16_fwd_pre_act_pool_anymap";
-    ONET_REQUIRE(xs && wq && save && aP, "%s: null pointer", entry);
-    ONET_REQUIRE(yP || y, "%s: a pooled destination is required (yP, y or both)", entry);
-    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
-    if (!anymap_domain(a_amax, Cin, Cout, H, W)) return 1;
-    if (pre_map_ok(true, H, W))
-        return pre_act_pool_impl(entry, true, 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, aP, aP_bs, nullptr, nullptr, a, a_bs, yP, yP_bs, y, y_bs, B,
-                                 Cin, Cout, H, W, stream);
-    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 2, Cin, Cout, H, W)) return rc;
-    const int64_t n = (int64_t)Cout * H * W, np = (int64_t)Cout * (H >> 1) * (W >> 1);      // floor pooling
-    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0 && (!yP || ((yP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(yP) & 15) == 0)),
-                 "%s: 16-byte aligned slots required", entry);
-    ONET_REQUIRE((!a || (reinterpret_cast<uintptr_t>(a) & 3) == 0) && (!y || (reinterpret_cast<uintptr_t>(y) & 3) == 0), "%s: 4-byte aligned floats required",
-                 entry);
-    ONET_REQUIRE(aP_bs >= n / 2 && (!a || a_bs >= n) && (!yP || yP_bs >= np / 2) && (!y || y_bs >= np), "%s: batch stride too small", entry);
-    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, nullptr, 0, nullptr, 0};
-    p.zP = aP;
-    p.zP_bs = aP_bs;
-    p.zP_ch0 = 0;
-    p.act_save = save;
-    p.act_a = a;
-    p.act_a_bs = a_bs;
-    p.pl_P = yP;
-    p.pl_P_bs = yP_bs;
-    p.pl_y = y;
-    p.pl_y_bs = y_bs;
-    return launch_split_pre<false, 2, false, false, true, false, true, false, true>(p, as_stream(stream));
-}
-
-// The one-part _act entry on IMAGE-PAIR tiles (include/onet_hip_pairs.h, round 16): maps of any H and 0 < W <= 16 -- the bottom level of
-// the eval plan (16 x 16, 14 x 14, 12 x 12) -- two images side by side in a tile's 32 columns, each with its own halo columns
-// (SpPreCfg<true>), where the any-map entry walks one half-empty tile per image.  On the map, value for value, what that entry writes:
-// the same chunks and taps in the same order per pixel, the same epilogue expressions.  Any batch size: the last tile of an odd one
-// holds one image.  Returns 1 (nothing launched, nothing written) for W > 16, Cin % 32, Cout % 64, a non-NULL a_amax or an image pair
-// beyond the buffer-resource range.
-int onet_conv3x3_plain16_fwd_pre_act_pairs(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
-                                           void* a_amax, float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
-    const char* entry = "conv3x3_plain16_fwd_pre_act_pairs";
-    ONET_REQUIRE(xs && wq && save && aP, "%s: null pointer", entry);
-    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
-    if (W > 16 || !anymap_domain(a_amax, Cin, Cout, H, W)) return 1;
-    // a tile's buffer resource spans an image pair: the batch stride, then one image and the chunk the staging runs ahead by
-    if (xs_bs > (1ll << 29) || xs_bs * 4 + (int64_t)(Cin + 32) * H * W * 4 >= (1ll << 31)) return 1;
-    if (const int rc = pre_operand_checks(entry, xs, xs_bs, 2, Cin, Cout, H, W)) return rc;
-    ONET_REQUIRE((aP_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(aP) & 15) == 0, "%s: 16-byte aligned slots required", entry);
-    ONET_REQUIRE(!a || (reinterpret_cast<uintptr_t>(a) & 3) == 0, "%s: 4-byte aligned floats required", entry);
-    ONET_REQUIRE(aP_bs >= (int64_t)Cout * H * W / 2 && (!a || a_bs >= (int64_t)Cout * H * W), "%s: batch stride too small", entry);
-    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, nullptr, 0, nullptr, 0};
-    p.zP = aP;
-    p.zP_bs = aP_bs;
-    p.zP_ch0 = 0;
-    p.act_save = save;
-    p.act_a = a;
-    p.act_a_bs = a_bs;
-    return launch_split_pre<false, 2, true, false, true>(p, as_stream(stream));
+    return eval_conv({"conv3x3_split_fwd_pre_plain_ragged", 2, EvMap::Ragged, EvEpi::Plain}, {xs, xs_bs, {x_amax, scale_always, x_amax2, split_ch}, wq,
+                     nullptr, {}, {}, {}, {z, z_bs}, B, Cin, Cout, H, W, stream});
 }
 
 int onet_conv3x3_split_fwd_pre_act_pool(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
                                         const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots, void* a_amax, float* a,
                                         int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin, int Cout, int H, int W,
                                         void* stream) {
-    return pre_act_pool_impl("conv3x3_split_fwd_pre_act_pool", false, 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, aP, aP_bs, aP_slots,
-                             a_amax, a, a_bs, yP, yP_bs, y, y_bs, B, Cin, Cout, H, W, stream);
+    return eval_conv({"conv3x3_split_fwd_pre_act_pool", 2, EvMap::Full, EvEpi::Pool}, {xs, xs_bs, {x_amax, scale_always, x_amax2, split_ch}, wq, save,
+                     {aP, aP_bs, aP_slots, a_amax, a, a_bs}, {yP, yP_bs, y, y_bs}, {}, {}, B, Cin, Cout, H, W, stream});
 }
 
-// ... on a ragged map (pre_map_ok; H / 2 x W / 2 pooled maps): see onet_conv3x3_split_fwd_pre_act_ragged -- a_amax is taken, masked to the map
 int onet_conv3x3_split_fwd_pre_act_pool_ragged(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2,
                                                int split_ch, const void* wq, const float* save, void* aP, int64_t aP_bs, const void* aP_slots,
                                                void* a_amax, float* a, int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin,
                                                int Cout, int H, int W, void* stream) {
-    return pre_act_pool_impl("conv3x3_split_fwd_pre_act_pool_ragged", true, 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, aP, aP_bs,
-                             aP_slots, a_amax, a, a_bs, yP, yP_bs, y, y_bs, B, Cin, Cout, H, W, stream);
-}
-
-// Labels-only inference: the model's LAST unit with the head in the convolution's epilogue (SpPreArgs::hd_*).  The two entries below run
-// the forward convolution of the _act entries above on the same operands, form h = max(0, fma(z - mean, sc, sh)) from save [4][Cout] on
-// the accumulators and write V [B][H][W] = sum_c L[c] h[c] (L: fp32 NCHW, batch stride L_bs) -- nothing else: neither z nor h is stored.
-// Returns 1 (nothing launched, nothing written) outside maps made of full 16 x 32 tiles, Cin % 32 (plain bf16) / % 16 (fp16), Cout == 64.
-static int pre_head_impl(const char* entry, bool ragged, int wq_f16, const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2,
-                         int split_ch, const void* wq, const float* save, const float* L, int64_t L_bs, float* V, int B, int Cin, int Cout,
-                         int H, int W, void* stream) {
-    ONET_REQUIRE(xs && wq && save && L && V, "%s: null pointer", entry);
-    ONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", entry);
-    if (!pre_map_ok(ragged, H, W) || (Cin % (wq_f16 == 2 ? 32 : 16)) || Cout != 64) return 1;
-    ONET_REQUIRE(split_ch >= 0 && split_ch < Cin && (split_ch % 32) == 0, "%s: split_ch must be a multiple of 32 inside Cin", entry);
-    ONET_REQUIRE((L_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(L) & 15) == 0 && (reinterpret_cast<uintptr_t>(V) & 15) == 0,
-                 "%s: 16-byte aligned rows required", entry);
-    if (const int rc = pre_operand_checks(entry, xs, xs_bs, wq_f16, Cin, Cout, H, W)) return rc;
-    ONET_REQUIRE(L_bs >= (int64_t)Cout * H * W, "%s: batch stride too small", entry);
-    SpPreArgs p{xs, xs_bs, (const __bf16*)wq, nullptr, 0, B, Cin, Cout, H, W, 0, 0, 0, nullptr, (const unsigned*)x_amax, scale_always,
-                (const unsigned*)x_amax2, split_ch};
-    p.act_save = save;
-    p.hd_L = L;
-    p.hd_L_bs = L_bs;
-    p.hd_V = V;
-    if (wq_f16 == 2) return launch_split_pre<false, 2, false, false, false, true>(p, as_stream(stream));
-    return launch_split_pre<false, 1, false, false, false, true>(p, as_stream(stream));
-}
-
-int onet_conv3x3_plain16_fwd_pre_head(const void* xs, int64_t xs_bs, const void* wq, const float* save, const float* L, int64_t L_bs, float* V,
-                                      int B, int Cin, int Cout, int H, int W, void* stream) {
-    return pre_head_impl("conv3x3_plain16_fwd_pre_head", false, 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, L, L_bs, V, B, Cin, Cout, H, W, stream);
-}
-
-// ... on a ragged map (pre_map_ok): the L loads and the V store are guarded per float4; see onet_conv3x3_plain16_fwd_pre_act_ragged
-int onet_conv3x3_plain16_fwd_pre_head_ragged(const void* xs, int64_t xs_bs, const void* wq, const float* save, const float* L, int64_t L_bs,
-                                             float* V, int B, int Cin, int Cout, int H, int W, void* stream) {
-    return pre_head_impl("conv3x3_plain16_fwd_pre_head_ragged", true, 2, xs, xs_bs, nullptr, 0, nullptr, 0, wq, save, L, L_bs, V, B, Cin, Cout, H, W,
-                         stream);
+    return eval_conv({"conv3x3_split_fwd_pre_act_pool_ragged", 2, EvMap::Ragged, EvEpi::Pool}, {xs, xs_bs, {x_amax, scale_always, x_amax2, split_ch}, wq,
+                     save, {aP, aP_bs, aP_slots, a_amax, a, a_bs}, {yP, yP_bs, y, y_bs}, {}, {}, B, Cin, Cout, H, W, stream});
 }
 
 int onet_conv3x3_split_fwd_pre_head(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
                                     const void* wq, const float* save, const float* L, int64_t L_bs, float* V, int B, int Cin, int Cout, int H,
                                     int W, void* stream) {
-    return pre_head_impl("conv3x3_split_fwd_pre_head", false, 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, L, L_bs, V, B, Cin, Cout,
-                         H, W, stream);
+    return eval_conv({"conv3x3_split_fwd_pre_head", 2, EvMap::Full, EvEpi::Head}, {xs, xs_bs, {x_amax, scale_always, x_amax2, split_ch}, wq, save, {}, {},
+                     {L, L_bs, V}, {}, B, Cin, Cout, H, W, stream});
 }
 
-// ... on a ragged map (pre_map_ok): the L loads and the V store are guarded per float4, the staging per slot
 int onet_conv3x3_split_fwd_pre_head_ragged(const void* xs, int64_t xs_bs, const void* x_amax, int scale_always, const void* x_amax2, int split_ch,
                                            const void* wq, const float* save, const float* L, int64_t L_bs, float* V, int B, int Cin, int Cout,
                                            int H, int W, void* stream) {
-    return pre_head_impl("conv3x3_split_fwd_pre_head_ragged", true, 1, xs, xs_bs, x_amax, scale_always, x_amax2, split_ch, wq, save, L, L_bs, V, B, Cin,
-                         Cout, H, W, stream);
+    return eval_conv({"conv3x3_split_fwd_pre_head_ragged", 2, EvMap::Ragged, EvEpi::Head}, {xs, xs_bs, {x_amax, scale_always, x_amax2, split_ch}, wq, save,
+                     {}, {}, {L, L_bs, V}, {}, B, Cin, Cout, H, W, stream});
+}
+
+int onet_conv3x3_plain16_fwd_pre_act(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs, void* a_amax,
+                                     float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    return eval_conv({"conv3x3_plain16_fwd_pre_act", 1, EvMap::Full, EvEpi::Act}, {xs, xs_bs, {}, wq, save, {aP, aP_bs, nullptr, a_amax, a, a_bs}, {}, {}, {},
+                     B, Cin, Cout, H, W, stream});
+}
+
+int onet_conv3x3_plain16_fwd_pre_act_ragged(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
+                                            void* a_amax, float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    return eval_conv({"conv3x3_plain16_fwd_pre_act_ragged", 1, EvMap::Ragged, EvEpi::Act}, {xs, xs_bs, {}, wq, save, {aP, aP_bs, nullptr, a_amax, a, a_bs}, {},
+                     {}, {}, B, Cin, Cout, H, W, stream});
+}
+
+int onet_conv3x3_plain16_fwd_pre_act_anymap(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
+                                            void* a_amax, float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    return eval_conv({"conv3x3_plain16_fwd_pre_act_anymap", 1, EvMap::AnyMap, EvEpi::Act}, {xs, xs_bs, {}, wq, save, {aP, aP_bs, nullptr, a_amax, a, a_bs}, {},
+                     {}, {}, B, Cin, Cout, H, W, stream});
+}
+
+int onet_conv3x3_plain16_fwd_pre_act_pairs(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
+                                           void* a_amax, float* a, int64_t a_bs, int B, int Cin, int Cout, int H, int W, void* stream) {
+    return eval_conv({"conv3x3_plain16_fwd_pre_act_pairs", 1, EvMap::Pairs, EvEpi::Act}, {xs, xs_bs, {}, wq, save, {aP, aP_bs, nullptr, a_amax, a, a_bs}, {},
+                     {}, {}, B, Cin, Cout, H, W, stream});
+}
+
+int onet_conv3x3_plain16_fwd_pre_plain_ragged(const void* xs, int64_t xs_bs, const void* wq, float* z, int64_t z_bs, int B, int Cin, int Cout,
+                                              int H, int W, void* stream) {
+    return eval_conv({"conv3x3_plain16_fwd_pre_plain_ragged", 1, EvMap::Ragged, EvEpi::Plain}, {xs, xs_bs, {}, wq, nullptr, {}, {}, {}, {z, z_bs}, B, Cin,
+                     Cout, H, W, stream});
+}
+
+int onet_conv3x3_plain16_fwd_pre_act_pool(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs, void* a_amax,
+                                          float* a, int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B, int Cin, int Cout, int H,
+                                          int W, void* stream) {
+    return eval_conv({"conv3x3_plain16_fwd_pre_act_pool", 1, EvMap::Full, EvEpi::Pool}, {xs, xs_bs, {}, wq, save, {aP, aP_bs, nullptr, a_amax, a, a_bs},
+                     {yP, yP_bs, y, y_bs}, {}, {}, B, Cin, Cout, H, W, stream});
+}
+
+int onet_conv3x3_plain16_fwd_pre_act_pool_ragged(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
+                                                 void* a_amax, float* a, int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B,
+                                                 int Cin, int Cout, int H, int W, void* stream) {
+    return eval_conv({"conv3x3_plain16_fwd_pre_act_pool_ragged", 1, EvMap::Ragged, EvEpi::Pool}, {xs, xs_bs, {}, wq, save,
+                     {aP, aP_bs, nullptr, a_amax, a, a_bs}, {yP, yP_bs, y, y_bs}, {}, {}, B, Cin, Cout, H, W, stream});
+}
+
+int onet_conv3x3_plain16_fwd_pre_act_pool_anymap(const void* xs, int64_t xs_bs, const void* wq, const float* save, void* aP, int64_t aP_bs,
+                                                 void* a_amax, float* a, int64_t a_bs, void* yP, int64_t yP_bs, float* y, int64_t y_bs, int B,
+                                                 int Cin, int Cout, int H, int W, void* stream) {
+    return eval_conv({"conv3x3_plain16_fwd_pre_act_pool_anymap", 1, EvMap::AnyMap, EvEpi::Pool}, {xs, xs_bs, {}, wq, save,
+                     {aP, aP_bs, nullptr, a_amax, a, a_bs}, {yP, yP_bs, y, y_bs}, {}, {}, B, Cin, Cout, H, W, stream});
+}
+
+int onet_conv3x3_plain16_fwd_pre_head(const void* xs, int64_t xs_bs, const void* wq, const float* save, const float* L, int64_t L_bs, float* V,
+                                      int B, int Cin, int Cout, int H, int W, void* stream) {
+    return eval_conv({"conv3x3_plain16_fwd_pre_head", 1, EvMap::Full, EvEpi::Head}, {xs, xs_bs, {}, wq, save, {}, {}, {L, L_bs, V}, {}, B, Cin, Cout, H, W,
+                     stream});
+}
+
+int onet_conv3x3_plain16_fwd_pre_head_ragged(const void* xs, int64_t xs_bs, const void* wq, const float* save, const float* L, int64_t L_bs,
+                                             float* V, int B, int Cin, int Cout, int H, int W, void* stream) {
+    return eval_conv({"conv3x3_plain16_fwd_pre_head_ragged", 1, EvMap::Ragged, EvEpi::Head}, {xs, xs_bs, {}, wq, save, {}, {}, {L, L_bs, V}, {}, B, Cin, Cout,
+                     H, W, stream});
 }
 
 // a[co] = relu(sc (z - mean) + sh) with |z[co]| <= sum_ci |w[co][ci][.]| max |x[ci]|:  |a[co]| <= |sc| (S1 max1 + S2 max2) + |sh - mean sc|,

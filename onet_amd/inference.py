@@ -1,11 +1,56 @@
 """Fused eval-mode inference (Settings.fused_eval): a straight-line forward plan on the pre-split kernels.
 
 In eval BatchNorm is a fixed per-channel affine map, so `relu(bn(z))` rides in the convolution's epilogue and the activation leaves
-the convolution as 16-byte slots (ops.conv3x3_split_pre_act): no pre-activation tensor, no BatchNorm pass, half the HBM bytes per
-activation element of the default eval path.  No autograd Function is involved: the plan reads the module tree's parameters and
-buffers and calls `ops` directly.
+the convolution as 16-byte slots: no pre-activation tensor, no BatchNorm pass, half the HBM bytes per activation element of the
+default eval path.  No autograd Function is involved: the plan reads the module tree's parameters and buffers and calls `ops`
+directly.
 
-Every tensor kept as slots carries two sets of magnitude slots:
+THE TABLE.  Every fused convolution launch is one row of ops.EVAL_ENTRIES, keyed by
+  slot format   "fp16x2": fp16 (hi | mid) parts, fp32-level results; "bf16": ONE part of plain bf16 -- the operands conv == "bf16"
+                trains with, one MFMA per product term instead of three and 2-byte slot elements (_Format);
+  level mode    what the maps of a level are (_Level.mode, below);
+  epilogue      "act" (a fused unit), "act_pool" (a unit in front of a max-pool as ONE launch: skip slots, L at level 0 and the 2 x 2
+                maximum from the same accumulators), "head" (the last unit of a labels-only call), "plain" (fp32 z: the last unit
+                elsewhere, and the first pass of a two-pass pooled unit).
+The plan names the mode of each level once (_build_plan) and its units look their launch up (_launch); nothing else decides a launch.
+
+LEVELS AND MODES.  Level k is the part of the U-Net on maps of H >> k x W >> k.  The plan is fused down to depth d, the deepest level
+all of whose layers the level's predicate accepts (_depth); the levels below run the existing eval kernels on fp32 tensors (the pooled
+tensor of level d - 1 is written as fp32 going down, ops.convT2x2_fwd_p writes slots coming back up).  A fused level's mode is the
+narrowest of
+  "full"     maps made of full 16 x 32 tiles: every value, every level (256 x 256 down to its 32-pixel level);
+  "ragged"   even H, W % 4 == 0, wider than 16 pixels (the *_ragged entries: the same kernels, bounds-checked loads that return zero
+             and guarded stores): the "+ragged" and "+anymap" values, every level -- the data sets' 224 x 224 down to its 28-pixel
+             level, 200 x 200 down to 100;
+  "anymap"   ANY H and W above the width floor: the "+anymap" values, levels k >= 1 -- 200 x 200 (200, 100, 50, 25, 12) down to its
+             25-pixel level.  The pooling rounds down, as nn.MaxPool2d(2) does, and a unit in front of a pool on an odd map writes
+             the floor-pooled tensor.  Level 0 keeps the ragged domain (the stem's pass and the head's float4 accesses need
+             W % 4 == 0 and even H).  One-part format only: without it H and W must be multiples of 2^k at level k;
+  "pairs"    level 4, and level 4 alone, where its map is ops.PAIRS_MIN_W .. 16 pixels wide (16 x 16, 14 x 14, 12 x 12 for inputs of
+             256, 224, 200 pixels): the "+pairs" values of either format.  One image fills at most half of a 16 x 32 tile there, so
+             the launch puts TWO images side by side per tile.  The level has no pooled unit and no head; a level k < 4 that narrow
+             stays a fall-back level (its pooled unit would need a pooled pair launch).
+and the predicate a level is asked with is the widest one its value enables there (_asked_mode), which says yes wherever the narrower
+ones do.  On a map a narrower mode takes, the launches, their order and the bits are those of the value without the wider mode: a
+256 x 256 input runs the plan of "bf16+pool" / "fp16x2+pool" down to its 32-pixel level under every value.
+  value                          format   pooled units   modes
+  True                           fp16x2   two passes     full
+  "fp16x2+pool"                  fp16x2   one launch     full
+  "fp16x2+ragged"                fp16x2   one launch     full, ragged
+  "fp16x2+ragged+pairs"          fp16x2   one launch     full, ragged, pairs
+  "bf16"                         bf16     two passes     full
+  "bf16+pool"                    bf16     one launch     full
+  "bf16+pool+ragged"             bf16     one launch     full, ragged
+  "bf16+pool+anymap"             bf16     one launch     full, ragged, anymap
+  "bf16+pool+anymap+pairs"       bf16     one launch     full, ragged, anymap, pairs
+  "bf16+pool+anymap+pairs+up"    bf16     one launch     ... and the any-map ConvTranspose2d edge (below)
+A pooled unit in two passes is a plain convolution writing the fp32 pre-activation and one BatchNorm + ReLU + pooling pass reading it
+back; as one launch it writes the same bits.
+
+What is not in the table:
+
+MAGNITUDE SLOTS (fp16x2 alone: bf16 has fp32's exponent range, so that format carries none -- scale = amax = None on every tensor, no
+bound launches).  Every tensor kept as slots carries two sets:
   scale   an upper BOUND of max |a|, known before the launch that writes the tensor (ops.conv3x3_act_bound from the weights, the
           coefficients and the input's magnitude; ops.convT2x2_out_bound): the fp16 parts are those of 2^k a with the guard k these
           slots select, and the consumers undo 2^k from the same slots;
@@ -13,86 +58,41 @@ Every tensor kept as slots carries two sets of magnitude slots:
           never exceeds one convolution (one ConvTranspose2d + one convolution behind a ConvTranspose2d).  Producers without an
           exact record (the stem's and the pooled units' BatchNorm passes) hand their bound on: at most three bounds chain
           (measured: 56-183x per convolution, up to 1.4e4x where two chain -- profiles/r07_fused_eval.md).
+A pooled unit hands on its bound as scale AND amax in one launch as in two passes, so every launch behind it sees the same magnitude
+slots and the forward is bit-identical either way.  On a ragged or pair level amax is the EXACT maximum over the map's own pixels of
+the batch's own images (those instances mask their record: relu(bn(.)) of an out-of-map accumulator is not zero and would otherwise
+loosen every later bound; an absent image of an odd batch's last pair tile is masked likewise).
+One exception, the hand-off in front of an fp16 pair level (_pooled_unit(record=True)): down3.c2 also records the exact maximum of its
+activation and hands it on with the POOLED tensor -- otherwise down4.c1's bound would chain two bounds over its 4608-term sums
+(measured: 1.45e4 - 1.70e4 x the exact maximum on small maps, above the full-tile plan's 1.4e4 x); down3.c2's skip tensor keeps the
+bound, as every other pooled unit's tensors do.
 
-Levels: level k is the part of the U-Net on maps of H / 2^k x W / 2^k.  The plan is fused down to depth d, the deepest level all of
-whose layers ops.eval_layer_ok accepts; the levels below run the existing eval kernels on fp32 tensors (the pooled tensor of level
-d - 1 is written as fp32 going down, ops.convT2x2_fwd_p writes slots coming back up).
+CONVTRANSPOSE2D EDGES.  The ConvTranspose2d of level k reads the output of level k + 1 and fills the up-sampled groups of level k's
+concat buffer; _Level.route names its launches (_build_plan.up_edge decides, _conv_t follows):
+  "slots"         the slot-operand GEMM, from the slots of a fused level below (h w % 128 == 0);
+  "slots_ragged"  its ragged entry (h w % 128 != 0, even w; two parts on fp16x2) where ops.convt_slots_ok_ragged holds;
+  "gemm"          from an fp32 tensor -- a fall-back level's output -- by the fp32-operand GEMM that writes slots;
+  "pack"          where that GEMM does not take the map: the general kernel into an fp32 tensor of the concat map's size, then one
+                  conversion pass (two parts scaled by the ConvTranspose2d's own bound on fp16x2).  On any-map levels also wherever
+                  the output must be padded (level k is odd) or the input map has odd w -- the slot GEMMs keep their dense 2h x 2w,
+                  even-w domain -- at the reference's F.pad offsets (diffY // 2, diffX // 2; the pad strip zeroed first);
+  "slots_anymap"  "+up" alone: ONE launch of the slot-operand GEMM's any-map entry on exactly those padded / odd-w edges between fused
+                  levels where ops.convt_slots_ok_anymap holds -- at 200 x 200 up1 (12 -> 24, placed in 25) and up2 (25 -> 50).  It
+                  puts the 2h x 2w block at the top-left corner of the concat map (floor pooling leaves at most one row and one
+                  column over, so the reference's F.pad offsets are 0) and writes the pad strip as zero slots itself: no memset, no
+                  general kernel, no conversion pass.
+keep_fp32: where an edge reads fp32 from a FUSED level ("pack", "gemm"), that level's last unit also writes its activation as fp32
+(_Unit.keep_fp32); under "+up" an edge between fused levels reads slots, so the pair launch of down4.c2 and the any-map launch below
+an odd level write slots alone.
+Why "+up" is a value of its own: its edge reads bf16-rounded slots where `pack` read the unrounded fp32 activation, so its results
+differ in the last bf16 digit.  An edge from a fall-back level keeps `pack`; whole-tile and ragged even-w edges keep their routes: an
+input without a padded or odd-w edge (224 x 224, 256 x 256) launches what "bf16+pool+anymap+pairs" launches, the same bits.
 
-Settings.fused_eval = "bf16" runs the same plan on ONE part of plain bf16 per slot (ops.conv3x3_plain16_pre_act; layer predicate
-ops.eval_layer_ok_bf16): the operands conv == "bf16" trains with, one MFMA per product term instead of three and 2-byte slot elements.
-bf16 has fp32's exponent range, so that plan carries no magnitude slots at all: scale = amax = None on every tensor, no bound launches.
-
-Labels-only calls (scores, segment(head="fused")): the same plan on either slot format, ending in ONE launch for the last unit and the
-head's channel product (ops.conv3x3_plain16_pre_head / conv3x3_split_pre_head: relu(bn(.)) on the accumulators, times L, summed over
-the unit's 64 channels, V the only store) followed by ops.softmax2_labels.  The last unit's fp32 pre-activation -- the largest tensor
-of the forward -- is never written, the head kernel does not run, and segment does not materialise S.  Onet.forward does not take this
-route: under every setting it launches what it launched before these calls existed.
-
-Settings.fused_eval = "fp16x2+pool" | "bf16+pool" (ops.fused_eval_pool()): the plan of True / "bf16" with each of the four units in front
-of a max-pool -- inc.c2, down1.c2, down2.c2, down3.c2: otherwise a plain convolution writing the fp32 pre-activation and one BatchNorm +
-ReLU + pooling pass reading it back -- as ONE launch (ops.conv3x3_*_pre_act_pool: skip slots, L at level 0 and the 2 x 2 maximum from the
-same accumulators).  Those units keep handing on their bound as scale AND amax, so every launch behind them sees the magnitude slots of
-the two-pass form and the whole forward is bit-identical to the plan without "+pool".
-
-Settings.fused_eval = "bf16+pool+ragged" (ops.fused_eval_ragged()): the plan of "bf16+pool" that also takes RAGGED levels -- maps not
-made of full 16 x 32 tiles, of even H and W % 4 == 0 above 16 pixels (ops.eval_layer_ok_ragged): the data sets' 224 x 224 down to its
-28-pixel level, 200 x 200 down to 100.  _build_plan marks such a level (_Level.ragged) and its units run the *_ragged entry points
-(include/onet_hip_ragged.h: the same kernels, bounds-checked loads that return zero and guarded stores); a ConvTranspose2d edge carries
-its route (_Level.route): the slot-operand GEMM or its ragged entry (h w % 128 != 0), and from a fall-back level the fp32-operand GEMM
-or, where that does not take the map, the general kernel and one conversion pass.  On a level made of full tiles the launches, their
-order and the bits are those of "bf16+pool".
-
-Settings.fused_eval = "fp16x2+ragged": the plan of "fp16x2+pool" that also takes ragged levels (ops.eval_layer_ok_ragged_fp16; the
-entry points of include/onet_hip_ragged_split.h) -- the fp32-level plan at the data sets' resolution.  Everything said about magnitude
-slots above holds on a ragged level: a fused unit's amax is the EXACT maximum over the map's own pixels (the ragged kernel instance
-masks its record: relu(bn(.)) of an out-of-map accumulator is not zero and would otherwise loosen every later bound), the pooled units
-hand on their bound, the `pack` route's conversion pass writes two parts scaled by the ConvTranspose2d's own bound.  On a level made
-of full tiles the launches, their order and the bits are those of "fp16x2+pool".
-
-Settings.fused_eval = "bf16+pool+anymap" (ops.fused_eval_anymap()): the plan of "bf16+pool+ragged" whose levels k >= 1 also take maps of
-ANY H and W above the width floor (ops.eval_layer_ok_anymap; the entry points of include/onet_hip_anymap.h), so that 200 x 200 -- levels
-of 200, 100, 50, 25 and 12 pixels -- is fused down to its 25-pixel level.  Level k is H >> k x W >> k: the pooling rounds down, as
-nn.MaxPool2d(2) does, and a unit in front of a pool on an odd map writes the floor-pooled tensor.  Level 0 keeps the ragged domain (the
-stem's pass and the head's float4 accesses need W % 4 == 0 and even H).  Such a level is marked _Level.ragged = "anymap" where its map
-lies outside the ragged domain; on every other level the launches are those of "bf16+pool+ragged".  A ConvTranspose2d edge takes the
-`pack` route -- the general kernel into an fp32 tensor of the concat map's size at the reference's F.pad offsets (diffY // 2,
-diffX // 2; the pad strip zeroed first), then one conversion pass -- where its output must be padded (level k is odd) or its input map
-has odd w: the slot-operand GEMM keeps its dense 2h x 2w, even-w domain.  The lower level's last unit then also writes fp32 (keep_fp32).
-
-Settings.fused_eval = "bf16+pool+anymap+pairs" (ops.fused_eval_pairs()): the plan of "bf16+pool+anymap" at FULL depth.  Level 4 -- down4.c1,
-down4.c2 and the ConvTranspose2d of up1 that reads them -- is 16 x 16, 14 x 14 and 12 x 12 for inputs of 256, 224 and 200 pixels: maps
-the predicates above refuse (W > 16) because one image fills at most half of a 16 x 32 tile.  Under this value level 4, and level 4
-alone, takes ops.eval_layer_ok_pairs: a map of ops.PAIRS_MIN_W <= W <= 16 runs ops.conv3x3_plain16_pre_act_pairs (include/
-onet_hip_pairs.h), TWO images side by side per tile, and is marked _Level.ragged = "pairs".  The level has no pooled unit and no head;
-its input is the pooled slots of down3.c2 (the any-map / ragged / full-tile _act_pool launch of level 3), its output goes to the
-ConvTranspose2d by the routes above (slots where h w % 128 == 0, the ragged slot GEMM for even w, `pack` with keep_fp32 elsewhere).  A
-level k < 4 whose map is 16 pixels wide or narrower stays a fall-back level (its pooled unit would need a pooled pair launch), so an
-input whose level 4 is wider than 16 pixels or narrower than the floor launches what "bf16+pool+anymap" launches: the same bits.
-
-Settings.fused_eval = "bf16+pool+anymap+pairs+up" (ops.fused_eval_upmap()): the plan of "bf16+pool+anymap+pairs" without its `pack` route
-between fused levels.  A ConvTranspose2d edge whose input map has odd w or whose output is padded into an odd concat map -- at 200 x 200
-up1 (12 -> 24, placed in 25) and up2 (25 -> 50) -- takes route "slots_anymap" where ops.convt_slots_ok_anymap holds: ONE launch of the
-slot-operand GEMM (ops.convT2x2_fwd_slots_anymap, include/onet_hip_upmap.h) that reads the slots of the level below, puts the 2h x 2w
-block at the top-left corner of the concat map (floor pooling leaves at most one row and one column over, so the reference's F.pad
-offsets are 0) and writes the pad strip as zero slots itself -- no memset, no general kernel, no conversion pass.  Its `convt` is "slots",
-so the level below keeps no fp32 copy (keep_fp32 is empty: the pair launch of down4.c2 and the any-map launch below an odd level write
-slots alone).  The edge now reads bf16-rounded slots where `pack` read the unrounded fp32 activation: its results differ in the last
-bf16 digit, which is why this is a value of its own.  An edge from a fall-back level keeps `pack`; whole-tile and ragged even-w edges
-keep their routes: an input without such an edge (224 x 224, 256 x 256) launches what "bf16+pool+anymap+pairs" launches, the same bits.
-
-Settings.fused_eval = "fp16x2+ragged+pairs" (ops.fused_eval_pairs_fp16()): the plan of "fp16x2+ragged" at FULL depth where level 4 is
-ops.PAIRS_MIN_W .. 16 pixels wide (256 x 256: 16 x 16, 224 x 224: 14 x 14).  Level 4, and level 4 alone, takes
-ops.eval_layer_ok_pairs_fp16: its two units run ops.conv3x3_split_pre_act_pairs (include/onet_hip_split_pairs.h), TWO images side by side
-per tile, and the level is marked _Level.ragged = "pairs".  The magnitude slots are a ragged level's: the launch scales by the unit's
-bound and records the EXACT maximum over the map's pixels of the batch's own images (an absent image of an odd batch's last tile is
-masked like an out-of-map pixel).  Its input is the pooled slots of down3.c2, and that one pooled unit also records the exact maximum of
-its activation and hands it on with the pooled tensor (_pooled_unit(record=True)): otherwise down4.c1's bound would chain two bounds
-over its 4608-term sums (measured: 1.45e4 - 1.70e4 x the exact maximum on small maps, above the full-tile plan's 1.4e4 x); down3.c2's
-skip tensor keeps the bound, as every other pooled unit's tensors do.  Level 4's output goes to the ConvTranspose2d of up1 by the routes
-above ("slots" where h w % 128 == 0, "slots_ragged" with two parts elsewhere -- w is even, since level 3 has W % 4 == 0 -- and
-`pack` with keep_fp32 where ops.convt_slots_ok_ragged says no).  No any-map rules come with it: H and W must still be multiples of 16
-at the input and levels 0 .. 3 keep ops.eval_layer_ok_ragged_fp16, so an input whose level 4 is wider than 16 pixels or narrower than
-the floor, and an odd-sized one (200 x 200 stays at depth 2), launch what "fp16x2+ragged" launches: the same bits.
+LABELS-ONLY CALLS (scores, segment(head="fused")): the same plan on either slot format, ending in ONE launch for the last unit and the
+head's channel product (epilogue "head": relu(bn(.)) on the accumulators, times L, summed over the unit's 64 channels, V the only
+store) followed by ops.softmax2_labels.  The last unit's fp32 pre-activation -- the largest tensor of the forward -- is never written,
+the head kernel does not run, and segment does not materialise S.  Onet.forward does not take this route: under every setting it
+launches what it launched before these calls existed.
 
 The validation step (validate, EvalCounts): the scores of a batch -- by the labels-only plan where it applies, the ordinary forward
 elsewhere -- then ONE launch (ops.score_counts) that forms the labels and adds each image's confusion counts against the ground truth
@@ -127,51 +127,35 @@ def _units(blk):
     return s[0], s[1], s[3], s[4]
 
 
-# The slot format of a plan: parts per slot, the weight pack, the layer predicate, the three launches (act_pool: the unit in front of a
-# max-pool in one launch, taken where ops.fused_eval_pool() holds), whether tensors carry magnitude slots (without them: scale = amax =
-# None everywhere, no bound launches) and whether the pooled tensors are traced
-# (ragged: the launches of a level whose maps are not made of full 16 x 32 tiles -- None: the format takes no such level)
-# (anymap: the layer predicate and the launches of a level k >= 1 whose map lies outside the ragged domain -- None: no such level)
-# (pairs: the layer predicate and the launch of level 4 on maps no wider than 16 pixels of a format WITHOUT any-map levels -- None: such
-# a level is not fused; the one-part format carries its own in `anymap`)
-_Format = namedtuple("_Format", "operands parts pack layer_ok act act_pool head magnitude trace_pool ragged anymap pairs",
-                     defaults=(None, None, None))
-_Pairs = namedtuple("_Pairs", "layer_ok act")
-_Ragged = namedtuple("_Ragged", "act act_pool head plain")
-# (pairs_ok, pairs_act: the layer predicate and the launch of level 4 on maps no wider than 16 pixels -- None: such a level is not fused)
-# (upmap: a ConvTranspose2d edge with an odd-w input map or a padded output takes the any-map slot GEMM where its predicate holds)
-_AnyMap = namedtuple("_AnyMap", "layer_ok act act_pool pairs_ok pairs_act upmap", defaults=(None, None, False))
-_ANYMAP = _AnyMap(ops.eval_layer_ok_anymap, ops.conv3x3_plain16_pre_act_anymap, ops.conv3x3_plain16_pre_act_pool_anymap)
-_ANYMAP_PAIRS = _ANYMAP._replace(pairs_ok=ops.eval_layer_ok_pairs, pairs_act=ops.conv3x3_plain16_pre_act_pairs)
-_ANYMAP_UP = _ANYMAP_PAIRS._replace(upmap=True)
-_RAGGED = _Ragged(ops.conv3x3_plain16_pre_act_ragged, ops.conv3x3_plain16_pre_act_pool_ragged, ops.conv3x3_plain16_pre_head_ragged,
-                  ops.conv3x3_plain16_pre_plain_ragged)
-_RAGGED_FP16 = _Ragged(ops.conv3x3_split_pre_act_ragged, ops.conv3x3_split_pre_act_pool_ragged, ops.conv3x3_split_pre_head_ragged,
-                       ops.conv3x3_split_pre_plain_ragged)
-_PAIRS_FP16 = _Pairs(ops.eval_layer_ok_pairs_fp16, ops.conv3x3_split_pre_act_pairs)
+# The slot format of a plan: parts per slot, the weight pack, whether tensors carry magnitude slots (without them: scale = amax = None
+# everywhere, no bound launches) and whether the pooled tensors are traced (the one-part plan's trace is complete -- every convolution's
+# exact input can be rebuilt); modes, upmap: the level modes and the ConvTranspose2d rule the setting's value enables (ops._FusedEval)
+_Format = namedtuple("_Format", "operands parts pack magnitude trace_pool modes upmap")
+_FORMATS = {"bf16": (1, "plain16", False, True), "fp16x2": (2, "split", True, False)}
+# (slot format, the widest mode a level is asked with) -> the layer predicate in `ops` (by name: read at call time, printed in reasons)
+_LAYER_OK = {("fp16x2", "full"): "eval_layer_ok", ("fp16x2", "ragged"): "eval_layer_ok_ragged_fp16", ("fp16x2", "pairs"): "eval_layer_ok_pairs_fp16",
+             ("bf16", "full"): "eval_layer_ok_bf16", ("bf16", "ragged"): "eval_layer_ok_ragged", ("bf16", "anymap"): "eval_layer_ok_anymap",
+             ("bf16", "pairs"): "eval_layer_ok_pairs"}
 
 
 def _format():
-    """The format Settings.fused_eval selects: fp16 (hi | mid) parts, or one part of plain bf16 ("bf16"); "bf16+pool+ragged" /
-    "fp16x2+ragged": with the format's ragged launches and their wider layer predicate"""
-    name = ops.fused_eval_operands()
-    rag = ops.fused_eval_ragged()
-    if name == "bf16":
-        # (trace_pool: the one-part plan's trace is complete -- every convolution's exact input can be rebuilt)
-        return _Format(name, 1, "plain16", ops.eval_layer_ok_ragged if rag else ops.eval_layer_ok_bf16, ops.conv3x3_plain16_pre_act,
-                       ops.conv3x3_plain16_pre_act_pool, ops.conv3x3_plain16_pre_head, False, True, _RAGGED if rag else None,
-                       (_ANYMAP_UP if ops.fused_eval_upmap() else _ANYMAP_PAIRS if ops.fused_eval_pairs() else _ANYMAP)
-                       if ops.fused_eval_anymap() else None)
-    return _Format(name, 2, "split", ops.eval_layer_ok_ragged_fp16 if rag else ops.eval_layer_ok, ops.conv3x3_split_pre_act,
-                   ops.conv3x3_split_pre_act_pool, ops.conv3x3_split_pre_head, True, False, _RAGGED_FP16 if rag else None,
-                   pairs=_PAIRS_FP16 if ops.fused_eval_pairs_fp16() else None)
+    """The format and modes Settings.fused_eval selects (off: the fp16 format's fields around operands = None)"""
+    v = ops._fused_eval_value()
+    return _Format(v.format, *_FORMATS[v.format or "fp16x2"], v.modes, v.upmap)
 
 
-def _pairs(fmt):
-    """-> (layer predicate, launch) of level 4 on maps no wider than 16 pixels, (None, None) where the plan does not fuse such a level"""
-    if fmt.anymap is not None:
-        return fmt.anymap.pairs_ok, fmt.anymap.pairs_act
-    return (fmt.pairs.layer_ok, fmt.pairs.act) if fmt.pairs is not None else (None, None)
+def _asked_mode(fmt, k, w):
+    """The mode whose predicate level k (maps w pixels wide) is asked with: the widest the value enables there -- level 4 takes pairs
+    where w <= 16, level 0 never takes any-map"""
+    if k == 4 and w <= 16 and "pairs" in fmt.modes:
+        return "pairs"
+    if k and "anymap" in fmt.modes:
+        return "anymap"
+    return "ragged" if "ragged" in fmt.modes else "full"
+
+
+def _layer_ok(fmt, mode):
+    return getattr(ops, _LAYER_OK[fmt.operands, mode])
 
 
 def _static_reason(unet, fmt):
@@ -211,37 +195,26 @@ def _level_layers(unet):
     return [[(name, conv) for name, conv, _ in e + d] for e, d in _level_units(unet)]
 
 
-def _depth(units, ups, layer_ok, N, H, W, anymap_ok=None, pairs_ok=None):
-    """-> (d, why level d is not fused | None): levels 0 .. d - 1 are fused.  anymap_ok: the predicate of the levels k >= 1 of a plan
-    that takes maps of any size there -- level k is then H >> k x W >> k (floor pooling) whatever the input's divisibility;
-    pairs_ok: the predicate of level 4 where that level's map is 16 pixels wide or narrower -- with anymap_ok on top of the any-map
-    rules, without it on top of the rule above (the input size a multiple of 16, levels 0 .. 3 by layer_ok)"""
-    level0_ok = layer_ok
+def _depth(units, ups, fmt, N, H, W):
+    """-> (d, why level d is not fused | None): levels 0 .. d - 1 are fused.  With any-map levels level k is H >> k x W >> k (floor
+    pooling) whatever the input's divisibility; without, the input size must be a multiple of 2^k"""
+    anymap = "anymap" in fmt.modes
     for k, (e, d) in enumerate(units):
-        if anymap_ok is None and ((H % (1 << k)) or (W % (1 << k))):
+        if not anymap and ((H % (1 << k)) or (W % (1 << k))):
             return k, f"level {k}: the input size is not a multiple of {1 << k}"
         h, w = H >> k, W >> k
-        if anymap_ok is not None:
-            if h <= 0 or w <= 0:
-                return k, f"level {k}: the map is empty"
-            layer_ok = anymap_ok if k else level0_ok
-            if pairs_ok is not None and k == 4 and w <= 16:
-                layer_ok = pairs_ok
-        elif pairs_ok is not None and k == 4 and w <= 16:
-            layer_ok = pairs_ok
+        if anymap and (h <= 0 or w <= 0):
+            return k, f"level {k}: the map is empty"
+        mode = _asked_mode(fmt, k, w)
+        layer_ok = _layer_ok(fmt, mode)
         for name, conv, _ in e + d:
             if not layer_ok(N, conv.in_channels, conv.out_channels, h, w):
-                if layer_ok is pairs_ok:
-                    return k, f"level {k}: {name} ({conv.in_channels} -> {conv.out_channels} on {N} maps of {h} x {w}) is outside ops.{pairs_ok.__name__}"
-                # (on a map made of full tiles, or no wider than 16 pixels, the ragged predicate IS eval_layer_ok_bf16, and the reason
-                # says so: the answer of "bf16+pool")
-                full = {ops.eval_layer_ok_ragged: ops.eval_layer_ok_bf16, ops.eval_layer_ok_ragged_fp16: ops.eval_layer_ok}.get(layer_ok)
-                if layer_ok is anymap_ok:
-                    full = ops.eval_layer_ok_bf16
-                ragged = full is not None and w > 16 and not ops.full_tiles(h, w)
-                ok_name = (layer_ok if ragged or full is None else full).__name__
+                # (on a map made of full tiles, or no wider than 16 pixels, the ragged and any-map predicates ARE the full-tile one, and
+                # the reason says so: the answer of the value without those modes)
+                beyond = mode in ("ragged", "anymap") and w > 16 and not ops.full_tiles(h, w)
+                ok_name = (layer_ok if beyond or mode == "pairs" else _layer_ok(fmt, "full")).__name__
                 why = f"level {k}: {name} ({conv.in_channels} -> {conv.out_channels} on {N} maps of {h} x {w}) is outside ops.{ok_name}"
-                if ragged and layer_ok is not anymap_ok and (w % 4 or h % 2):
+                if beyond and mode == "ragged" and (w % 4 or h % 2):
                     why += f": W = {w} must be a multiple of 4 and H = {h} even"
                 return k, why
         if k < 4:
@@ -266,15 +239,10 @@ def _check_head(head):
 # ConvTranspose2d that reads it as "fp32->slots"
 _Unit = namedtuple("_Unit", "name conv bn kind keep_fp32")
 # One level: its encoder and decoder units in execution order, the ConvTranspose2d that fills its concat buffer with its kind ("slots":
-# from the slots of the level below; "fp32->slots": from an fp32 tensor; level 4 has none), and whether the pooled tensor leaves as
-# slots (fp32: for the fall-back levels); ragged: the level's maps are not made of full tiles, its units take the format's ragged
-# launches ("anymap": the map also lies outside the ragged domain, its units take the format's any-map launches; "pairs": level 4 on maps
-# no wider than 16 pixels, its units take the image-pair launch); route: the launch(es)
-# behind `convt` -- "slots" / "slots_ragged" (the slot-operand GEMM, on maps with h w % 128 != 0 its ragged entry), "gemm" (the fp32-operand GEMM that writes slots) / "pack" (where that GEMM does not take the map, h w % 128 != 0: the general
-# ConvTranspose2d into an fp32 tensor, then one conversion pass into the concat buffer's up-sampled groups; also wherever the output must be
-# padded into the concat buffer or the input map has odd w -- any-map levels) / "slots_anymap" (the slot-operand GEMM's any-map entry on
-# exactly those edges, under "bf16+pool+anymap+pairs+up")
-_Level = namedtuple("_Level", "enc dec up convt pooled_slots ragged route", defaults=(False, None))
+# from the slots of the level below; "fp32->slots": from an fp32 tensor; level 4 has none), whether the pooled tensor leaves as slots
+# (fp32: for the fall-back levels), the level's mode ("full" | "ragged" | "anymap" | "pairs": the key its units look their launches up
+# with; None: a fall-back level) and the route of the launch(es) behind `convt` (module docstring)
+_Level = namedtuple("_Level", "enc dec up convt pooled_slots mode route", defaults=(None, None))
 # One U-Net pass.  reason: why the plan does not run (None: it runs); static: the part of it that holds whatever the input;
 # levels 0 .. depth - 1 are fused, fallback_reason says why level `depth` is not; head: the last unit ends in the head-epilogue launch
 _Plan = namedtuple("_Plan", "fmt batch reason static depth fallback_reason unet levels head", defaults=(None, 0, None, None, (), False))
@@ -294,27 +262,29 @@ def _build_plan(unet, shape, head=None):
     if C != unet.inc.double_conv[0].in_channels:
         return _Plan(fmt, N, _WHY_CHANNELS)
     units, ups = _level_units(unet), _blocks(unet)[2]
-    d, why_d = _depth(units, ups, fmt.layer_ok, N, H, W, fmt.anymap.layer_ok if fmt.anymap else None, _pairs(fmt)[0])
+    d, why_d = _depth(units, ups, fmt, N, H, W)
     if d == 0:
         return _Plan(fmt, N, why_d, None, 0, why_d)
     # the ConvTranspose2d of level k reads the output of level k + 1: slots where that level is fused and the slot-operand kernel takes
     # the map, else the fp32 tensor its producer -- the last unit of level k + 1, or the fall-back levels -- leaves
+    ragged = "ragged" in fmt.modes
+
     def up_edge(k, up):
         h, w, cin, ct = H >> (k + 1), W >> (k + 1), up.up.in_channels, up.up.out_channels
         if k >= d:
             return "fallback", None
-        if fmt.anymap and ((H >> k, W >> k) != (2 * h, 2 * w) or w % 2):
+        if "anymap" in fmt.modes and ((H >> k, W >> k) != (2 * h, 2 * w) or w % 2):
             # (any-map levels: the output is padded into the concat buffer -- level k is odd -- or the input map has odd w; the slot
             # GEMMs keep their dense 2h x 2w, even-w domain -- but for the any-map entry, which takes both and writes the pad strip)
-            if fmt.anymap.upmap and k + 1 < d and ops.convt_slots_ok_anymap(N, cin, ct, h, w, H >> k, W >> k):
+            if fmt.upmap and k + 1 < d and ops.convt_slots_ok_anymap(N, cin, ct, h, w, H >> k, W >> k):
                 return "slots", "slots_anymap"
             return "fp32->slots", "pack"
         if k + 1 < d and ops.convt_slots_ok(N, cin, ct, h, w, parts=fmt.parts):
             return "slots", "slots"
-        if k + 1 < d and fmt.ragged and (h * w) % 128 and ops.convt_slots_ok_ragged(N, cin, ct, h, w, parts=fmt.parts):
+        if k + 1 < d and ragged and (h * w) % 128 and ops.convt_slots_ok_ragged(N, cin, ct, h, w, parts=fmt.parts):
             return "slots", "slots_ragged"
         # (without ragged levels a fused level is made of full 16 x 32 tiles, so the map below it has h w % 128 == 0)
-        return "fp32->slots", ("pack" if fmt.ragged and (h * w) % 128 else "gemm")
+        return "fp32->slots", ("pack" if ragged and (h * w) % 128 else "gemm")
     edges = [up_edge(k, up) for k, up in enumerate(ups)]
     convt = [e[0] for e in edges]
     with_head = head == "fused" and _head_ok(unet)
@@ -331,19 +301,19 @@ def _build_plan(unet, shape, head=None):
         keep = {(dec or e)[-1][0]} if 0 < k < d and convt[k - 1] == "fp32->slots" else ()
         enc_u, dec_u = ([_Unit(name, conv, bn, kind[name], name in keep) for name, conv, bn in us] for us in (e, dec))
         levels.append(_Level(enc_u, dec_u, ups[k].up if k < 4 else None, convt[k] if k < 4 else None, k + 1 < d,
-                             _level_ragged(k < d, H >> k, W >> k, k == 4 and _pairs(fmt)[0] is not None),
+                             _level_mode(fmt, k, H >> k, W >> k) if k < d else None,
                              edges[k][1] if k < 4 else None))
     return _Plan(fmt, N, None, None, d, why_d, unet, tuple(levels), with_head)
 
 
-def _level_ragged(fused, h, w, pairs=False):
-    """_Level.ragged of a level of h x w maps: False (fall-back, or full tiles), True (the ragged launches), "anymap", "pairs" (pairs:
-    level 4 of a plan that takes it on image-pair tiles -- a fused map no wider than 16 pixels is there by that predicate alone)"""
-    if not fused or ops.full_tiles(h, w):
-        return False
-    if pairs and w <= 16:
+def _level_mode(fmt, k, h, w):
+    """_Level.mode of fused level k on h x w maps: the narrowest mode that holds the map (a fused map no wider than 16 pixels is there
+    by the pair predicate alone)"""
+    if ops.full_tiles(h, w):
+        return "full"
+    if k == 4 and w <= 16 and "pairs" in fmt.modes:
         return "pairs"
-    return True if ops._ragged_map(h, w) else "anymap"
+    return "ragged" if ops._ragged_map(h, w) else "anymap"
 
 
 def _query(unet, shape, head=None, device=None):
@@ -496,33 +466,38 @@ def _stem_unit(fmt, u, x):
     return _T(a0, None, scale0, scale0)
 
 
-def _fused_unit(fmt, u, t, ragged=False):
-    """Conv-BatchNorm-ReLU in one launch, output as slots (+ fp32 when another reader needs it); ragged: by the format's ragged launch"""
+def _launch(fmt, mode, epilogue, conv, t, *args, **kw):
+    """The launch ops.EVAL_ENTRIES holds for a unit of this format on a level of `mode`, on the slots of `t` with conv's weight pack:
+    the row's binding in `ops`, read at call time (tests and tools watch or replace a binding by its name)"""
+    name = ops.eval_conv_name(fmt.operands, mode, epilogue)
+    out = None if name is None else getattr(ops, name)(t.P, _wq(fmt, conv), conv.out_channels, *args, **kw)
+    if out is None:
+        raise RuntimeError(f"onet_amd: no {epilogue!r} launch of {fmt.operands} slots took a {mode!r} level the plan's layer predicate accepted "
+                           f"({tuple(t.P.shape)} -> {conv.out_channels} channels)")
+    return out
+
+
+def _fused_unit(fmt, u, t, mode):
+    """Conv-BatchNorm-ReLU in one launch, output as slots (+ fp32 when another reader needs it)"""
     conv = u.conv
     save = _coeffs(u.bn)
     scale = _bound(fmt, conv, save, t)
     B, _, H, _, W, _ = t.P.shape
     amax = ops.new_amax(t.P.device) if fmt.magnitude else None
     a = torch.empty((B, conv.out_channels, H, W), dtype=torch.float32, device=t.P.device) if u.keep_fp32 else None
-    # (a ragged launch takes its sibling's magnitude-slot arguments: none on the one-part format, whose ragged entries record no maximum)
-    # (a pair launch likewise: the fp16 one takes aP_slots = the bound and a_amax = a fresh record, exactly as on a ragged level)
-    launch = _pairs(fmt)[1] if ragged == "pairs" else fmt.anymap.act if ragged == "anymap" else fmt.ragged.act if ragged else fmt.act
-    aP = launch(t.P, _wq(fmt, conv), conv.out_channels, save, a=a, **_slot_kw(fmt, t, aP_slots=scale, a_amax=amax))
-    if aP is None:
-        raise RuntimeError(f"onet_amd: the fused eval kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
+    # (every mode takes the same magnitude-slot arguments: none on the one-part format, whose entries beyond "full" record no maximum;
+    # the fp16 ones take aP_slots = the bound and a_amax = a fresh record)
+    aP = _launch(fmt, mode, "act", conv, t, save, a=a, **_slot_kw(fmt, t, aP_slots=scale, a_amax=amax))
     return _T(aP, a, scale, amax)
 
 
-def _plain_conv(fmt, conv, t, ragged=False):
-    if ragged:
-        z = fmt.ragged.plain(t.P, _wq(fmt, conv), conv.out_channels, **_slot_kw(fmt, t))
-        if z is None:
-            raise RuntimeError(f"onet_amd: the ragged convolution refused a shape ops.{fmt.layer_ok.__name__} accepted")
-        return z
-    return ops.conv3x3_split_pre(t.P, _wq(fmt, conv), conv.out_channels, **_slot_kw(fmt, t))
+def _plain_conv(fmt, conv, t, mode):
+    if mode == "full":          # (the training forward's launch: not an eval entry)
+        return ops.conv3x3_split_pre(t.P, _wq(fmt, conv), conv.out_channels, **_slot_kw(fmt, t))
+    return _launch(fmt, mode, "plain", conv, t, **_slot_kw(fmt, t))
 
 
-def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots, ragged=False, record=False):
+def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots, mode, record=False):
     """An encoder block's second unit, which writes the skip slots into the concat buffer, the pooled tensor (slots, or fp32 for a
     fall-back level) and -- level 0 -- the fp32 tensor the caller receives.  "two-pass": plain convolution, then ONE BatchNorm + ReLU +
     2 x 2 max-pooling pass; "fused+pool": all of it in the convolution's launch, the same bits (no exact maximum is taken from it: the
@@ -535,19 +510,14 @@ def _pooled_unit(fmt, u, t, skipP, want_L, pooled_slots, ragged=False, record=Fa
     scale = _bound(fmt, u.conv, save, t)
     B, _, H, _, W, _ = t.P.shape
     C, dev = u.conv.out_channels, t.P.device
-    z = None if u.kind == "fused+pool" else _plain_conv(fmt, u.conv, t, ragged)
+    z = None if u.kind == "fused+pool" else _plain_conv(fmt, u.conv, t, mode)
     L = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if want_L else None
     yP = ops.p16_empty(B, C, H // 2, W // 2, dev, parts=fmt.parts) if pooled_slots else None
     yF = None if pooled_slots else torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=dev)
     amax = ops.new_amax(dev) if record and fmt.magnitude and z is None and pooled_slots else None
     out_kw = dict(aP_slots=scale) if amax is None else dict(aP_slots=scale, a_amax=amax)
-    if z is None and ragged:
-        act_pool = fmt.anymap.act_pool if ragged == "anymap" else fmt.ragged.act_pool
-        if act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, **out_kw)) is None:
-            raise RuntimeError(f"onet_amd: the ragged pooling kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
-    elif z is None:
-        if fmt.act_pool(t.P, _wq(fmt, u.conv), C, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, **out_kw)) is None:
-            raise RuntimeError(f"onet_amd: the fused pooling kernel refused a shape ops.{fmt.layer_ok.__name__} accepted")
+    if z is None:
+        _launch(fmt, mode, "act_pool", u.conv, t, save, out=skipP, a=L, yP=yP, y=yF, **_slot_kw(fmt, t, **out_kw))
     elif not ops.bn_relu_apply_pool_split(z, save, skipP, L, yP, yF, slots=scale):
         raise RuntimeError("onet_amd: the BatchNorm + pooling pass refused a shape ops.eval_layer_ok accepted")
     if yF is not None and fmt.magnitude:
@@ -610,15 +580,9 @@ def _tail(unet, k, xk):
     return ups[k](_tail(unet, k + 1, downs[k](xk)), xk)
 
 
-def _head_unit(fmt, u, t, L, ragged=False):
+def _head_unit(fmt, u, t, L, mode):
     """The last Conv-BatchNorm-ReLU unit with the head's channel product in the epilogue -> V [N, 1, H, W]"""
-    if ragged:
-        V = fmt.ragged.head(t.P, _wq(fmt, u.conv), u.conv.out_channels, _coeffs(u.bn), L, **_slot_kw(fmt, t))
-    else:
-        V = fmt.head(t.P, _wq(fmt, u.conv), u.conv.out_channels, _coeffs(u.bn), L, **_slot_kw(fmt, t))
-    if V is None:
-        raise RuntimeError("onet_amd: the fused head kernel refused a shape the plan accepted")
-    return V
+    return _launch(fmt, mode, "head", u.conv, t, _coeffs(u.bn), L, **_slot_kw(fmt, t))
 
 
 def _unet_pass(plan, x):
@@ -641,13 +605,13 @@ def _unet_pass_L(plan, x):
             if u.kind == "stem":
                 t = _note(u.name, _stem_unit(fmt, u, x))
             elif u.kind == "fused":
-                t = _note(u.name, _fused_unit(fmt, u, t, lv.ragged))
+                t = _note(u.name, _fused_unit(fmt, u, t, lv.mode))
             else:
                 C = u.conv.out_channels
                 catP[k] = ops.p16_empty(N, C + lv.up.out_channels, H >> k, W >> k, x.device, parts=fmt.parts)
                 # (fp16 pair level below: its first unit's bound starts from this unit's exact record, see _pooled_unit)
-                record = fmt.pairs is not None and k + 1 < len(fused) and fused[k + 1].ragged == "pairs"
-                skips[k], t, Lk = _pooled_unit(fmt, u, t, catP[k][:, :C // 8], k == 0, lv.pooled_slots, lv.ragged, record)
+                record = k + 1 < len(fused) and fused[k + 1].mode == "pairs"
+                skips[k], t, Lk = _pooled_unit(fmt, u, t, catP[k][:, :C // 8], k == 0, lv.pooled_slots, lv.mode, record)
                 _note(u.name, skips[k])
                 if fmt.trace_pool and lv.pooled_slots:
                     _note(_ENC[k] + ".pool", t)
@@ -667,14 +631,14 @@ def _unet_pass_L(plan, x):
         s_up = _conv_t(fmt, lv, t, catP[k], C)
         cat = _T(catP[k], None, (skips[k].scale, s_up, C), (skips[k].amax, s_up, C)) if fmt.magnitude else _T(catP[k])
         _note(_DEC[k] + ".up", _T(catP[k][:, C // 8:], None, s_up, s_up))
-        t = _note(u1.name, _fused_unit(fmt, u1, cat, lv.ragged))
+        t = _note(u1.name, _fused_unit(fmt, u1, cat, lv.mode))
         catP[k] = None
         if u2.kind == "fused":
-            t = _note(u2.name, _fused_unit(fmt, u2, t, lv.ragged))
+            t = _note(u2.name, _fused_unit(fmt, u2, t, lv.mode))
         elif u2.kind == "fused+head":
-            return L, _head_unit(fmt, u2, t, L, lv.ragged)
+            return L, _head_unit(fmt, u2, t, L, lv.mode)
         else:
-            z, save = _plain_conv(fmt, u2.conv, t, lv.ragged), _coeffs(u2.bn)
+            z, save = _plain_conv(fmt, u2.conv, t, lv.mode), _coeffs(u2.bn)
     return L, z, save
 
 

@@ -15,6 +15,7 @@ F32 = torch.float32
 
 # ----------------------------------------------------------------------------- per-model settings
 import os as _os
+from collections import namedtuple as _namedtuple
 
 
 def _flags_from_env():
@@ -186,13 +187,24 @@ def presplit():
     return split_enabled() and conv_algo() in ("auto", "split") and split_f16() and split_dgrad()
 
 
-# The string values of Settings.fused_eval -> (slot format, pooled units in one launch[, ragged levels]); True is ("fp16x2", False)
-_FUSED_EVAL_VALUES = {"bf16": ("bf16", False), "fp16x2+pool": ("fp16x2", True), "bf16+pool": ("bf16", True),
-                      "bf16+pool+ragged": ("bf16", True, True), "fp16x2+ragged": ("fp16x2", True, True),
-                      "bf16+pool+anymap": ("bf16", True, True, True), "bf16+pool+anymap+pairs": ("bf16", True, True, True, True),
-                      "bf16+pool+anymap+pairs+up": ("bf16", True, True, True, True, True),
-                      # (positions 3 .. 5 -- any map, pairs, any-map ConvTranspose2d -- are the one-part plan's; 6: the fp16 plan's pair level)
-                      "fp16x2+ragged+pairs": ("fp16x2", True, True, False, False, False, True)}
+# One value of Settings.fused_eval.  format: the slot format ("fp16x2": fp16 hi | mid parts, "bf16": one part of plain bf16, None: off);
+# pool: the pooled units run as one launch; modes: the level modes the plan takes -- "full" (maps made of full 16 x 32 tiles), "ragged"
+# (even H, W % 4 == 0), "anymap" (any H and W, levels below the first), "pairs" (level 4 on image-pair tiles where its map is 16 pixels
+# wide or narrower); upmap: ConvTranspose2d edges with an odd-w input or a padded output take the any-map slot GEMM
+_FusedEval = _namedtuple("_FusedEval", "format pool modes upmap", defaults=(False, frozenset(("full",)), False))
+
+
+def _modes(*more):
+    return frozenset(("full",) + more)
+
+
+# The string values of Settings.fused_eval; True is _FusedEval("fp16x2")
+_FUSED_EVAL_VALUES = {"bf16": _FusedEval("bf16"), "fp16x2+pool": _FusedEval("fp16x2", True), "bf16+pool": _FusedEval("bf16", True),
+                      "bf16+pool+ragged": _FusedEval("bf16", True, _modes("ragged")), "fp16x2+ragged": _FusedEval("fp16x2", True, _modes("ragged")),
+                      "bf16+pool+anymap": _FusedEval("bf16", True, _modes("ragged", "anymap")),
+                      "bf16+pool+anymap+pairs": _FusedEval("bf16", True, _modes("ragged", "anymap", "pairs")),
+                      "bf16+pool+anymap+pairs+up": _FusedEval("bf16", True, _modes("ragged", "anymap", "pairs"), True),
+                      "fp16x2+ragged+pairs": _FusedEval("fp16x2", True, _modes("ragged", "pairs"))}
 # 1: eval forwards under no_grad take the fused inference plan (Settings.fused_eval); bf16: its one-part plain-bf16 form; either with
 # "+pool" ("fp16x2+pool", "bf16+pool"): the pooled units in one launch; "bf16+pool+ragged" / "fp16x2+ragged" ("+pool" implied): ... on
 # maps not made of full tiles too; "bf16+pool+anymap": the plan of "bf16+pool+ragged" whose levels below the first take maps of any H and W;
@@ -213,44 +225,43 @@ FUSED_EVAL = _FLAGS["FUSED_EVAL"] if _FLAGS.get("FUSED_EVAL") in _FUSED_EVAL_VAL
 
 
 def _fused_eval_value():
-    """-> (slot format | None: off, pooled units in one launch) of the active Settings.fused_eval"""
+    """-> the _FusedEval record of the active Settings.fused_eval (format None: off)"""
     v = _setting("fused_eval", FUSED_EVAL)
     if isinstance(v, str):
         if v not in _FUSED_EVAL_VALUES:
             raise ValueError(f"onet_amd: Settings.fused_eval must be None, a bool or one of {sorted(_FUSED_EVAL_VALUES)}, not {v!r}")
         return _FUSED_EVAL_VALUES[v]
-    return ("fp16x2" if v else None), False
+    return _FusedEval("fp16x2" if v else None)
 
 
 def fused_eval():
-    return _fused_eval_value()[0] is not None
+    return _fused_eval_value().format is not None
 
 
 def fused_eval_operands():
     """The slot format of the fused eval plan: "fp16x2" (Settings.fused_eval = True, "fp16x2+pool" or "fp16x2+ragged": fp16 hi | mid
     parts), "bf16" (= "bf16", "bf16+pool" or "bf16+pool+ragged": one part of plain bf16), None (off)."""
-    return _fused_eval_value()[0]
+    return _fused_eval_value().format
 
 
 def fused_eval_pool():
     """Does the fused eval plan run a unit in front of a max-pool as ONE launch, the pooling in the convolution's epilogue
     (Settings.fused_eval = "fp16x2+pool" | "bf16+pool" and the two ragged values: conv3x3_*_pre_act_pool)?"""
-    return _fused_eval_value()[1]
+    return _fused_eval_value().pool
 
 
 def fused_eval_ragged():
     """Does the fused eval plan take levels whose maps are not made of full 16 x 32 tiles (Settings.fused_eval = "bf16+pool+ragged":
     the *_ragged entry points of include/onet_hip_ragged.h, layer predicate eval_layer_ok_ragged; "fp16x2+ragged": those of
     include/onet_hip_ragged_split.h, eval_layer_ok_ragged_fp16)?"""
-    return len(_fused_eval_value()) > 2
+    return "ragged" in _fused_eval_value().modes
 
 
 def fused_eval_anymap():
     """Does the fused eval plan take, at its levels below the first, maps of ANY H and W above the width floor (Settings.fused_eval =
     "bf16+pool+anymap": the entry points of include/onet_hip_anymap.h, layer predicate eval_layer_ok_anymap)?  Implies
     fused_eval_ragged(): level 0 and every map of even H and W % 4 == 0 run what "bf16+pool+ragged" runs."""
-    v = _fused_eval_value()
-    return len(v) > 3 and bool(v[3])
+    return "anymap" in _fused_eval_value().modes
 
 
 def fused_eval_pairs():
@@ -258,15 +269,14 @@ def fused_eval_pairs():
     (Settings.fused_eval = "bf16+pool+anymap+pairs": the entry point of include/onet_hip_pairs.h, layer predicate eval_layer_ok_pairs)?
     Implies fused_eval_anymap(): every other level runs what "bf16+pool+anymap" runs."""
     v = _fused_eval_value()
-    return len(v) > 4 and bool(v[4])
+    return v.format == "bf16" and "pairs" in v.modes
 
 
 def fused_eval_upmap():
     """Do the fused eval plan's ConvTranspose2d edges whose input map has odd w or whose output is padded into an odd concat map take the
     slot-operand GEMM (Settings.fused_eval = "bf16+pool+anymap+pairs+up": the entry point of include/onet_hip_upmap.h, predicate
     convt_slots_ok_anymap)?  Implies fused_eval_pairs(): every other launch is what "bf16+pool+anymap+pairs" runs."""
-    v = _fused_eval_value()
-    return len(v) > 5 and bool(v[5])
+    return _fused_eval_value().upmap
 
 
 def fused_eval_pairs_fp16():
@@ -275,7 +285,7 @@ def fused_eval_pairs_fp16():
     predicate eval_layer_ok_pairs_fp16)?  Implies fused_eval_ragged() on fp16x2 operands: every other level runs what "fp16x2+ragged"
     runs.  The one-part plan's queries (fused_eval_anymap(), fused_eval_pairs(), fused_eval_upmap()) answer False under it."""
     v = _fused_eval_value()
-    return len(v) > 6 and bool(v[6])
+    return v.format == "fp16x2" and "pairs" in v.modes
 
 
 Z_BF16 = _flag("Z_BF16", True)       # BASELINE configs[2] (conv == "bf16", pre-split operands): conv outputs stored as bf16 (Settings.z_bf16)
@@ -1364,11 +1374,40 @@ def eval_layer_ok(B, Cin, Cout, H, W):
     of onet_conv3x3_split_fwd_pre_act: fp16 (hi | mid) parts, maps made of full 16 x 32 tiles, Cin % 16 == 0, Cout % 64 == 0.  A
     function of shapes, settings and -- through conv3x3_algo's tile threshold -- the current device's compute-unit count (n_cu): no
     tensor is looked at, nothing is launched, but the fused depth of a small batch can differ between devices."""
-    if not presplit() or p16_parts() != 2:
+    return _eval_domain("fp16x2", "full", B, Cin, Cout, H, W)
+
+
+def _eval_domain(fmt, mode, B, Cin, Cout, H, W):
+    """Does a 3x3 convolution layer lie in the domain the fused eval plan gives the entry points of slot format `fmt` on a level of `mode`
+    (EVAL_ENTRIES), and does the dispatch want it there?  The eval_layer_ok* predicates are this function and their chains: each mode's
+    rule covers the maps that mode ADDS ("anymap": outside the ragged domain; "pairs": the caller has W <= 16; fp16 "ragged": the caller
+    has sent maps made of full tiles to "full").  The floors are read at call time (tests and tools reassign them)."""
+    fp16 = fmt == "fp16x2"
+    # storage, channel multiples
+    if not presplit() or (fp16 and p16_parts() != 2) or Cin % (16 if fp16 else 32) or Cout % 64:
         return False
-    if Cin % 16 or Cout % 64 or W < 32 or W % 32 or H % 16 or H * W >= 2 ** 24:
+    # the mode's maps, above its width floor
+    if mode == "full":
+        map_ok = full_tiles(H, W) and H * W < 2 ** 24
+    elif mode == "ragged":
+        map_ok = W > 16 and _ragged_map(H, W) and (W >= RAGGED_MIN_W or full_tiles(H, W))
+    elif mode == "anymap":
+        map_ok = H > 0 and W > 16 and W >= max(RAGGED_MIN_W, ANYMAP_MIN_W) and H * W < 2 ** 24 and not _ragged_map(H, W)
+    else:
+        map_ok = B > 0 and H > 0 and W >= max(PAIRS_MIN_W, 1)
+    if not map_ok:
         return False
-    return conv3x3_algo(B, Cin, Cout, H, W) == "split"
+    # fill rule.  fp16 levels of whole images: wherever today's dispatch selects the split kernel (which asks the buffer-resource range
+    # itself); elsewhere inside that range, every layer under the format's own conv settings, else tiles >= 3/4 of the compute units
+    if fp16 and mode != "pairs":
+        return conv3x3_algo(B, Cin, Cout, H, W) == "split"
+    if not _in_buffer_range(Cin, Cout, H, W):
+        return False
+    if conv_algo() in (("split",) if fp16 else ("bf16", "split")):
+        return True
+    # (cdiv: a partly filled tile occupies a compute unit like a full one; a pair tile holds two images)
+    tiles = -(-B // 2) * -(-H // 16) if mode == "pairs" else B * -(-H // 16) * -(-W // 32)
+    return tiles * (Cout // 64) >= (n_cu() * 3) // 4
 
 
 def eval_layer_ok_bf16(B, Cin, Cout, H, W):
@@ -1377,13 +1416,7 @@ def eval_layer_ok_bf16(B, Cin, Cout, H, W):
     ("bf16", "split") every such layer is taken, as those settings take every legal layer of their own kernels; otherwise conv3x3_algo's
     fill rule decides (tiles >= 3/4 of the compute units; smaller layers stay on the existing eval kernels).  A function of shapes,
     settings and n_cu()."""
-    if not presplit():
-        return False
-    if Cin % 32 or Cout % 64 or W < 32 or W % 32 or H % 16 or H * W >= 2 ** 24 or not _in_buffer_range(Cin, Cout, H, W):
-        return False
-    if conv_algo() in ("bf16", "split"):
-        return True
-    return B * (H // 16) * (W // 32) * (Cout // 64) >= (n_cu() * 3) // 4
+    return _eval_domain("bf16", "full", B, Cin, Cout, H, W)
 
 
 def full_tiles(H, W):
@@ -1411,15 +1444,7 @@ def eval_layer_ok_ragged(B, Cin, Cout, H, W):
     eval_layer_ok_bf16's.  Narrower than the entry points' domain by one rule: W >= RAGGED_MIN_W = 20, that is W > 16 -- a map 16 pixels
     wide or narrower fills at most half of every tile's columns (the existing dispatch's own special case: image pairs), is left to the
     fall-back levels, and so the plan of an input made of full tiles (256 x 256: its 16-pixel level) stays the plan of "bf16+pool"."""
-    if not presplit():
-        return False
-    if Cin % 32 or Cout % 64 or W <= 16 or not _ragged_map(H, W) or not _in_buffer_range(Cin, Cout, H, W):
-        return False
-    if W < RAGGED_MIN_W and not full_tiles(H, W):
-        return False
-    if conv_algo() in ("bf16", "split"):
-        return True
-    return B * -(-H // 16) * -(-W // 32) * (Cout // 64) >= (n_cu() * 3) // 4
+    return _eval_domain("bf16", "ragged", B, Cin, Cout, H, W)
 
 
 # The narrowest map outside eval_layer_ok_ragged's domain (odd H or W, W % 4 != 0) that eval_layer_ok_anymap takes: the floor of the ragged
@@ -1433,15 +1458,7 @@ def eval_layer_ok_anymap(B, Cin, Cout, H, W):
     are stored float by float, pooling rounds down as nn.MaxPool2d(2) does) -- above the same width floor (W > 16, W >= RAGGED_MIN_W
     and ANYMAP_MIN_W), Cin % 32 == 0, Cout % 64 == 0, inside the buffer-resource range, with pre-split storage on, under the same fill
     rule on cdiv tile counts."""
-    if eval_layer_ok_ragged(B, Cin, Cout, H, W):
-        return True
-    if not presplit() or _ragged_map(H, W):
-        return False
-    if Cin % 32 or Cout % 64 or H <= 0 or W <= 16 or W < max(RAGGED_MIN_W, ANYMAP_MIN_W) or H * W >= 2 ** 24 or not _in_buffer_range(Cin, Cout, H, W):
-        return False
-    if conv_algo() in ("bf16", "split"):
-        return True
-    return B * -(-H // 16) * -(-W // 32) * (Cout // 64) >= (n_cu() * 3) // 4
+    return eval_layer_ok_ragged(B, Cin, Cout, H, W) or _eval_domain("bf16", "anymap", B, Cin, Cout, H, W)
 
 
 # The narrowest map eval_layer_ok_pairs takes: a map of 8 or fewer columns fills at most half of each image's half of a pair tile -- the
@@ -1459,13 +1476,7 @@ def eval_layer_ok_pairs(B, Cin, Cout, H, W):
     the kernel walks, which hold two images each: cdiv(B, 2) cdiv(H, 16) Cout / 64 >= 3/4 n_cu."""
     if W > 16:
         return eval_layer_ok_anymap(B, Cin, Cout, H, W)
-    if not presplit():
-        return False
-    if Cin % 32 or Cout % 64 or B <= 0 or H <= 0 or W < max(PAIRS_MIN_W, 1) or not _in_buffer_range(Cin, Cout, H, W):
-        return False
-    if conv_algo() in ("bf16", "split"):
-        return True
-    return -(-B // 2) * -(-H // 16) * (Cout // 64) >= (n_cu() * 3) // 4
+    return _eval_domain("bf16", "pairs", B, Cin, Cout, H, W)
 
 
 def eval_layer_ok_ragged_fp16(B, Cin, Cout, H, W):
@@ -1477,11 +1488,7 @@ def eval_layer_ok_ragged_fp16(B, Cin, Cout, H, W):
     floor: a 256 x 256 input keeps the plan of "fp16x2+pool")."""
     if full_tiles(H, W):
         return eval_layer_ok(B, Cin, Cout, H, W)
-    if not presplit() or p16_parts() != 2:
-        return False
-    if Cin % 16 or Cout % 64 or W <= 16 or W < RAGGED_MIN_W or not _ragged_map(H, W):
-        return False
-    return conv3x3_algo(B, Cin, Cout, H, W) == "split"
+    return _eval_domain("fp16x2", "ragged", B, Cin, Cout, H, W)
 
 
 def eval_layer_ok_pairs_fp16(B, Cin, Cout, H, W):
@@ -1491,25 +1498,92 @@ def eval_layer_ok_pairs_fp16(B, Cin, Cout, H, W):
     tiles the kernel walks, which hold two images each: cdiv(B, 2) cdiv(H, 16) Cout / 64 >= 3/4 n_cu."""
     if W > 16:
         return eval_layer_ok_ragged_fp16(B, Cin, Cout, H, W)
-    if not presplit() or p16_parts() != 2:
-        return False
-    if Cin % 16 or Cout % 64 or B <= 0 or H <= 0 or W < max(PAIRS_MIN_W, 1) or not _in_buffer_range(Cin, Cout, H, W):
-        return False
-    if conv_algo() == "split":
-        return True
-    return -(-B // 2) * -(-H // 16) * (Cout // 64) >= (n_cu() * 3) // 4
+    return _eval_domain("fp16x2", "pairs", B, Cin, Cout, H, W)
 
 
-def _pre_act(entry, kind, two, cin_mult, xs, wq, Cout, save, out, a_amax, a, extra_in, extra_out, pooled=None, ragged=False):
+def conv3x3_act_bound(weight, save, x_amax, x_amax2=None, split_ch=0):
+    """Magnitude slots bounding relu(bn_eval(conv3x3(x))) from the layer's weights, the coefficients `save` [4, Cout] and the magnitude
+    slots of x (two producers of a concat buffer: x_amax2 for the channels from split_ch): the scale slots of the fused eval kernel."""
+    w = weight.detach()
+    w = w if w.is_contiguous() else w.contiguous()
+    slots = new_amax(w.device)
+    _lib.call("onet_conv3x3_act_bound", _p(w), w.shape[0], w.shape[1], _p(save), _p(x_amax), _p(x_amax2), int(split_ch if x_amax2 is not None else 0),
+              _p(slots), _stream())
+    return slots
+
+
+# The fused eval convolutions (onet_amd/inference.py): (slot format, level mode, epilogue) -> (C entry, profile kind).  Slot format:
+# "fp16x2" (fp16 hi | mid parts, include/onet_hip_eval.h) | "bf16" (one part of plain bf16); level mode: "full" (maps made of full 16 x 32
+# tiles) | "ragged" (even H, W % 4 == 0: onet_hip_ragged.h, onet_hip_ragged_split.h) | "anymap" (any H and W: onet_hip_anymap.h) | "pairs"
+# (image-pair tiles, 0 < W <= 16: onet_hip_pairs.h, onet_hip_split_pairs.h); epilogue: "act" (BatchNorm + ReLU, slots out) | "act_pool" (...
+# and the 2 x 2 max-pooling) | "head" (... times L, summed over the 64 channels: V alone) | "plain" (fp32 z).  A combination that is not
+# a row does not exist: eval_conv raises KeyError, the plan (inference._launch) says which level asked for it.  Every row has a binding by
+# name below (eval_conv_name): conv3x3_{plain16,split}_pre_<epilogue>[_<mode>].
+EVAL_ENTRIES = {
+    ("fp16x2", "full", "act"): ("onet_conv3x3_split_fwd_pre_act", "conv3x3_split_pre_act_kernel"),
+    ("fp16x2", "full", "act_pool"): ("onet_conv3x3_split_fwd_pre_act_pool", "conv3x3_split_pre_act_pool_kernel"),
+    ("fp16x2", "full", "head"): ("onet_conv3x3_split_fwd_pre_head", "conv3x3_split_pre_head_kernel"),
+    ("fp16x2", "ragged", "act"): ("onet_conv3x3_split_fwd_pre_act_ragged", "conv3x3_split_pre_act_kernel"),
+    ("fp16x2", "ragged", "act_pool"): ("onet_conv3x3_split_fwd_pre_act_pool_ragged", "conv3x3_split_pre_act_pool_kernel"),
+    ("fp16x2", "ragged", "head"): ("onet_conv3x3_split_fwd_pre_head_ragged", "conv3x3_split_pre_head_kernel"),
+    ("fp16x2", "ragged", "plain"): ("onet_conv3x3_split_fwd_pre_plain_ragged", "conv3x3_split_pre_kernel"),
+    ("fp16x2", "pairs", "act"): ("onet_conv3x3_split_fwd_pre_act_pairs", "conv3x3_split_pre_act_pairs_kernel"),
+    ("bf16", "full", "act"): ("onet_conv3x3_plain16_fwd_pre_act", "conv3x3_pre16_act_kernel"),
+    ("bf16", "full", "act_pool"): ("onet_conv3x3_plain16_fwd_pre_act_pool", "conv3x3_pre16_act_pool_kernel"),
+    ("bf16", "full", "head"): ("onet_conv3x3_plain16_fwd_pre_head", "conv3x3_pre16_head_kernel"),
+    ("bf16", "ragged", "act"): ("onet_conv3x3_plain16_fwd_pre_act_ragged", "conv3x3_pre16_act_kernel"),
+    ("bf16", "ragged", "act_pool"): ("onet_conv3x3_plain16_fwd_pre_act_pool_ragged", "conv3x3_pre16_act_pool_kernel"),
+    ("bf16", "ragged", "head"): ("onet_conv3x3_plain16_fwd_pre_head_ragged", "conv3x3_pre16_head_kernel"),
+    ("bf16", "ragged", "plain"): ("onet_conv3x3_plain16_fwd_pre_plain_ragged", "conv3x3_split_pre_kernel"),
+    ("bf16", "anymap", "act"): ("onet_conv3x3_plain16_fwd_pre_act_anymap", "conv3x3_pre16_act_kernel"),
+    ("bf16", "anymap", "act_pool"): ("onet_conv3x3_plain16_fwd_pre_act_pool_anymap", "conv3x3_pre16_act_pool_kernel"),
+    ("bf16", "pairs", "act"): ("onet_conv3x3_plain16_fwd_pre_act_pairs", "conv3x3_pre16_act_pairs_kernel"),
+}
+
+
+_EVAL_NAMES = {key: entry[len("onet_"):].replace("_fwd_pre_", "_pre_") for key, (entry, _) in EVAL_ENTRIES.items()}
+
+
+def eval_conv_name(fmt, mode, epilogue):
+    """The name in this module of the binding of EVAL_ENTRIES[fmt, mode, epilogue] (the C entry's, without onet_ and _fwd) -- None: no row"""
+    return _EVAL_NAMES.get((fmt, mode, epilogue))
+
+
+def eval_conv(fmt, mode, epilogue, xs, wq, Cout, save=None, L=None, aP_slots=None, out=None, slots=None, slots2=None, split_ch=0,
+              a_amax=None, a=None, yP=None, y=None):
+    """The launch of EVAL_ENTRIES[fmt, mode, epilogue] on the slots xs with the weight pack wq: what the conv3x3_{plain16,split}_pre_*
+    functions below are bindings of, where each argument is described.  save: every epilogue but "plain"; L: "head"; aP_slots, slots,
+    slots2, split_ch: the magnitude slots of "fp16x2"; a_amax, a: "act" / "act_pool" (a_amax: not on the one-part ragged, any-map and pair
+    entries); yP, y: "act_pool".  -> the output (slots, V or z), or None where the entry does not take the shape (nothing launched)."""
+    entry, kind = EVAL_ENTRIES[fmt, mode, epilogue]
+    two = fmt == "fp16x2"
+    dt = torch.float16 if two else BF
+    if wq is None or not wq.is_cuda or wq.dtype != dt or xs.dtype != dt or xs.shape[3] != 1 + two:
+        raise TypeError(f"{eval_conv_name(fmt, mode, epilogue)}: xs and wq must be " + ("fp16 (hi | mid) split" if two else "one-part bf16") + " packs on the GPU")
+    if PAIRS_SINGLE and (fmt, mode) == ("bf16", "pairs"):
+        mode = "anymap"
+        entry, kind = EVAL_ENTRIES[fmt, mode, epilogue]
+    # (fp16: the magnitude slots the producers scaled xs by -- one set, or two with the first channel of the second)
+    x_slots = (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)) if two else ()
+    if epilogue == "head":
+        return _pre_head(entry, kind, 1 + two, xs, wq, Cout, save, L, out, x_slots)
+    if epilogue == "plain":
+        return _pre_plain(entry, kind, 1 + two, xs, wq, Cout, out, x_slots)
+    return _pre_act(entry, kind, 1 + two, mode, xs, wq, Cout, save, out, a_amax, a, x_slots, (_p(aP_slots),) if two else (),
+                    pooled=(yP, y) if epilogue == "act_pool" else None)
+
+
+def _pre_act(entry, kind, two, mode, xs, wq, Cout, save, out, a_amax, a, extra_in, extra_out, pooled=None):
     """pooled: (yP, y) of the _pool entries -- the pooled slots and / or the pooled fp32 tensor, at least one"""
     B, C8, H, _, W, _ = xs.shape
     Cin = C8 * 8
     if pooled is not None and pooled[0] is None and pooled[1] is None:
         raise ValueError(f"{entry[len('onet_'):]}: a pooled destination is required (yP, y or both)")
-    # (ragged = "anymap": the entries of include/onet_hip_anymap.h -- every map below 2^24 pixels)
-    # (ragged = "pairs": the entry of include/onet_hip_pairs.h -- any H on 0 < W <= 16)
-    map_ok = (0 < H * W < 2 ** 24 and (ragged == "anymap" or W <= 16)) if ragged in ("anymap", "pairs") else _ragged_map(H, W) if ragged else full_tiles(H, W)
-    if not map_ok or Cin % cin_mult or Cout % 64:
+    if mode in ("anymap", "pairs"):         # every map below 2^24 pixels; pairs: any H on 0 < W <= 16
+        map_ok = 0 < H * W < 2 ** 24 and (mode == "anymap" or W <= 16)
+    else:
+        map_ok = _ragged_map(H, W) if mode == "ragged" else full_tiles(H, W)
+    if not map_ok or Cin % (16 if two == 2 else 32) or Cout % 64:
         return None
     if out is None:
         out = p16_empty(B, Cout, H, W, xs.device, parts=two)
@@ -1527,193 +1601,6 @@ def _pre_act(entry, kind, two, cin_mult, xs, wq, Cout, save, out, a_amax, a, ext
     if rc < 0:
         raise _lib.OnetHipError(f"{entry} failed ({rc}): {_lib.last_error()}")
     return out if rc == 0 else None
-
-
-def conv3x3_plain16_pre_act(xs, wq, Cout, save, out=None, a_amax=None, a=None):
-    """aP = relu(bn(conv3x3(xs))) on PLAIN bf16 operands (xs [B, Cin/8, H, 1, W, 8] bf16, wq the plain16 forward pack), written as one
-    part of bf16 slots, BatchNorm with the fixed coefficients `save` [4, Cout] (bn_eval_coeffs) in the convolution's epilogue:
-    conv3x3_split_pre (fp32 z) followed by bn_relu_apply_split, bit for bit, without the tensor z.  Unscaled: no magnitude slots.
-    a_amax: slots that receive the exact max a; a: optional fp32 destination.  -> aP, or None where the kernel does not take the shape
-    (nothing launched)."""
-    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
-        raise TypeError("conv3x3_plain16_pre_act: xs and wq must be one-part bf16 packs on the GPU")
-    return _pre_act("onet_conv3x3_plain16_fwd_pre_act", "conv3x3_pre16_act_kernel", 1, 32, xs, wq, Cout, save, out, a_amax, a, (), ())
-
-
-def conv3x3_plain16_pre_act_ragged(xs, wq, Cout, save, out=None, a=None):
-    """conv3x3_plain16_pre_act on a ragged map (even H, W % 4 == 0; onet_conv3x3_plain16_fwd_pre_act_ragged): on the map, value for value,
-    what conv3x3_plain16_pre_act writes on the map zero-padded to whole 16 x 32 tiles; nothing outside the map is written.  No exact
-    maximum is recorded.  -> aP, or None where the kernel does not take the shape (nothing launched)."""
-    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
-        raise TypeError("conv3x3_plain16_pre_act_ragged: xs and wq must be one-part bf16 packs on the GPU")
-    return _pre_act("onet_conv3x3_plain16_fwd_pre_act_ragged", "conv3x3_pre16_act_kernel", 1, 32, xs, wq, Cout, save, out, None, a, (), (), ragged=True)
-
-
-def conv3x3_plain16_pre_act_pool_ragged(xs, wq, Cout, save, out=None, a=None, yP=None, y=None):
-    """conv3x3_plain16_pre_act_pool on a ragged map (conv3x3_plain16_pre_act_ragged's domain): the pooled maps are H / 2 x W / 2.
-    -> aP, or None (nothing launched)."""
-    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
-        raise TypeError("conv3x3_plain16_pre_act_pool_ragged: xs and wq must be one-part bf16 packs on the GPU")
-    return _pre_act("onet_conv3x3_plain16_fwd_pre_act_pool_ragged", "conv3x3_pre16_act_pool_kernel", 1, 32, xs, wq, Cout, save, out, None, a, (), (),
-                    pooled=(yP, y), ragged=True)
-
-
-def conv3x3_plain16_pre_act_anymap(xs, wq, Cout, save, out=None, a=None):
-    """conv3x3_plain16_pre_act_ragged on a map of ANY H and W (onet_conv3x3_plain16_fwd_pre_act_anymap): on the map, value for value, what
-    conv3x3_plain16_pre_act writes on the map zero-padded to whole 16 x 32 tiles; nothing outside the map is written, and `a` needs no
-    row alignment.  On a map the ragged entry takes: that entry's launch.  -> aP, or None (nothing launched)."""
-    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
-        raise TypeError("conv3x3_plain16_pre_act_anymap: xs and wq must be one-part bf16 packs on the GPU")
-    return _pre_act("onet_conv3x3_plain16_fwd_pre_act_anymap", "conv3x3_pre16_act_kernel", 1, 32, xs, wq, Cout, save, out, None, a, (), (), ragged="anymap")
-
-
-def conv3x3_plain16_pre_act_pairs(xs, wq, Cout, save, out=None, a=None):
-    """conv3x3_plain16_pre_act_anymap on maps of 0 < W <= 16 and any H, on IMAGE-PAIR tiles (onet_conv3x3_plain16_fwd_pre_act_pairs): two
-    images of the batch side by side in a tile's 32 columns; the same values.  Any batch size (an odd one: the last tile holds one
-    image).  -> aP, or None where the kernel does not take the shape (nothing launched)."""
-    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
-        raise TypeError("conv3x3_plain16_pre_act_pairs: xs and wq must be one-part bf16 packs on the GPU")
-    if PAIRS_SINGLE:
-        return conv3x3_plain16_pre_act_anymap(xs, wq, Cout, save, out=out, a=a)
-    return _pre_act("onet_conv3x3_plain16_fwd_pre_act_pairs", "conv3x3_pre16_act_pairs_kernel", 1, 32, xs, wq, Cout, save, out, None, a, (), (), ragged="pairs")
-
-
-def conv3x3_plain16_pre_act_pool_anymap(xs, wq, Cout, save, out=None, a=None, yP=None, y=None):
-    """conv3x3_plain16_pre_act_pool_ragged on a map of ANY H and W (onet_conv3x3_plain16_fwd_pre_act_pool_anymap): the pooled maps are
-    H // 2 x W // 2 -- floor pooling, nn.MaxPool2d(2)'s; a window partly outside an odd map is pooled nowhere.  -> aP, or None."""
-    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
-        raise TypeError("conv3x3_plain16_pre_act_pool_anymap: xs and wq must be one-part bf16 packs on the GPU")
-    return _pre_act("onet_conv3x3_plain16_fwd_pre_act_pool_anymap", "conv3x3_pre16_act_pool_kernel", 1, 32, xs, wq, Cout, save, out, None, a, (), (),
-                    pooled=(yP, y), ragged="anymap")
-
-
-def conv3x3_plain16_pre_plain_ragged(xs, wq, Cout, out=None):
-    """z = conv3x3 (fp32) of one-part bf16 slots on a ragged map (conv3x3_plain16_pre_act_ragged's domain): conv3x3_split_pre's launch
-    there.  -> z, or None (nothing launched)."""
-    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
-        raise TypeError("conv3x3_plain16_pre_plain_ragged: xs and wq must be one-part bf16 packs on the GPU")
-    B, C8, H, _, W, _ = xs.shape
-    Cin = C8 * 8
-    if not _ragged_map(H, W) or Cin % 32 or Cout % 64:
-        return None
-    if out is None:
-        out = torch.empty((B, Cout, H, W), dtype=F32, device=xs.device)
-    e0 = _prof_begin("conv3x3_split_pre_kernel")
-    rc = _lib.load().onet_conv3x3_plain16_fwd_pre_plain_ragged(_p(xs), _pbs(xs), _p(wq), _p(out), out.stride(0) if B > 1 else Cout * H * W, B, Cin,
-                                                               Cout, H, W, _stream())
-    _prof_end("conv3x3_split_pre_kernel", 2.0 * B * H * W * Cin * Cout * 9 if rc == 0 else 0.0, e0,
-              (B * H * W * (2.0 * Cin + 4.0 * Cout) + 2.0 * 9 * Cin * Cout) if rc == 0 else 0.0)
-    if rc < 0:
-        raise _lib.OnetHipError(f"onet_conv3x3_plain16_fwd_pre_plain_ragged failed ({rc}): {_lib.last_error()}")
-    return out if rc == 0 else None
-
-
-def conv3x3_plain16_pre_act_pool(xs, wq, Cout, save, out=None, a_amax=None, a=None, yP=None, y=None):
-    """conv3x3_plain16_pre_act with the 2 x 2 max-pooling of the activation in the same epilogue: besides aP (`out`: the skip groups of a
-    concat buffer qualify), `a` and `a_amax` the launch writes the pooled tensor as one-part bf16 slots (yP [B, Cout/8, H/2, 1, W/2, 8]),
-    as fp32 (y [B, Cout, H/2, W/2]) or both -- at least one.  conv3x3_split_pre (fp32 z) followed by bn_relu_apply_pool_split, bit for
-    bit, without the tensor z.  -> aP, or None where the kernel does not take the shape (nothing launched)."""
-    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
-        raise TypeError("conv3x3_plain16_pre_act_pool: xs and wq must be one-part bf16 packs on the GPU")
-    return _pre_act("onet_conv3x3_plain16_fwd_pre_act_pool", "conv3x3_pre16_act_pool_kernel", 1, 32, xs, wq, Cout, save, out, a_amax, a, (), (),
-                    pooled=(yP, y))
-
-
-def conv3x3_split_pre_act_pool(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None, yP=None,
-                               y=None):
-    """conv3x3_split_pre_act with the 2 x 2 max-pooling of the activation in the same epilogue (conv3x3_plain16_pre_act_pool on fp16
-    hi | mid parts): the pooled slots yP [B, Cout/8, H/2, 2, W/2, 8] are parts of 2^k m with the k of aP (aP_slots).  conv3x3_split_pre
-    followed by bn_relu_apply_pool_split(.., slots=aP_slots), bit for bit.  -> aP, or None (nothing launched)."""
-    if wq is None or not wq.is_cuda or wq.dtype != torch.float16 or xs.dtype != torch.float16 or xs.shape[3] != 2:
-        raise TypeError("conv3x3_split_pre_act_pool: xs and wq must be fp16 (hi | mid) split packs on the GPU")
-    return _pre_act("onet_conv3x3_split_fwd_pre_act_pool", "conv3x3_split_pre_act_pool_kernel", 2, 16, xs, wq, Cout, save, out, a_amax, a,
-                    (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)), (_p(aP_slots),),
-                    pooled=(yP, y))
-
-
-def _fp16_packs(name, xs, wq):
-    if wq is None or not wq.is_cuda or wq.dtype != torch.float16 or xs.dtype != torch.float16 or xs.shape[3] != 2:
-        raise TypeError(f"{name}: xs and wq must be fp16 (hi | mid) split packs on the GPU")
-
-
-def conv3x3_split_pre_act_pool_ragged(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None,
-                                      yP=None, y=None):
-    """conv3x3_split_pre_act_pool on a ragged map (even H, W % 4 == 0; onet_conv3x3_split_fwd_pre_act_pool_ragged): the pooled maps are
-    H / 2 x W / 2; a_amax receives the maximum over the map's own pixels.  -> aP, or None (nothing launched)."""
-    _fp16_packs("conv3x3_split_pre_act_pool_ragged", xs, wq)
-    return _pre_act("onet_conv3x3_split_fwd_pre_act_pool_ragged", "conv3x3_split_pre_act_pool_kernel", 2, 16, xs, wq, Cout, save, out, a_amax, a,
-                    (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)), (_p(aP_slots),),
-                    pooled=(yP, y), ragged=True)
-
-
-def conv3x3_split_pre_act_ragged(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None):
-    """conv3x3_split_pre_act on a ragged map (even H, W % 4 == 0; onet_conv3x3_split_fwd_pre_act_ragged): on the map, value for value,
-    what conv3x3_split_pre_act writes on the map zero-padded to whole 16 x 32 tiles; nothing outside the map is written.  a_amax: the
-    exact maximum over the MAP's pixels (bit-equal to a.max() of the same launch).  -> aP, or None (nothing launched)."""
-    _fp16_packs("conv3x3_split_pre_act_ragged", xs, wq)
-    return _pre_act("onet_conv3x3_split_fwd_pre_act_ragged", "conv3x3_split_pre_act_kernel", 2, 16, xs, wq, Cout, save, out, a_amax, a,
-                    (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)), (_p(aP_slots),), ragged=True)
-
-
-def conv3x3_split_pre_act_pairs(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None):
-    """conv3x3_split_pre_act_ragged on maps of 0 < W <= 16 and any H, on IMAGE-PAIR tiles (onet_conv3x3_split_fwd_pre_act_pairs): two
-    images of the batch side by side in a tile's 32 columns; the same values, a_amax the exact maximum over the map's pixels of the
-    batch's own images.  Any batch size (an odd one: the last tile holds one image).  -> aP, or None where the kernel does not take
-    the shape (nothing launched)."""
-    _fp16_packs("conv3x3_split_pre_act_pairs", xs, wq)
-    return _pre_act("onet_conv3x3_split_fwd_pre_act_pairs", "conv3x3_split_pre_act_pairs_kernel", 2, 16, xs, wq, Cout, save, out, a_amax, a,
-                    (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)), (_p(aP_slots),), ragged="pairs")
-
-
-def conv3x3_split_pre_head_ragged(xs, wq, Cout, save, L, out=None, slots=None, slots2=None, split_ch=0):
-    """conv3x3_split_pre_head on a ragged map (conv3x3_split_pre_act_ragged's domain, Cout == 64).  -> V, or None (nothing launched,
-    nothing written)."""
-    _fp16_packs("conv3x3_split_pre_head_ragged", xs, wq)
-    return _pre_head("onet_conv3x3_split_fwd_pre_head_ragged", "conv3x3_split_pre_head_kernel", 2, xs, wq, Cout, save, L, out,
-                     (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)))
-
-
-def conv3x3_split_pre_plain_ragged(xs, wq, Cout, out=None, slots=None, slots2=None, split_ch=0):
-    """z = conv3x3 (fp32) of fp16 (hi | mid) slots on a ragged map (conv3x3_split_pre_act_ragged's domain): conv3x3_split_pre's launch
-    there (slots / slots2 / split_ch: the magnitude slots the producers scaled xs by).  -> z, or None (nothing launched)."""
-    _fp16_packs("conv3x3_split_pre_plain_ragged", xs, wq)
-    B, C8, H, _, W, _ = xs.shape
-    Cin = C8 * 8
-    if not _ragged_map(H, W) or Cin % 16 or Cout % 64:
-        return None
-    if out is None:
-        out = torch.empty((B, Cout, H, W), dtype=F32, device=xs.device)
-    e0 = _prof_begin("conv3x3_split_pre_kernel")
-    rc = _lib.load().onet_conv3x3_split_fwd_pre_plain_ragged(_p(xs), _pbs(xs), _p(slots), 0, _p(slots2),
-                                                             int(split_ch if slots2 is not None or slots is not None else 0), _p(wq), _p(out),
-                                                             out.stride(0) if B > 1 else Cout * H * W, B, Cin, Cout, H, W, _stream())
-    _prof_end("conv3x3_split_pre_kernel", 2.0 * B * H * W * Cin * Cout * 9 if rc == 0 else 0.0, e0,
-              (B * H * W * (4.0 * Cin + 4.0 * Cout) + 4.0 * 9 * Cin * Cout) if rc == 0 else 0.0)
-    if rc < 0:
-        raise _lib.OnetHipError(f"onet_conv3x3_split_fwd_pre_plain_ragged failed ({rc}): {_lib.last_error()}")
-    return out if rc == 0 else None
-
-
-def conv3x3_act_bound(weight, save, x_amax, x_amax2=None, split_ch=0):
-    """Magnitude slots bounding relu(bn_eval(conv3x3(x))) from the layer's weights, the coefficients `save` [4, Cout] and the magnitude
-    slots of x (two producers of a concat buffer: x_amax2 for the channels from split_ch): the scale slots of the fused eval kernel."""
-    w = weight.detach()
-    w = w if w.is_contiguous() else w.contiguous()
-    slots = new_amax(w.device)
-    _lib.call("onet_conv3x3_act_bound", _p(w), w.shape[0], w.shape[1], _p(save), _p(x_amax), _p(x_amax2), int(split_ch if x_amax2 is not None else 0),
-              _p(slots), _stream())
-    return slots
-
-
-def conv3x3_split_pre_act(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None):
-    """aP = relu(bn(conv3x3(xs))) written PRE-SPLIT, BatchNorm with the fixed coefficients `save` [4, Cout] (bn_eval_coeffs) in the
-    convolution's epilogue: conv3x3_split_pre followed by bn_relu_apply_split(.., slots=aP_slots), bit for bit, without the tensor z.
-    aP_slots: the bound the parts are scaled by (conv3x3_act_bound, before this launch); a_amax: slots that receive the exact max a;
-    a: optional fp32 destination.  -> aP, or None where the kernel does not take the shape (nothing launched)."""
-    if wq is None or not wq.is_cuda or wq.dtype != torch.float16 or xs.dtype != torch.float16 or xs.shape[3] != 2:
-        raise TypeError("conv3x3_split_pre_act: xs and wq must be fp16 (hi | mid) split packs on the GPU")
-    return _pre_act("onet_conv3x3_split_fwd_pre_act", "conv3x3_split_pre_act_kernel", 2, 16, xs, wq, Cout, save, out, a_amax, a,
-                    (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)), (_p(aP_slots),))
 
 
 def _pre_head(entry, kind, two, xs, wq, Cout, save, L, out, extra):
@@ -1736,6 +1623,80 @@ def _pre_head(entry, kind, two, xs, wq, Cout, save, L, out, extra):
     return out if rc == 0 else None
 
 
+def _pre_plain(entry, kind, two, xs, wq, Cout, out, extra):
+    B, C8, H, _, W, _ = xs.shape
+    Cin = C8 * 8
+    if not _ragged_map(H, W) or Cin % (16 if two == 2 else 32) or Cout % 64:
+        return None
+    if out is None:
+        out = torch.empty((B, Cout, H, W), dtype=F32, device=xs.device)
+    e0 = _prof_begin(kind)
+    rc = getattr(_lib.load(), entry)(_p(xs), _pbs(xs), *extra, _p(wq), _p(out), out.stride(0) if B > 1 else Cout * H * W, B, Cin, Cout, H, W,
+                                     _stream())
+    _prof_end(kind, 2.0 * B * H * W * Cin * Cout * 9 if rc == 0 else 0.0, e0,
+              (B * H * W * (2.0 * two * Cin + 4.0 * Cout) + 2.0 * two * 9 * Cin * Cout) if rc == 0 else 0.0)
+    if rc < 0:
+        raise _lib.OnetHipError(f"{entry} failed ({rc}): {_lib.last_error()}")
+    return out if rc == 0 else None
+
+
+# ---- the table's rows by name: one-part bf16 operands
+def conv3x3_plain16_pre_act(xs, wq, Cout, save, out=None, a_amax=None, a=None):
+    """aP = relu(bn(conv3x3(xs))) on PLAIN bf16 operands (xs [B, Cin/8, H, 1, W, 8] bf16, wq the plain16 forward pack), written as one
+    part of bf16 slots, BatchNorm with the fixed coefficients `save` [4, Cout] (bn_eval_coeffs) in the convolution's epilogue:
+    conv3x3_split_pre (fp32 z) followed by bn_relu_apply_split, bit for bit, without the tensor z.  Unscaled: no magnitude slots.
+    a_amax: slots that receive the exact max a; a: optional fp32 destination.  -> aP, or None where the kernel does not take the shape
+    (nothing launched)."""
+    return eval_conv("bf16", "full", "act", xs, wq, Cout, save, out=out, a_amax=a_amax, a=a)
+
+
+def conv3x3_plain16_pre_act_ragged(xs, wq, Cout, save, out=None, a=None):
+    """conv3x3_plain16_pre_act on a ragged map (even H, W % 4 == 0; onet_conv3x3_plain16_fwd_pre_act_ragged): on the map, value for value,
+    what conv3x3_plain16_pre_act writes on the map zero-padded to whole 16 x 32 tiles; nothing outside the map is written.  No exact
+    maximum is recorded.  -> aP, or None where the kernel does not take the shape (nothing launched)."""
+    return eval_conv("bf16", "ragged", "act", xs, wq, Cout, save, out=out, a=a)
+
+
+def conv3x3_plain16_pre_act_pool_ragged(xs, wq, Cout, save, out=None, a=None, yP=None, y=None):
+    """conv3x3_plain16_pre_act_pool on a ragged map (conv3x3_plain16_pre_act_ragged's domain): the pooled maps are H / 2 x W / 2.
+    -> aP, or None (nothing launched)."""
+    return eval_conv("bf16", "ragged", "act_pool", xs, wq, Cout, save, out=out, a=a, yP=yP, y=y)
+
+
+def conv3x3_plain16_pre_act_anymap(xs, wq, Cout, save, out=None, a=None):
+    """conv3x3_plain16_pre_act_ragged on a map of ANY H and W (onet_conv3x3_plain16_fwd_pre_act_anymap): on the map, value for value, what
+    conv3x3_plain16_pre_act writes on the map zero-padded to whole 16 x 32 tiles; nothing outside the map is written, and `a` needs no
+    row alignment.  On a map the ragged entry takes: that entry's launch.  -> aP, or None (nothing launched)."""
+    return eval_conv("bf16", "anymap", "act", xs, wq, Cout, save, out=out, a=a)
+
+
+def conv3x3_plain16_pre_act_pairs(xs, wq, Cout, save, out=None, a=None):
+    """conv3x3_plain16_pre_act_anymap on maps of 0 < W <= 16 and any H, on IMAGE-PAIR tiles (onet_conv3x3_plain16_fwd_pre_act_pairs): two
+    images of the batch side by side in a tile's 32 columns; the same values.  Any batch size (an odd one: the last tile holds one
+    image).  -> aP, or None where the kernel does not take the shape (nothing launched).  (PAIRS_SINGLE: the any-map entry's launch.)"""
+    return eval_conv("bf16", "pairs", "act", xs, wq, Cout, save, out=out, a=a)
+
+
+def conv3x3_plain16_pre_act_pool_anymap(xs, wq, Cout, save, out=None, a=None, yP=None, y=None):
+    """conv3x3_plain16_pre_act_pool_ragged on a map of ANY H and W (onet_conv3x3_plain16_fwd_pre_act_pool_anymap): the pooled maps are
+    H // 2 x W // 2 -- floor pooling, nn.MaxPool2d(2)'s; a window partly outside an odd map is pooled nowhere.  -> aP, or None."""
+    return eval_conv("bf16", "anymap", "act_pool", xs, wq, Cout, save, out=out, a=a, yP=yP, y=y)
+
+
+def conv3x3_plain16_pre_plain_ragged(xs, wq, Cout, out=None):
+    """z = conv3x3 (fp32) of one-part bf16 slots on a ragged map (conv3x3_plain16_pre_act_ragged's domain): conv3x3_split_pre's launch
+    there.  -> z, or None (nothing launched)."""
+    return eval_conv("bf16", "ragged", "plain", xs, wq, Cout, out=out)
+
+
+def conv3x3_plain16_pre_act_pool(xs, wq, Cout, save, out=None, a_amax=None, a=None, yP=None, y=None):
+    """conv3x3_plain16_pre_act with the 2 x 2 max-pooling of the activation in the same epilogue: besides aP (`out`: the skip groups of a
+    concat buffer qualify), `a` and `a_amax` the launch writes the pooled tensor as one-part bf16 slots (yP [B, Cout/8, H/2, 1, W/2, 8]),
+    as fp32 (y [B, Cout, H/2, W/2]) or both -- at least one.  conv3x3_split_pre (fp32 z) followed by bn_relu_apply_pool_split, bit for
+    bit, without the tensor z.  -> aP, or None where the kernel does not take the shape (nothing launched)."""
+    return eval_conv("bf16", "full", "act_pool", xs, wq, Cout, save, out=out, a_amax=a_amax, a=a, yP=yP, y=y)
+
+
 def conv3x3_plain16_pre_head(xs, wq, Cout, save, L, out=None):
     """V [B, 1, H, W] = sum_c L[c] relu(bn(conv3x3(xs)))[c] on PLAIN bf16 operands (conv3x3_plain16_pre_act's), the model's last unit
     with the head's channel product in the convolution's epilogue: neither the pre-activation nor the activation is written.  `save`
@@ -1743,27 +1704,71 @@ def conv3x3_plain16_pre_head(xs, wq, Cout, save, L, out=None):
     destination.  The accumulators are those of conv3x3_split_pre's launch bit for bit; the channel sum runs in the kernel's own fixed
     order.  -> V, or None where the kernel does not take the shape (Cout != 64, maps not made of full 16 x 32 tiles, Cin % 32: nothing
     launched, nothing written)."""
-    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
-        raise TypeError("conv3x3_plain16_pre_head: xs and wq must be one-part bf16 packs on the GPU")
-    return _pre_head("onet_conv3x3_plain16_fwd_pre_head", "conv3x3_pre16_head_kernel", 1, xs, wq, Cout, save, L, out, ())
+    return eval_conv("bf16", "full", "head", xs, wq, Cout, save, L, out=out)
 
 
 def conv3x3_plain16_pre_head_ragged(xs, wq, Cout, save, L, out=None):
     """conv3x3_plain16_pre_head on a ragged map (conv3x3_plain16_pre_act_ragged's domain, Cout == 64).  -> V, or None (nothing launched,
     nothing written)."""
-    if wq is None or not wq.is_cuda or wq.dtype != BF or xs.dtype != BF or xs.shape[3] != 1:
-        raise TypeError("conv3x3_plain16_pre_head_ragged: xs and wq must be one-part bf16 packs on the GPU")
-    return _pre_head("onet_conv3x3_plain16_fwd_pre_head_ragged", "conv3x3_pre16_head_kernel", 1, xs, wq, Cout, save, L, out, ())
+    return eval_conv("bf16", "ragged", "head", xs, wq, Cout, save, L, out=out)
+
+
+# ---- fp16 (hi | mid) operands.  slots / slots2 / split_ch: the magnitude slots the producers scaled xs by
+def conv3x3_split_pre_act(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None):
+    """aP = relu(bn(conv3x3(xs))) written PRE-SPLIT, BatchNorm with the fixed coefficients `save` [4, Cout] (bn_eval_coeffs) in the
+    convolution's epilogue: conv3x3_split_pre followed by bn_relu_apply_split(.., slots=aP_slots), bit for bit, without the tensor z.
+    aP_slots: the bound the parts are scaled by (conv3x3_act_bound, before this launch); a_amax: slots that receive the exact max a;
+    a: optional fp32 destination.  -> aP, or None where the kernel does not take the shape (nothing launched)."""
+    return eval_conv("fp16x2", "full", "act", xs, wq, Cout, save, None, aP_slots, out, slots, slots2, split_ch, a_amax, a)
+
+
+def conv3x3_split_pre_act_ragged(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None):
+    """conv3x3_split_pre_act on a ragged map (even H, W % 4 == 0; onet_conv3x3_split_fwd_pre_act_ragged): on the map, value for value,
+    what conv3x3_split_pre_act writes on the map zero-padded to whole 16 x 32 tiles; nothing outside the map is written.  a_amax: the
+    exact maximum over the MAP's pixels (bit-equal to a.max() of the same launch).  -> aP, or None (nothing launched)."""
+    return eval_conv("fp16x2", "ragged", "act", xs, wq, Cout, save, None, aP_slots, out, slots, slots2, split_ch, a_amax, a)
+
+
+def conv3x3_split_pre_act_pairs(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None):
+    """conv3x3_split_pre_act_ragged on maps of 0 < W <= 16 and any H, on IMAGE-PAIR tiles (onet_conv3x3_split_fwd_pre_act_pairs): two
+    images of the batch side by side in a tile's 32 columns; the same values, a_amax the exact maximum over the map's pixels of the
+    batch's own images.  Any batch size (an odd one: the last tile holds one image).  -> aP, or None where the kernel does not take
+    the shape (nothing launched)."""
+    return eval_conv("fp16x2", "pairs", "act", xs, wq, Cout, save, None, aP_slots, out, slots, slots2, split_ch, a_amax, a)
+
+
+def conv3x3_split_pre_act_pool(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None, yP=None,
+                               y=None):
+    """conv3x3_split_pre_act with the 2 x 2 max-pooling of the activation in the same epilogue (conv3x3_plain16_pre_act_pool on fp16
+    hi | mid parts): the pooled slots yP [B, Cout/8, H/2, 2, W/2, 8] are parts of 2^k m with the k of aP (aP_slots).  conv3x3_split_pre
+    followed by bn_relu_apply_pool_split(.., slots=aP_slots), bit for bit.  -> aP, or None (nothing launched)."""
+    return eval_conv("fp16x2", "full", "act_pool", xs, wq, Cout, save, None, aP_slots, out, slots, slots2, split_ch, a_amax, a, yP, y)
+
+
+def conv3x3_split_pre_act_pool_ragged(xs, wq, Cout, save, aP_slots, out=None, slots=None, slots2=None, split_ch=0, a_amax=None, a=None,
+                                      yP=None, y=None):
+    """conv3x3_split_pre_act_pool on a ragged map (even H, W % 4 == 0; onet_conv3x3_split_fwd_pre_act_pool_ragged): the pooled maps are
+    H / 2 x W / 2; a_amax receives the maximum over the map's own pixels.  -> aP, or None (nothing launched)."""
+    return eval_conv("fp16x2", "ragged", "act_pool", xs, wq, Cout, save, None, aP_slots, out, slots, slots2, split_ch, a_amax, a, yP, y)
 
 
 def conv3x3_split_pre_head(xs, wq, Cout, save, L, out=None, slots=None, slots2=None, split_ch=0):
-    """conv3x3_plain16_pre_head on fp16 (hi | mid) parts (conv3x3_split_pre_act's operands; slots / slots2 / split_ch: the magnitude
-    slots the producers scaled xs by).  The convolution runs on the 16x16x32 kernel: its accumulators agree with conv3x3_split_pre's
-    (the 32x32x16 kernel) to fp32 accumulation order.  -> V, or None (Cout != 64, maps not made of full tiles, Cin % 16)."""
-    if wq is None or not wq.is_cuda or wq.dtype != torch.float16 or xs.dtype != torch.float16 or xs.shape[3] != 2:
-        raise TypeError("conv3x3_split_pre_head: xs and wq must be fp16 (hi | mid) split packs on the GPU")
-    return _pre_head("onet_conv3x3_split_fwd_pre_head", "conv3x3_split_pre_head_kernel", 2, xs, wq, Cout, save, L, out,
-                     (_p(slots), 0, _p(slots2), int(split_ch if slots2 is not None or slots is not None else 0)))
+    """conv3x3_plain16_pre_head on fp16 (hi | mid) parts (conv3x3_split_pre_act's operands).  The convolution runs on the 16x16x32
+    kernel: its accumulators agree with conv3x3_split_pre's (the 32x32x16 kernel) to fp32 accumulation order.  -> V, or None
+    (Cout != 64, maps not made of full tiles, Cin % 16)."""
+    return eval_conv("fp16x2", "full", "head", xs, wq, Cout, save, L, None, out, slots, slots2, split_ch)
+
+
+def conv3x3_split_pre_head_ragged(xs, wq, Cout, save, L, out=None, slots=None, slots2=None, split_ch=0):
+    """conv3x3_split_pre_head on a ragged map (conv3x3_split_pre_act_ragged's domain, Cout == 64).  -> V, or None (nothing launched,
+    nothing written)."""
+    return eval_conv("fp16x2", "ragged", "head", xs, wq, Cout, save, L, None, out, slots, slots2, split_ch)
+
+
+def conv3x3_split_pre_plain_ragged(xs, wq, Cout, out=None, slots=None, slots2=None, split_ch=0):
+    """z = conv3x3 (fp32) of fp16 (hi | mid) slots on a ragged map (conv3x3_split_pre_act_ragged's domain): conv3x3_split_pre's launch
+    there.  -> z, or None (nothing launched)."""
+    return eval_conv("fp16x2", "ragged", "plain", xs, wq, Cout, out=out, slots=slots, slots2=slots2, split_ch=split_ch)
 
 
 FUSE_DGRAD_REDUCE = _flag("FUSE_DGRAD_REDUCE", True)      # False (tests / A-B): the first unit of a DoubleConv runs its own BatchNorm-backward reduce pass

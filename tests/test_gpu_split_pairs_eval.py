@@ -79,7 +79,7 @@ def _check_run(r, route_up1, what):
     assert n_of == {"fused": 12, "fused+pool": 4, "plain+head": 1}, n_of
     with ops.using(r["m"].settings):
         levels = inference._query(r["m"].topu, (plan["batch"],) + tuple(r["Xg"].shape[1:])).levels
-    assert levels[4].ragged == "pairs" and levels[3].route == route_up1 and levels[3].pooled_slots, [(lv.ragged, lv.route) for lv in levels]
+    assert levels[4].mode == "pairs" and levels[3].route == route_up1 and levels[3].pooled_slots, [(lv.mode, lv.route) for lv in levels]
     assert not any(u.keep_fp32 for lv in levels for u in lv.enc + lv.dec)
     assert r["names"] == fe._slot_writers(plan) * passes, (what, r["names"], fe._slot_writers(plan))
     assert {"down4.c1", "down4.c2", "up1.up", "up1.c1"} <= set(r["names"])

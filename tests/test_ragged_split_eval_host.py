@@ -38,7 +38,7 @@ def _module(name, file):
 def test_value_is_accepted_and_a_misspelling_raises():
     import onet_amd
     from onet_amd import ops
-    assert ops._FUSED_EVAL_VALUES[VALUE] == ("fp16x2", True, True)
+    assert ops._FUSED_EVAL_VALUES[VALUE] == ops._FusedEval("fp16x2", True, frozenset(("full", "ragged")), False)
     with ops.using(ops.Settings(fused_eval=VALUE)):
         assert (ops.fused_eval(), ops.fused_eval_operands(), ops.fused_eval_pool(), ops.fused_eval_ragged()) == (True, "fp16x2", True, True)
     for v, want in ((None, False), (False, False), (True, False), ("bf16", False), ("fp16x2+pool", False), ("bf16+pool", False),

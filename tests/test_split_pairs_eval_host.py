@@ -49,7 +49,7 @@ def test_value_is_accepted_and_the_other_values_answer_as_before():
         with ops.using(ops.Settings(fused_eval=v)):
             assert _answers(ops) == want, v
             assert ops.fused_eval_pairs_fp16() is False, v
-    assert ops._FUSED_EVAL_VALUES[RAGGED] == ("fp16x2", True, True)
+    assert ops._FUSED_EVAL_VALUES[RAGGED] == ops._FusedEval("fp16x2", True, frozenset(("full", "ragged")), False)
     s = ops.Settings(conv="split", fused_eval=VALUE)
     assert s.replace(twin=False).fused_eval == VALUE and f"fused_eval={VALUE!r}" in repr(s)
     m = onet_amd.Onet(in_chns=1, binit=True, bshare=True).eval()
