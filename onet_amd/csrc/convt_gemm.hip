@@ -1434,82 +1434,82 @@ int onet_convT2x2_wgrad_slots(const void* xP, int64_t xP_bs, const void* x_amax,
     return check_launch("convt_dbias_reduce_kernel");
 }
 
+// ---- the slot-operand forward: four entries, one checked launch path (convt_slots), as eval_conv in conv_split.hip.  Each entry is a
+// descriptor row and its arguments; a new point of the parts x map-mode space is a row here ("The fused eval table").
+// Every entry asks Cin % 32 == 0, Cin >= 128, Ct % 32 == 0, 16-byte aligned pointers, batch strides (4-byte units) that are multiples
+// of 4, operand and weight pack inside the buffer-resource range (2 GiB), and the maps of its mode (CtMap); outside: 1, nothing launched.
+//   Full    h w % 128 == 0, even w: the pixel tiles run over the batch.
+//   Ragged  even w (include/onet_hip_ragged.h, onet_hip_ragged_split.h): cdiv(h w, 128) tiles PER IMAGE, below 2^24 over the batch.
+//   AnyMap  ANY w, into an output map of Ho x Wo slots per channel group, Ho - 2h and Wo - 2w in {0, 1} (include/onet_hip_upmap.h): the
+//           up-sampled block in the top-left corner, the pad strip written as zero slots by the same launch.  Even w without a pad
+//           strip: the Ragged instance, under this entry's name.
+enum class CtMap { Full, Ragged, AnyMap };
+struct CtEntry {
+    const char* name;      // what the messages start with
+    int parts;             // the parts per slot in the entry's domain, 1 (plain bf16) or 2 (fp16 hi | mid) -- another nparts: 1; 0: both
+    CtMap map;
+    bool full_tiles;       // Ragged: h w % 128 == 0 launches the Full instance (the fp16 entry; the one-part entry keeps its own)
+};
+struct CtArgs {            // (as the prototypes list them; x_amax, y_amax: NULL and nparts = 1 where the entry has none)
+    const void* xP; int64_t xP_bs; const void* x_amax; const void* wP; const float* bias;
+    void* yP; int64_t yP_bs; const void* y_amax;
+    int nparts, B, Cin, Ct, h, w, Ho, Wo;      // (Ho, Wo: AnyMap alone -- the other modes write the dense 2h x 2w map)
+    void* stream;
+};
+
+static int convt_slots(const CtEntry& e, const CtArgs& a) {
+    const bool any = e.map == CtMap::AnyMap;
+    const int np = a.nparts, B = a.B, Cin = a.Cin, Ct = a.Ct, h = a.h, w = a.w;
+    // 1. arguments
+    ONET_REQUIRE(a.xP && a.wP && a.yP && B > 0 && Cin > 0 && Ct > 0 && h > 0 && w > 0 && (!any || (a.Ho > 0 && a.Wo > 0)) && (np == 1 || np == 2),
+                 "%s: bad args", e.name);
+    // 2. domain: 1, nothing launched
+    const int64_t hw = (int64_t)h * w, ph = any ? (int64_t)a.Ho - 2ll * h : 0, pw = any ? (int64_t)a.Wo - 2ll * w : 0;
+    if ((e.parts && np != e.parts) || (Cin % 32) || Cin < 128 || (Ct % 32) || !aligned16(a.xP) || !aligned16(a.wP) || !aligned16(a.yP) || (a.xP_bs & 3) ||
+        (a.yP_bs & 3) || (int64_t)Cin * hw * 2 * np >= (1ll << 31) || (int64_t)Cin * 4 * Ct * 2 * np >= (1ll << 31) ||
+        (any ? (ph < 0 || ph > 1 || pw < 0 || pw > 1) : ((w & 1) || (e.map == CtMap::Full && (hw % 128)))))
+        return 1;
+    const int Ho = 2 * h + (int)ph, Wo = 2 * w + (int)pw;
+    // 3. batch strides: slots of 8 two-byte elements per part, in 4-byte units
+    ONET_REQUIRE(a.xP_bs >= (int64_t)(Cin / 8) * hw * 4 * np && a.yP_bs >= (int64_t)(Ct / 8) * Ho * Wo * 4 * np, "%s: batch stride too small", e.name);
+    // 4. a map a narrower mode holds takes that mode's instance
+    CtMap map = e.map;
+    if (any && !(w & 1) && !ph && !pw) map = CtMap::Ragged;
+    else if (map == CtMap::Ragged && e.full_tiles && (hw % 128) == 0) map = CtMap::Full;
+    // 5. pixel tiles: per image
+    const int64_t ntiles = (int64_t)B * ((hw + 127) / 128);
+    ONET_REQUIRE(map == CtMap::Full || ntiles < (1ll << 24), "%s: grid too large", e.name);
+    SArgs g{a.wP, a.xP, a.xP_bs, a.bias, a.yP, a.yP_bs, (const unsigned*)a.x_amax, (const unsigned*)a.y_amax, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)ntiles, Ho, Wo};
+    const int64_t blocks = (int64_t)g.mTiles * g.nTiles;      // 6. grid
+    ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "%s: grid too large", e.name);
+    const dim3 grid((unsigned)blocks), block(256);      // the instances that exist: <NP, RAG, ANY>
+    hipStream_t st = as_stream(a.stream);
+    if (map == CtMap::Full && np == 2) hipLaunchKernelGGL(convt_slot_fwd_kernel<2>, grid, block, 0, st, g);
+    else if (map == CtMap::Full) hipLaunchKernelGGL(convt_slot_fwd_kernel<1>, grid, block, 0, st, g);
+    else if (map == CtMap::Ragged && np == 1) hipLaunchKernelGGL((convt_slot_fwd_kernel<1, true>), grid, block, 0, st, g);
+    else if (map == CtMap::Ragged) hipLaunchKernelGGL((convt_slot_fwd_kernel<2, true>), grid, block, 0, st, g);
+    else hipLaunchKernelGGL((convt_slot_fwd_kernel<1, true, true>), grid, block, 0, st, g);
+    return check_launch("convt_slot_fwd_kernel");
+}
+
 int onet_convT2x2_fwd_slots(const void* xP, int64_t xP_bs, const void* x_amax, const void* wP, const float* bias, void* yP, int64_t yP_bs,
                             const void* y_amax, int nparts, int B, int Cin, int Ct, int h, int w, void* stream) {
-    ONET_REQUIRE(xP && wP && yP && B > 0 && Cin > 0 && Ct > 0 && h > 0 && w > 0 && (nparts == 1 || nparts == 2), "convT2x2_fwd_slots: bad args");
-    const int64_t hw = (int64_t)h * w;
-    if ((Cin % 32) || Cin < 128 || (Ct % 32) || (hw % 128) || (w & 1) || !aligned16(xP) || !aligned16(wP) || !aligned16(yP) || (xP_bs & 3) || (yP_bs & 3) ||
-        (int64_t)Cin * hw * 2 * nparts >= (1ll << 31) || (int64_t)Cin * 4 * Ct * 2 * nparts >= (1ll << 31))
-        return 1;                                              // shape outside the fast path: nothing done
-    ONET_REQUIRE(xP_bs >= (int64_t)Cin * hw * nparts / 2 && yP_bs >= (int64_t)Ct * 4 * hw * nparts / 2, "convT2x2_fwd_slots: batch stride too small");
-    SArgs g{wP, xP, xP_bs, bias, yP, yP_bs, (const unsigned*)x_amax, (const unsigned*)y_amax, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)(B * hw / 128), 2 * h, 2 * w};
-    const int64_t blocks = (int64_t)g.mTiles * g.nTiles;
-    ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "convT2x2_fwd_slots: grid too large");
-    if (nparts == 2) hipLaunchKernelGGL(convt_slot_fwd_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
-    else hipLaunchKernelGGL(convt_slot_fwd_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
-    return check_launch("convt_slot_fwd_kernel");
+    return convt_slots({"convT2x2_fwd_slots", 0, CtMap::Full, false}, {xP, xP_bs, x_amax, wP, bias, yP, yP_bs, y_amax, nparts, B, Cin, Ct, h, w, 0, 0, stream});
 }
 
-// onet_convT2x2_fwd_slots (nparts = 1) on maps whose pixel count is no multiple of 128 (include/onet_hip_ragged.h): its domain without
-// h w % 128 == 0.  Returns 1 (nothing launched) outside it.
 int onet_convT2x2_fwd_slots_ragged(const void* xP, int64_t xP_bs, const void* wP, const float* bias, void* yP, int64_t yP_bs, int B, int Cin, int Ct,
                                    int h, int w, void* stream) {
-    ONET_REQUIRE(xP && wP && yP && B > 0 && Cin > 0 && Ct > 0 && h > 0 && w > 0, "convT2x2_fwd_slots_ragged: bad args");
-    const int64_t hw = (int64_t)h * w;
-    if ((Cin % 32) || Cin < 128 || (Ct % 32) || (w & 1) || !aligned16(xP) || !aligned16(wP) || !aligned16(yP) || (xP_bs & 3) || (yP_bs & 3) ||
-        (int64_t)Cin * hw * 2 >= (1ll << 31) || (int64_t)Cin * 4 * Ct * 2 >= (1ll << 31))
-        return 1;
-    ONET_REQUIRE(xP_bs >= (int64_t)Cin * hw / 2 && yP_bs >= (int64_t)Ct * 4 * hw / 2, "convT2x2_fwd_slots_ragged: batch stride too small");
-    const int64_t ntiles = (int64_t)B * ((hw + 127) / 128);
-    ONET_REQUIRE(ntiles < (1ll << 24), "convT2x2_fwd_slots_ragged: grid too large");
-    SArgs g{wP, xP, xP_bs, bias, yP, yP_bs, nullptr, nullptr, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)ntiles, 2 * h, 2 * w};
-    const int64_t blocks = (int64_t)g.mTiles * g.nTiles;
-    ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "convT2x2_fwd_slots_ragged: grid too large");
-    hipLaunchKernelGGL((convt_slot_fwd_kernel<1, true>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
-    return check_launch("convt_slot_fwd_kernel");
+    return convt_slots({"convT2x2_fwd_slots_ragged", 1, CtMap::Ragged, false}, {xP, xP_bs, nullptr, wP, bias, yP, yP_bs, nullptr, 1, B, Cin, Ct, h, w, 0, 0, stream});
 }
 
-// onet_convT2x2_fwd_slots (nparts = 2: fp16 hi | mid operands with their magnitude slots) on maps whose pixel count is no multiple of 128
-// (include/onet_hip_ragged_split.h): its domain without h w % 128 == 0.  Returns 1 (nothing launched) outside it, nparts = 1 included
-// (onet_convT2x2_fwd_slots_ragged is that entry).  h w % 128 == 0: the launch of onet_convT2x2_fwd_slots.
 int onet_convT2x2_fwd_slots_split_ragged(const void* xP, int64_t xP_bs, const void* x_amax, const void* wP, const float* bias, void* yP,
                                          int64_t yP_bs, const void* y_amax, int nparts, int B, int Cin, int Ct, int h, int w, void* stream) {
-    ONET_REQUIRE(xP && wP && yP && B > 0 && Cin > 0 && Ct > 0 && h > 0 && w > 0 && (nparts == 1 || nparts == 2), "convT2x2_fwd_slots_split_ragged: bad args");
-    const int64_t hw = (int64_t)h * w;
-    if (nparts != 2 || (Cin % 32) || Cin < 128 || (Ct % 32) || (w & 1) || !aligned16(xP) || !aligned16(wP) || !aligned16(yP) || (xP_bs & 3) ||
-        (yP_bs & 3) || (int64_t)Cin * hw * 4 >= (1ll << 31) || (int64_t)Cin * 4 * Ct * 4 >= (1ll << 31))
-        return 1;
-    ONET_REQUIRE(xP_bs >= (int64_t)Cin * hw && yP_bs >= (int64_t)Ct * 4 * hw, "convT2x2_fwd_slots_split_ragged: batch stride too small");
-    if ((hw % 128) == 0) return onet_convT2x2_fwd_slots(xP, xP_bs, x_amax, wP, bias, yP, yP_bs, y_amax, 2, B, Cin, Ct, h, w, stream);
-    const int64_t ntiles = (int64_t)B * ((hw + 127) / 128);
-    ONET_REQUIRE(ntiles < (1ll << 24), "convT2x2_fwd_slots_split_ragged: grid too large");
-    SArgs g{wP, xP, xP_bs, bias, yP, yP_bs, (const unsigned*)x_amax, (const unsigned*)y_amax, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)ntiles, 2 * h, 2 * w};
-    const int64_t blocks = (int64_t)g.mTiles * g.nTiles;
-    ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "convT2x2_fwd_slots_split_ragged: grid too large");
-    hipLaunchKernelGGL((convt_slot_fwd_kernel<2, true>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
-    return check_launch("convt_slot_fwd_kernel");
+    return convt_slots({"convT2x2_fwd_slots_split_ragged", 2, CtMap::Ragged, true}, {xP, xP_bs, x_amax, wP, bias, yP, yP_bs, y_amax, nparts, B, Cin, Ct, h, w, 0, 0, stream});
 }
 
-// onet_convT2x2_fwd_slots_ragged on a map of ANY w, odd included, into an output map of Ho x Wo slots per channel group
-// (include/onet_hip_upmap.h): the up-sampled 2h x 2w block in the top-left corner, the pad strip -- Ho - 2h, Wo - 2w in {0, 1} --
-// written as zero slots by the same launch.  Returns 1 (nothing launched) outside the domain.  Even w without a pad strip: the launch of
-// onet_convT2x2_fwd_slots_ragged.
 int onet_convT2x2_fwd_slots_anymap(const void* xP, int64_t xP_bs, const void* wP, const float* bias, void* yP, int64_t yP_bs, int B, int Cin, int Ct,
                                    int h, int w, int Ho, int Wo, void* stream) {
-    ONET_REQUIRE(xP && wP && yP && B > 0 && Cin > 0 && Ct > 0 && h > 0 && w > 0 && Ho > 0 && Wo > 0, "convT2x2_fwd_slots_anymap: bad args");
-    const int64_t hw = (int64_t)h * w, ph = (int64_t)Ho - 2ll * h, pw = (int64_t)Wo - 2ll * w;
-    if ((Cin % 32) || Cin < 128 || (Ct % 32) || ph < 0 || ph > 1 || pw < 0 || pw > 1 || !aligned16(xP) || !aligned16(wP) || !aligned16(yP) ||
-        (xP_bs & 3) || (yP_bs & 3) || (int64_t)Cin * hw * 2 >= (1ll << 31) || (int64_t)Cin * 4 * Ct * 2 >= (1ll << 31))
-        return 1;
-    ONET_REQUIRE(xP_bs >= (int64_t)Cin * hw / 2 && yP_bs >= (int64_t)(Ct / 8) * Ho * Wo * 4, "convT2x2_fwd_slots_anymap: batch stride too small");
-    if (!(w & 1) && !ph && !pw) return onet_convT2x2_fwd_slots_ragged(xP, xP_bs, wP, bias, yP, yP_bs, B, Cin, Ct, h, w, stream);
-    const int64_t ntiles = (int64_t)B * ((hw + 127) / 128);
-    ONET_REQUIRE(ntiles < (1ll << 24), "convT2x2_fwd_slots_anymap: grid too large");
-    SArgs g{wP, xP, xP_bs, bias, yP, yP_bs, nullptr, nullptr, B, Cin, Ct, h, w, (4 * Ct) / 128, (int)ntiles, Ho, Wo};
-    const int64_t blocks = (int64_t)g.mTiles * g.nTiles;
-    ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "convT2x2_fwd_slots_anymap: grid too large");
-    hipLaunchKernelGGL((convt_slot_fwd_kernel<1, true, true>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
-    return check_launch("convt_slot_fwd_kernel");
+    return convt_slots({"convT2x2_fwd_slots_anymap", 1, CtMap::AnyMap, false}, {xP, xP_bs, nullptr, wP, bias, yP, yP_bs, nullptr, 1, B, Cin, Ct, h, w, Ho, Wo, stream});
 }
 
 }  // extern "C"

@@ -68,10 +68,12 @@ activation and hands it on with the POOLED tensor -- otherwise down4.c1's bound 
 bound, as every other pooled unit's tensors do.
 
 CONVTRANSPOSE2D EDGES.  The ConvTranspose2d of level k reads the output of level k + 1 and fills the up-sampled groups of level k's
-concat buffer; _Level.route names its launches (_build_plan.up_edge decides, _conv_t follows):
+concat buffer; _Level.route names its launch, a row of _ROUTES: what the edge reads and, for the slot routes, the edge mode of its row
+in ops.CONVT_ENTRIES.  _up_edge decides the route, _conv_t looks the launch up and runs it; a refusal is an error, never another route:
   "slots"         the slot-operand GEMM, from the slots of a fused level below (h w % 128 == 0);
   "slots_ragged"  its ragged entry (h w % 128 != 0, even w; two parts on fp16x2) where ops.convt_slots_ok_ragged holds;
-  "gemm"          from an fp32 tensor -- a fall-back level's output -- by the fp32-operand GEMM that writes slots;
+  "gemm"          from an fp32 tensor -- a fall-back level's output, or a fused level's fp32 copy where the switches or the channel
+                  counts keep the slot GEMM off -- by the fp32-operand GEMM that writes slots (ops.convT2x2_fwd_p), and nothing else;
   "pack"          where that GEMM does not take the map: the general kernel into an fp32 tensor of the concat map's size, then one
                   conversion pass (two parts scaled by the ConvTranspose2d's own bound on fp16x2).  On any-map levels also wherever
                   the output must be padded (level k is odd) or the input map has odd w -- the slot GEMMs keep their dense 2h x 2w,
@@ -265,27 +267,7 @@ def _build_plan(unet, shape, head=None):
     d, why_d = _depth(units, ups, fmt, N, H, W)
     if d == 0:
         return _Plan(fmt, N, why_d, None, 0, why_d)
-    # the ConvTranspose2d of level k reads the output of level k + 1: slots where that level is fused and the slot-operand kernel takes
-    # the map, else the fp32 tensor its producer -- the last unit of level k + 1, or the fall-back levels -- leaves
-    ragged = "ragged" in fmt.modes
-
-    def up_edge(k, up):
-        h, w, cin, ct = H >> (k + 1), W >> (k + 1), up.up.in_channels, up.up.out_channels
-        if k >= d:
-            return "fallback", None
-        if "anymap" in fmt.modes and ((H >> k, W >> k) != (2 * h, 2 * w) or w % 2):
-            # (any-map levels: the output is padded into the concat buffer -- level k is odd -- or the input map has odd w; the slot
-            # GEMMs keep their dense 2h x 2w, even-w domain -- but for the any-map entry, which takes both and writes the pad strip)
-            if fmt.upmap and k + 1 < d and ops.convt_slots_ok_anymap(N, cin, ct, h, w, H >> k, W >> k):
-                return "slots", "slots_anymap"
-            return "fp32->slots", "pack"
-        if k + 1 < d and ops.convt_slots_ok(N, cin, ct, h, w, parts=fmt.parts):
-            return "slots", "slots"
-        if k + 1 < d and ragged and (h * w) % 128 and ops.convt_slots_ok_ragged(N, cin, ct, h, w, parts=fmt.parts):
-            return "slots", "slots_ragged"
-        # (without ragged levels a fused level is made of full 16 x 32 tiles, so the map below it has h w % 128 == 0)
-        return "fp32->slots", ("pack" if ragged and (h * w) % 128 else "gemm")
-    edges = [up_edge(k, up) for k, up in enumerate(ups)]
+    edges = [_up_edge(fmt, d, k, N, up.up.in_channels, up.up.out_channels, (H >> (k + 1), W >> (k + 1)), (H >> k, W >> k)) for k, up in enumerate(ups)]
     convt = [e[0] for e in edges]
     with_head = head == "fused" and _head_ok(unet)
     # pooled units: plain convolution + BatchNorm / ReLU / pooling pass writing slots, or -- "+pool" -- all of it in the convolution's launch
@@ -314,6 +296,34 @@ def _level_mode(fmt, k, h, w):
     if k == 4 and w <= 16 and "pairs" in fmt.modes:
         return "pairs"
     return "ragged" if ops._ragged_map(h, w) else "anymap"
+
+
+# The ConvTranspose2d edges: route -> (what the edge reads = _Level.convt, the mode of its launch in ops.CONVT_ENTRIES | None: one of the
+# two fp32 routes of _conv_t, the predicate in `ops` that accepted the shape)
+_Route = namedtuple("_Route", "convt mode ok", defaults=(None, None))
+_ROUTES = {"slots": _Route("slots", "full", "convt_slots_ok"), "slots_ragged": _Route("slots", "ragged", "convt_slots_ok_ragged"),
+           "slots_anymap": _Route("slots", "anymap", "convt_slots_ok_anymap"), "gemm": _Route("fp32->slots"), "pack": _Route("fp32->slots")}
+
+
+def _up_edge(fmt, d, k, N, cin, ct, lo, hi):
+    """-> (convt, route) of the ConvTranspose2d (cin -> ct) that reads the output of level k + 1 (maps of lo = (h, w)) and fills level
+    k's concat buffer (maps of hi): slots where level k + 1 is fused (k + 1 < d) and a slot-operand entry takes the map, else the fp32
+    tensor its producer -- the last unit of level k + 1, or the fall-back levels -- leaves"""
+    (h, w), ragged = lo, "ragged" in fmt.modes
+    if k >= d:
+        return "fallback", None
+    if "anymap" in fmt.modes and (hi != (2 * h, 2 * w) or w % 2):
+        # (any-map levels: the output is padded into the concat buffer -- level k is odd -- or the input map has odd w; the slot
+        # GEMMs keep their dense 2h x 2w, even-w domain -- but for the any-map entry, which takes both and writes the pad strip)
+        route = "slots_anymap" if fmt.upmap and k + 1 < d and ops.convt_slots_ok_anymap(N, cin, ct, h, w, *hi) else "pack"
+    elif k + 1 < d and ops.convt_slots_ok(N, cin, ct, h, w, parts=fmt.parts):
+        route = "slots"
+    elif k + 1 < d and ragged and (h * w) % 128 and ops.convt_slots_ok_ragged(N, cin, ct, h, w, parts=fmt.parts):
+        route = "slots_ragged"
+    else:
+        # (without ragged levels a fused level is made of full 16 x 32 tiles, so the map below it has h w % 128 == 0)
+        route = "pack" if ragged and (h * w) % 128 else "gemm"
+    return _ROUTES[route].convt, route
 
 
 def _query(unet, shape, head=None, device=None):
@@ -535,40 +545,27 @@ def _conv_t(fmt, lv, t, catP, C2):
         s_up = ops.convT2x2_out_bound(up.weight, up.bias, _amax(t))
     dst = catP[:, C2 // 8:]
     packed = up.packed()
-    if lv.route == "slots_ragged":
-        if fmt.parts == 2:
-            done = ops.convT2x2_fwd_slots_split_ragged(t.P, packed.slots(2), up.bias, dst, Ct, x_slots=t.scale, slots=s_up)
-        else:
-            done = ops.convT2x2_fwd_slots_ragged(t.P, packed.slots(fmt.parts), up.bias, dst, Ct)
-        if not done:
-            raise RuntimeError("onet_amd: the ragged slot-operand ConvTranspose2d refused a shape ops.convt_slots_ok_ragged accepted")
-        return s_up
-    if lv.route == "slots_anymap":
-        # (one-part format alone: an odd-w input map and / or an output one row, one column short of the concat map -- the launch
-        # writes the pad strip as zero slots itself)
-        if not ops.convT2x2_fwd_slots_anymap(t.P, packed.slots(1), up.bias, dst, Ct):
-            raise RuntimeError("onet_amd: the any-map slot-operand ConvTranspose2d refused a shape ops.convt_slots_ok_anymap accepted")
-        return s_up
-    if lv.route == "pack":
+    route = _ROUTES[lv.route]
+    if route.mode is not None:
+        # (the row's binding in `ops`, read at call time as _launch does; the magnitude slots of a format that has them)
+        name = ops.eval_convt_name(fmt.operands, route.mode)
+        kw = dict(x_slots=t.scale, slots=s_up) if fmt.magnitude else {}
+        if name is None or not getattr(ops, name)(t.P, packed.slots(fmt.parts), up.bias, dst, Ct, kind="convt_slot_fwd_kernel", **kw):
+            raise RuntimeError(f"onet_amd: route {lv.route!r}: the {route.mode!r} slot-operand ConvTranspose2d of {fmt.operands} slots ({name}) "
+                               f"refused a shape ops.{route.ok} accepted")
+    elif lv.route == "pack":
         # (the smallest maps of the pass: the general kernel into an fp32 tensor, then one conversion pass -- what the training forward
-        # does where the GEMM's fast path does not take the map)
-        # any-map levels: an odd concat map takes the up-sampled tensor at the reference's F.pad offsets, the pad strip zero (the kernel
-        # writes its 2h x 2w window alone)
+        # does where the GEMM's fast path does not take the map.  An odd concat map of an any-map level takes the up-sampled tensor at
+        # the reference's F.pad offsets, the pad strip zero: the kernel writes its 2h x 2w window alone)
         B, _, h, w = t.F.shape
         Ho, Wo = catP.shape[2], catP.shape[4]
         padded = (Ho, Wo) != (2 * h, 2 * w)
         y = (torch.zeros if padded else torch.empty)((B, Ct, Ho, Wo), dtype=torch.float32, device=t.F.device)
         ops.convT2x2_fwd(t.F, packed[0], up.bias, y, Ct, (Ho - 2 * h) // 2, (Wo - 2 * w) // 2)
         ops.split_pack_act(y, out=dst, slots=s_up)
-        return s_up
-    if t.P is not None and ops.convT2x2_fwd_slots(t.P, packed.slots(fmt.parts), up.bias, dst, Ct, x_slots=t.scale, slots=s_up,
-                                                   kind="convt_slot_fwd_kernel"):
-        return s_up
-    if t.F is None:
-        raise RuntimeError("onet_amd: the slot-operand ConvTranspose2d refused a shape ops.convt_slots_ok accepted")
-    # (route "gemm": the map has h w % 128 == 0 -- _build_plan -- so the GEMM's fast path takes it)
-    if not ops.convT2x2_fwd_p(t.F, packed[0], up.bias, dst, Ct, 0, 0, slots=s_up):
-        raise RuntimeError("onet_amd: the ConvTranspose2d GEMM refused the fp32 input of a fused level")
+    # ("gemm": the map has h w % 128 == 0 -- _up_edge -- so the fp32-operand GEMM's fast path takes it)
+    elif not ops.convT2x2_fwd_p(t.F, packed[0], up.bias, dst, Ct, 0, 0, slots=s_up):
+        raise RuntimeError("onet_amd: route 'gemm': the ConvTranspose2d GEMM refused the fp32 input of a fused level")
     return s_up
 
 

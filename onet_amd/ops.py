@@ -628,12 +628,33 @@ def conv3x3_split_dgrad_pre_slots(dzP, wq, Cout, ch0, daP_slots, slots=None, alw
 CONVT_SLOTS = _flag("CONVT_SLOTS", True)     # 0: the ConvTranspose2d forward reads the fp32 activation (round 4's kernels)
 
 
+def _convt_domain(parts, mode, B, Cin, Ct, h, w, Ho=None, Wo=None):
+    """Does the slot-operand ConvTranspose2d forward of edge mode `mode` (CONVT_ENTRIES) take a layer Cin -> Ct on B maps of h x w with
+    `parts` parts per slot, and do the switches want it there?  The convt_slots_ok* predicates are its bindings."""
+    # switches; channels and the buffer-resource range
+    if not (CONVT_SLOTS and presplit() and (parts == 2 or CONVT_BF16)) or Cin % 32 or Cin < 128 or Ct % 32 or Cin * h * w * 2 * parts >= 2 ** 31:
+        return False
+    # the mode's maps: any w into the concat map of a floor-pooled level ("anymap"); even w ("ragged") and whole 128-pixel tiles ("full")
+    if mode == "anymap":
+        return h > 0 and w > 0 and Ho - 2 * h in (0, 1) and Wo - 2 * w in (0, 1)
+    return w % 2 == 0 and (mode == "ragged" or (h * w) % 128 == 0)
+
+
 def convt_slots_ok(B, Cin, Ct, h, w, parts=None):
     """Does the slot-operand ConvTranspose2d forward take this layer (onet_convT2x2_fwd_slots' predicate)?  The block below then writes
     its output pre-split for it (UNet._forward).  parts: parts per slot operand (None: p16_parts(), what the active `conv` trains with)."""
-    parts = p16_parts() if parts is None else parts
-    return bool(CONVT_SLOTS and presplit() and (parts == 2 or CONVT_BF16) and Cin % 32 == 0 and Cin >= 128 and Ct % 32 == 0 and (h * w) % 128 == 0 and w % 2 == 0
-                and Cin * h * w * 2 * parts < 2 ** 31)
+    return _convt_domain(p16_parts() if parts is None else parts, "full", B, Cin, Ct, h, w)
+
+
+def convt_slots_ok_ragged(B, Cin, Ct, h, w, parts=1):
+    """convt_slots_ok(parts) without h w % 128 == 0: the predicate of onet_convT2x2_fwd_slots_ragged (parts = 1, the default) /
+    onet_convT2x2_fwd_slots_split_ragged (parts = 2: fp16 hi | mid operands)."""
+    return _convt_domain(parts, "ragged", B, Cin, Ct, h, w)
+
+
+def convt_slots_ok_anymap(B, Cin, Ct, h, w, Ho, Wo):
+    """convt_slots_ok_ragged (one part) without even w, into an output map of Ho x Wo: the predicate of onet_convT2x2_fwd_slots_anymap"""
+    return _convt_domain(1, "anymap", B, Cin, Ct, h, w, Ho, Wo)
 
 
 CONVT_BWD_SLOTS = _flag("CONVT_BWD_SLOTS", True)     # 0: the ConvTranspose2d backward GEMMs read fp32 operands (round 4's kernels)
@@ -705,88 +726,67 @@ class PackedT:
         return v[1]
 
 
-def convT2x2_fwd_slots(xP, wP, bias, outP, Ct, x_slots=None, slots=None, kind="convt_gemm_kernel"):
-    """ConvTranspose2d(k=2, s=2) + bias from the PRE-SPLIT input xP [B, Cin/8, h, parts, w, 8] and the slot pack wP (packT2x2_slots),
-    written pre-split into outP [B, Ct/8, 2h, parts, 2w, 8]: both GEMM operands are LDS-DMA copies.  x_slots / slots: the magnitude slots
-    of the input / output.  -> False where the kernel does not take the shape (nothing written)."""
+# The slot-operand ConvTranspose2d forward (the training forward's launch and the fused eval plan's edges, inference._conv_t): (slot
+# format as EVAL_ENTRIES', edge mode) -> (C entry, its binding by name below).  Edge mode: "full" (h w % 128 == 0, even w) | "ragged" (even
+# w) | "anymap" (any w, into a map of up to one row and one column more).  A combination that is not a row does not exist.
+CONVT_ENTRIES = {
+    ("fp16x2", "full"): ("onet_convT2x2_fwd_slots", "convT2x2_fwd_slots"),
+    ("bf16", "full"): ("onet_convT2x2_fwd_slots", "convT2x2_fwd_slots"),
+    ("bf16", "ragged"): ("onet_convT2x2_fwd_slots_ragged", "convT2x2_fwd_slots_ragged"),
+    ("fp16x2", "ragged"): ("onet_convT2x2_fwd_slots_split_ragged", "convT2x2_fwd_slots_split_ragged"),
+    ("bf16", "anymap"): ("onet_convT2x2_fwd_slots_anymap", "convT2x2_fwd_slots_anymap"),
+}
+
+
+def eval_convt_name(fmt, mode):
+    """The name in this module of the binding of CONVT_ENTRIES[fmt, mode] -- None: no row"""
+    return CONVT_ENTRIES.get((fmt, mode), (None, None))[1]
+
+
+def eval_convt(fmt, mode, xP, wP, bias, outP, Ct, x_slots=None, slots=None, kind="convt_slot_fwd_kernel"):
+    """The launch of CONVT_ENTRIES[fmt, mode], what the convT2x2_fwd_slots* functions below are bindings of: ConvTranspose2d(k=2, s=2) +
+    bias from the PRE-SPLIT input xP [B, Cin/8, h, parts, w, 8] and the slot pack wP (packT2x2_slots), written pre-split into outP
+    [B, Ct/8, Ho, parts, Wo, 8] -- both GEMM operands are LDS-DMA copies.  x_slots / slots: the magnitude slots of input / output.
+    -> False where the kernel does not take the shape (nothing written)."""
+    (entry, _), two = CONVT_ENTRIES[fmt, mode], fmt == "fp16x2"
     B, C8, h, parts, w, _ = xP.shape
-    assert outP.shape[3] == parts and outP.shape[2] == 2 * h and outP.shape[4] == 2 * w and xP.dtype == wP.dtype == outP.dtype
-    Cin = C8 * 8
-    e0 = _prof_begin(kind)       # (the fused eval plan records its launches under the device kernel's own name)
-    rc = _lib.load().onet_convT2x2_fwd_slots(_p(xP), _pbs(xP), _p(x_slots), _p(wP), _p(bias), _p(outP), _pbs(outP), _p(slots), parts, B, Cin, Ct,
-                                             h, w, _stream())
-    eb = 2.0 * parts
-    flops, nb = 2.0 * B * h * w * Cin * 4 * Ct, eb * (B * h * w * (Cin + 4 * Ct) + 4 * Cin * Ct)
+    Cin, Ho, Wo = C8 * 8, outP.shape[2], outP.shape[4]
+    assert parts == outP.shape[3] == 1 + two and xP.dtype == wP.dtype == outP.dtype == (torch.float16 if two else BF)
+    assert outP.shape[1] * 8 == Ct if mode == "anymap" else (Ho, Wo) == (2 * h, 2 * w)
+    with_slots = two or mode == "full"        # (the one-part ragged and any-map entries take neither magnitude slots nor nparts)
+    args = (_p(xP), _pbs(xP), *((_p(x_slots),) if with_slots else ()), _p(wP), _p(bias), _p(outP), _pbs(outP),
+            *((_p(slots), parts) if with_slots else ()), B, Cin, Ct, h, w, *((Ho, Wo) if mode == "anymap" else ()), _stream())
+    e0 = _prof_begin(kind)
+    rc = getattr(_lib.load(), entry)(*args)
+    flops, nb = 2.0 * B * h * w * Cin * 4 * Ct, 2.0 * parts * (B * (h * w * Cin + Ho * Wo * Ct) + 4 * Cin * Ct)
     _prof_end(kind, flops if rc == 0 else 0.0, e0, nb if rc == 0 else 0.0)
     if rc < 0:
-        raise _lib.OnetHipError(f"onet_convT2x2_fwd_slots failed ({rc}): {_lib.last_error()}")
+        raise _lib.OnetHipError(f"{entry} failed ({rc}): {_lib.last_error()}")
     return rc == 0
 
 
-def convt_slots_ok_ragged(B, Cin, Ct, h, w, parts=1):
-    """convt_slots_ok(parts) without h w % 128 == 0: the predicate of onet_convT2x2_fwd_slots_ragged (parts = 1, the default) /
-    onet_convT2x2_fwd_slots_split_ragged (parts = 2: fp16 hi | mid operands) -- pixel tiles counted per image."""
-    return bool(CONVT_SLOTS and presplit() and (parts == 2 or CONVT_BF16) and Cin % 32 == 0 and Cin >= 128 and Ct % 32 == 0 and w % 2 == 0
-                and Cin * h * w * 2 * parts < 2 ** 31)
+# ---- the table's rows by name
+def convT2x2_fwd_slots(xP, wP, bias, outP, Ct, x_slots=None, slots=None, kind="convt_gemm_kernel"):
+    """The "full" rows, either format (parts from xP): the training forward's launch too, whose profile kind is the default here (the
+    fused eval plan records its launches under the device kernel's own name)"""
+    return eval_convt("fp16x2" if xP.shape[3] == 2 else "bf16", "full", xP, wP, bias, outP, Ct, x_slots, slots, kind)
 
 
 def convT2x2_fwd_slots_ragged(xP, wP, bias, outP, Ct, kind="convt_slot_fwd_kernel"):
     """convT2x2_fwd_slots on one-part bf16 slots whose map has h w % 128 != 0 (any map of even w qualifies): the pixels of the map,
-    value for value, as convT2x2_fwd_slots writes them on the map with zero rows appended.  -> False where the kernel does not take the
-    shape (nothing written)."""
-    B, C8, h, parts, w, _ = xP.shape
-    assert parts == 1 and outP.shape[3] == 1 and outP.shape[2] == 2 * h and outP.shape[4] == 2 * w and xP.dtype == wP.dtype == outP.dtype == BF
-    Cin = C8 * 8
-    e0 = _prof_begin(kind)
-    rc = _lib.load().onet_convT2x2_fwd_slots_ragged(_p(xP), _pbs(xP), _p(wP), _p(bias), _p(outP), _pbs(outP), B, Cin, Ct, h, w, _stream())
-    flops, nb = 2.0 * B * h * w * Cin * 4 * Ct, 2.0 * (B * h * w * (Cin + 4 * Ct) + 4 * Cin * Ct)
-    _prof_end(kind, flops if rc == 0 else 0.0, e0, nb if rc == 0 else 0.0)
-    if rc < 0:
-        raise _lib.OnetHipError(f"onet_convT2x2_fwd_slots_ragged failed ({rc}): {_lib.last_error()}")
-    return rc == 0
-
-
-def convt_slots_ok_anymap(B, Cin, Ct, h, w, Ho, Wo):
-    """convt_slots_ok_ragged (one part) without even w, into an output map of Ho x Wo: the predicate of onet_convT2x2_fwd_slots_anymap --
-    any w, Ho - 2h and Wo - 2w in {0, 1} (the concat map of a floor-pooled level)."""
-    return bool(CONVT_SLOTS and presplit() and CONVT_BF16 and Cin % 32 == 0 and Cin >= 128 and Ct % 32 == 0 and h > 0 and w > 0
-                and Ho - 2 * h in (0, 1) and Wo - 2 * w in (0, 1) and Cin * h * w * 2 < 2 ** 31)
+    value for value, as convT2x2_fwd_slots writes them on the map with zero rows appended."""
+    return eval_convt("bf16", "ragged", xP, wP, bias, outP, Ct, kind=kind)
 
 
 def convT2x2_fwd_slots_anymap(xP, wP, bias, outP, Ct, kind="convt_slot_fwd_kernel"):
-    """convT2x2_fwd_slots_ragged on one-part bf16 slots of a map of ANY w, into outP [B, Ct/8, Ho, 1, Wo, 8] with Ho - 2h, Wo - 2w in
-    {0, 1}: the up-sampled 2h x 2w block in the top-left corner, value for value what convT2x2_fwd_slots_ragged writes for those pixels,
-    and the pad strip (row 2h, column 2w) as zero slots, all in one launch.  -> False where the kernel does not take the shape (nothing
-    written)."""
-    B, C8, h, parts, w, _ = xP.shape
-    Ho, Wo = outP.shape[2], outP.shape[4]
-    assert parts == 1 and outP.shape[3] == 1 and outP.shape[1] * 8 == Ct and xP.dtype == wP.dtype == outP.dtype == BF
-    Cin = C8 * 8
-    e0 = _prof_begin(kind)
-    rc = _lib.load().onet_convT2x2_fwd_slots_anymap(_p(xP), _pbs(xP), _p(wP), _p(bias), _p(outP), _pbs(outP), B, Cin, Ct, h, w, Ho, Wo, _stream())
-    flops, nb = 2.0 * B * h * w * Cin * 4 * Ct, 2.0 * (B * (h * w * Cin + Ho * Wo * Ct) + 4 * Cin * Ct)
-    _prof_end(kind, flops if rc == 0 else 0.0, e0, nb if rc == 0 else 0.0)
-    if rc < 0:
-        raise _lib.OnetHipError(f"onet_convT2x2_fwd_slots_anymap failed ({rc}): {_lib.last_error()}")
-    return rc == 0
+    """convT2x2_fwd_slots_ragged on a map of ANY w, into outP [B, Ct/8, Ho, 1, Wo, 8] with Ho - 2h, Wo - 2w in {0, 1}: the 2h x 2w block
+    in the top-left corner, value for value what that function writes, and the pad strip (row 2h, column 2w) as zero slots, in one launch"""
+    return eval_convt("bf16", "anymap", xP, wP, bias, outP, Ct, kind=kind)
 
 
 def convT2x2_fwd_slots_split_ragged(xP, wP, bias, outP, Ct, x_slots=None, slots=None, kind="convt_slot_fwd_kernel"):
-    """convT2x2_fwd_slots on fp16 (hi | mid) slots whose map has h w % 128 != 0 (any map of even w qualifies; x_slots / slots: the
-    magnitude slots of input / output): the pixels of the map, value for value, as convT2x2_fwd_slots writes them on the map with zero
-    rows appended.  -> False where the kernel does not take the shape (nothing written)."""
-    B, C8, h, parts, w, _ = xP.shape
-    assert parts == 2 and outP.shape[3] == 2 and outP.shape[2] == 2 * h and outP.shape[4] == 2 * w
-    assert xP.dtype == wP.dtype == outP.dtype == torch.float16
-    Cin = C8 * 8
-    e0 = _prof_begin(kind)
-    rc = _lib.load().onet_convT2x2_fwd_slots_split_ragged(_p(xP), _pbs(xP), _p(x_slots), _p(wP), _p(bias), _p(outP), _pbs(outP), _p(slots), 2, B,
-                                                          Cin, Ct, h, w, _stream())
-    flops, nb = 2.0 * B * h * w * Cin * 4 * Ct, 4.0 * (B * h * w * (Cin + 4 * Ct) + 4 * Cin * Ct)
-    _prof_end(kind, flops if rc == 0 else 0.0, e0, nb if rc == 0 else 0.0)
-    if rc < 0:
-        raise _lib.OnetHipError(f"onet_convT2x2_fwd_slots_split_ragged failed ({rc}): {_lib.last_error()}")
-    return rc == 0
+    """convT2x2_fwd_slots_ragged on fp16 (hi | mid) slots (x_slots / slots: the magnitude slots of input / output)"""
+    return eval_convt("fp16x2", "ragged", xP, wP, bias, outP, Ct, x_slots, slots, kind)
 
 
 def convT2x2_fwd_p(x, wq, bias, outP, Ct, pt, pl, slots=None):
