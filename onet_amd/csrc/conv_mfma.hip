@@ -344,6 +344,12 @@ static int launch_fwd(ConvArgs a, hipStream_t st) {
     a.coTiles = cdiv(a.Cout, C::CO_T);
     const int64_t blocks = (int64_t)a.B * a.tilesX * a.tilesY * a.coTiles;
     ONET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "conv_fwd: grid %lld out of range", (long long)blocks);
+    // The kernel stages one image and the packed weights through 32-bit buffer resources (make_rsrc clamps the range at 2 GiB) with
+    // 32-bit byte offsets that run up to two K chunks past the last channel (the pipeline's look-ahead, zero-filled by the range
+    // check): beyond 2^31 bytes an element would silently read as zero or alias.  The output is addressed with 64-bit pointers.
+    const int64_t img = (MODE == 2) ? (int64_t)(a.Cin / 4 + 2 * CI_T) * a.Ho * a.Wo * 4 : (int64_t)(a.Cin + 2 * CI_T) * a.H * a.W * 4;
+    ONET_REQUIRE(img < (1ll << 31) && (int64_t)(a.Cin + 2 * CI_T) * C::TAPS * a.Cout * 4 < (1ll << 31),
+                 "conv_fwd: operand exceeds the 2 GiB buffer-resource range");
     auto kern = conv_fwd_kernel<KS, MT, NT, WM, WN, TW, MODE>;
     static PerDeviceOnce attr_once;
     if (attr_once.first()) {
@@ -354,36 +360,17 @@ static int launch_fwd(ConvArgs a, hipStream_t st) {
     return check_launch("conv_fwd_kernel");
 }
 
-// Tile configurations <MT, NT, WM, WN, TW> (per-wave register tile MT x NT of 32x32 MFMA tiles,
-// 4 waves as WM x WN, TW-pixel-wide column tiles):
-//   P  <2,4,1,4,32>   64 co x (16 rows x 32 px)   pixel-heavy, single-level accumulation
-//   C  <2,4,2,2,32>  128 co x ( 8 rows x 32 px)   channel-heavy, single-level accumulation
-//   D  <2,2,1,4,TW>   64 co x ( 8 rows x 32 px | 16 rows x 16 px)   two-level accumulation
-//   E  <2,2,2,2,32>  128 co x ( 4 rows x 32 px)   two-level accumulation
-// ONET_CONV_CFG=P|C|D|E forces one (tuning / A-B runs); default: heuristic below.
-static int conv_cfg_override() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("ONET_CONV_CFG");
-        v = (e && e[0]) ? e[0] : 0;
-    }
-    return v;
-}
-
+// The one tile configuration <MT, NT, WM, WN, TW> = <2,2,1,4,TW> (per-wave register tile MT x NT of 32x32 MFMA tiles,
+// 4 waves as WM x WN, TW-pixel-wide column tiles): 64 co x (8 rows x 32 px | 16 rows x 16 px), two-level accumulation.
+// Measured on MI355X (tools/bench_conv.py, B=32, 256^2 U-Net layer shapes, fwd+dgrad) against the three alternatives
+// that used to be compiled beside it: <2,4,1,4,32> (single-level) 138.6, this one 134.6, <2,4,2,2,32> 115-124,
+// <2,2,2,2,32> 109-118 TFLOP/s.  It is within 3 % of the fastest and carries the two-level accumulation that keeps
+// |z - exact| ~2e-7 of the output scale on the model's data (fewer ReLU-kink sign flips against the reference).  The suite's bound is
+// per element and wider, 64 u conv(|x|, |w|) (tests/conv_refs.py: set by an outlier in a 64-channel chain); what it holds the fold to
+// is test_direct_fwd_dgrad[fold-*]: one-signed operands at Cin = 1024 and 4096, where a single chain of 9 Cin terms leaves that bound.
 template <int KS>
 static int dispatch_fwd(const ConvArgs& a, hipStream_t st) {
-    const bool wide = a.W > 16;
-    if (!wide) return launch_fwd<KS, 2, 2, 1, 4, 16>(a, st);
-    switch (conv_cfg_override()) {
-        case 'P': return launch_fwd<KS, 2, 4, 1, 4, 32>(a, st);
-        case 'C': return launch_fwd<KS, 2, 4, 2, 2, 32>(a, st);
-        case 'D': return launch_fwd<KS, 2, 2, 1, 4, 32>(a, st);
-        case 'E': return launch_fwd<KS, 2, 2, 2, 2, 32>(a, st);
-        default: break;
-    }
-    // Measured on MI355X (tools/bench_conv.py, B=32, 256^2 U-Net layer shapes, fwd+dgrad): P 138.6, D 134.6,
-    // C 115-124, E 109-118 TFLOP/s.  D is the default: within 3 % of P and it carries the two-level
-    // accumulation that keeps |z - exact| ~2e-7 (fewer ReLU-kink sign flips against the reference).
+    if (a.W <= 16) return launch_fwd<KS, 2, 2, 1, 4, 16>(a, st);
     return launch_fwd<KS, 2, 2, 1, 4, 32>(a, st);
 }
 
@@ -770,6 +757,13 @@ static void launch_wgrad(const WgArgs& a, int64_t blocks, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256 * KS), C::LDS_BYTES, st, a);
 }
 
+// conv_wgrad_kernel stages one image of x and of dz through 32-bit buffer resources with 32-bit byte offsets that run to the end of
+// the last 64-channel tile: beyond 2^31 bytes an element would silently read as zero or alias.  dz: dz_ch planes of dz_plane floats
+// (Cout of H W; the ConvTranspose2d fallback gathers from Ct planes of Ho Wo).
+static inline bool wgrad_in_range(int Cin, int H, int W, int64_t dz_ch, int64_t dz_plane) {
+    return (int64_t)(Cin + 64) * H * W * 4 < (1ll << 31) && (dz_ch + 64) * dz_plane * 4 < (1ll << 31);
+}
+
 static void wgrad_plan(int B, int Cin, int Cout, int H, int W, int ks, int& pw, int& splitK,
                        int& stripsX, int& stripsY) {
     pw = (W > 16) ? 32 : 16;
@@ -973,6 +967,7 @@ int onet_conv_wgrad(const float* x, int64_t x_bs, const float* dz, int64_t dz_bs
                            (const float*)ws, dw, nb, 9, Cout, Cin, 0, accumulate);
         return check_launch("wgrad_reduce_kernel");
     }
+    ONET_REQUIRE(wgrad_in_range(Cin, H, W, Cout, (int64_t)H * W), "conv_wgrad: image exceeds the 2 GiB buffer-resource range");
     int pw;
     wgrad_plan(B, Cin, Cout, H, W, ks, pw, a.splitK, a.stripsX, a.stripsY);
     const int64_t need = (int64_t)a.splitK * ks * ks * Cout * Cin * 4;
@@ -1005,6 +1000,7 @@ int onet_convT2x2_wgrad(const float* x, int64_t x_bs, const float* dy, int64_t d
         if (rc <= 0) return rc;
     }
     const int Cout = 4 * Ct;
+    ONET_REQUIRE(wgrad_in_range(Cin, h, w, Ct, (int64_t)Ho * Wo), "convT2x2_wgrad: image exceeds the 2 GiB buffer-resource range");
     WgArgs a{x, x_bs, dy, dy_bs, (float*)ws, B, Cin, Cout, h, w, cdiv(Cin, 64), cdiv(Cout, 64), 1, 1, 1, Ct, Ho, Wo, pt, pl};
     int pw;
     wgrad_plan(B, Cin, Cout, h, w, 1, pw, a.splitK, a.stripsX, a.stripsY);

@@ -903,6 +903,15 @@ def _in_buffer_range(Cin, Cout, H, W):
     return (2 * max(Cin, Cout) + 16) * H * W * 4 < 2 ** 31 and (max(Cin, Cout) + 16) * 36 * (max(Cin, Cout) + 63) * 4 < 2 ** 31
 
 
+def _direct_in_range(Cin, Cout, H, W):
+    """The direct fp32-MFMA kernels also stage one image and the packed weight through a 32-bit buffer resource with 32-bit byte
+    offsets.  This is the range of ONE launch, the convolution Cin -> Cout that the dispatch is asked about (launch_fwd of
+    conv_mfma.hip, the same arithmetic; the input gradient asks with the channels swapped).  The weight gradient's range is narrower --
+    (max(Cin, Cout) + 64) H W 4 bytes, a whole 64-channel tile of look-ahead -- and is not checked here, because inference never
+    runs it: a layer between the two is dispatched, and its backward is refused by onet_conv_wgrad's own check (OnetHipError)."""
+    return (Cin + 16) * H * W * 4 < 2 ** 31 and (Cin + 16) * 9 * Cout * 4 < 2 ** 31
+
+
 def _split_legal(Cin, Cout, H, W):
     return Cin % 16 == 0 and W > 16 and W % 4 == 0 and H >= 8
 
@@ -910,8 +919,13 @@ def _split_legal(Cin, Cout, H, W):
 def conv3x3_algo(B, Cin, Cout, H, W):
     """-> "split" | "winograd4" | "direct" | "bf16" for a conv with Cin inputs and Cout outputs on B maps of H x W."""
     algo = conv_algo()
+    if not _direct_in_range(Cin, Cout, H, W):
+        raise ValueError("conv3x3: one image of %d channels on a %d x %d map (or its packed weight) exceeds the 2 GiB buffer-resource "
+                         "range of every convolution kernel; tile the map" % (Cin, H, W))
     if algo in ("bf16", "winograd4", "auto", "split") and not _in_buffer_range(Cin, Cout, H, W):
-        algo = "direct"               # (operands beyond the 2 GiB buffer-resource range: the direct kernel addresses with 64-bit pointers)
+        # between the two ranges: _in_buffer_range allows for a concat buffer of twice the channels, the direct kernel
+        # (onet_conv_fwd / onet_conv_wgrad, which check their own range) addresses one image of exactly Cin channels
+        algo = "direct"
     if algo == "split":
         if _split_legal(Cin, Cout, H, W):
             return "split"
