@@ -8,6 +8,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from .handoff import Pooled, UnitIO
 
 
 def _carries_settings(cls):
@@ -57,33 +58,30 @@ class ConvBNReLUFn(torch.autograd.Function):
     forward : conv (MFMA; the F(4x4) kernel also emits the BN statistics records) -> finalize -> normalise+ReLU
     backward: BN+ReLU backward (reduce + apply) -> wgrad (MFMA split-K) -> dgrad (MFMA)
 
-    `link_out` / `link_in`: the dict DoubleConv shares between its two units.  The first unit publishes its
-    pre-activation and BN coefficients in it; the second unit's backward then folds the first unit's BN-backward reduce
-    pass into its own dgrad launch (whose output IS the first unit's `da`) and leaves the records in the dict."""
+    `link_out` / `link_in`: the UnitLink records (handoff.py) towards the consumer of this unit's activation and from the unit
+    below; `io`: the unit's UnitIO."""
 
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, running_mean, running_var, training, momentum, eps, packed, out, groups=1,
-                link_out=None, link_in=None, aux=None, p16=None):
+                link_out=None, link_in=None, io=None):
         ops.require_gpu(x, weight, gamma, beta)
-        if p16 is not None and (p16.get("x") is not None or p16.get("want")):
+        if io is None:
+            io = UnitIO()
+        if io.pre_split:
             return ConvBNReLUFn._forward_pre(ctx, x, weight, gamma, beta, running_mean, running_var, training, momentum, eps, packed,
-                                             groups, link_out, link_in, p16, aux)
-        ctx.pre = False
-        # an encoder output that is max-pooled next: a request left in the link dict by UNet.forward (read before the dict is refilled
-        # below); the pooled tensor goes back through the same dict for SkipPoolFn
-        want_pool = link_out.pop("want_pool", None) if link_out is not None else None
-        # normalise on load (ops.norm_on_load_ok, decided by DoubleConv for the pair): as the FIRST unit, this launch computes
-        # z and the BatchNorm coefficients and stops there -- the second unit's convolution applies BatchNorm + ReLU in its own
-        # operand staging, forward and weight gradient, and a placeholder stands in for the activation in the graph; as the
-        # SECOND unit, x is that placeholder and the operand comes from (z, save) of the first
-        defer = bool(link_out.pop("defer", False)) if link_out is not None else False
+                                             groups, link_out, link_in, io)
+        # want_pool: an encoder output that is max-pooled next (asked for by UNet._forward; the pooled tensor goes back through the
+        # link for SkipPoolFn).  defer: normalise on load (ops.norm_on_load_ok, decided by DoubleConv for the pair): as the FIRST
+        # unit, this launch computes z and the BatchNorm coefficients and stops there -- the second unit's convolution applies
+        # BatchNorm + ReLU in its own operand staging, forward and weight gradient, and a placeholder stands in for the activation
+        # in the graph; as the SECOND unit, x is that placeholder and the operand comes from (z, save) of the first
+        want_pool, defer = link_out.take_requests() if link_out is not None else (None, False)
         defer = defer and training and out is None and want_pool is None
         norm = None
-        if link_in is not None and link_in.get("deferred"):
-            norm = (link_in["z"], link_in["save"], link_in.get("slots"))
+        if link_in is not None and link_in.deferred:
+            norm = (link_in.z, link_in.save, link_in.slots)
         # the magnitude slots x's producer left on it (ops.tag_amax): the fp16-split kernel's overflow guard
-        # (aux: {"x_amax": slots of x or None} in, {"a_amax": slots of the output} out -- DoubleConv._unit tags the tensors)
-        x_amax = aux.get("x_amax") if (aux is not None and norm is None) else None
+        x_amax = io.x_amax if norm is None else None
         # training: the F(4x4) kernel emits the BatchNorm statistics records from its epilogue (cm), where it can
         if norm is not None:
             z, cm = ops.conv3x3_fwd_bn_partials(None, packed, norm=norm)
@@ -102,7 +100,7 @@ class ConvBNReLUFn(torch.autograd.Function):
                                             and ops.conv_algo() in ("auto", "split", "bf16")) else None
         act_slots = ops.new_amax(z.device) if (defer and ops.split_f16()) else None
         if want_pool is not None and ops.FUSE_POOL and Hz % 2 == 0 and Wz % 4 == 0:
-            pooled = (torch.empty((Bz, C, Hz // 2, Wz // 2), dtype=torch.float32, device=z.device), None)
+            pooled = Pooled(y=torch.empty((Bz, C, Hz // 2, Wz // 2), dtype=torch.float32, device=z.device))
 
         def apply(zg, sv, o, sl):
             """BatchNorm + ReLU of one statistics group (batch slice sl), with the pooled output where it was asked for"""
@@ -112,7 +110,7 @@ class ConvBNReLUFn(torch.autograd.Function):
             if pooled is not None:
                 if o is None:
                     o = torch.empty_like(zg)
-                if ops.bn_relu_apply_pool(zg, sv, o, pooled[0][sl], amax=a_amax):
+                if ops.bn_relu_apply_pool(zg, sv, o, pooled.y[sl], amax=a_amax):
                     return o
                 pooled = None                       # shape not taken: the separate pooling pass runs as before
             return ops.bn_relu_apply(zg, sv, out=o, amax=a_amax)
@@ -138,64 +136,61 @@ class ConvBNReLUFn(torch.autograd.Function):
                 ops.bn_train_coeffs(zg, gamma, beta, running_mean, running_var, momentum, eps,
                                     cm=None if cm is None else (cm, g * npg, npg), save=save_all[g], act_slots=act_slots)
                 apply(zg, save_all[g], None if defer else a[g * Bg:(g + 1) * Bg], slice(g * Bg, (g + 1) * Bg))
-        if aux is not None:
-            aux["a_amax"] = a_amax
+        io.a_amax = a_amax
+        ConvBNReLUFn._finish_forward(ctx, False, x, weight, gamma, beta, training, packed, z, save_all,
+                                     (None, None) if norm is None else norm[:2], link_out, link_in, pooled, defer, act_slots)
+        return a
+
+    @staticmethod
+    def _finish_forward(ctx, pre, x, weight, gamma, beta, training, packed, z, save_all, saved, link_out, link_in, pooled,
+                        deferred=False, slots=None):
+        """The common end of forward and _forward_pre: what backward needs goes on the node (`saved`: the branch's own saved tensors,
+        between (x, z, save_all) and the unit below's (z, save), which leave their link here: UnitLink.take_below), and the links are
+        refilled for this unit's consumers."""
+        ctx.pre = pre
         ctx.twin = ops.twin_src_of(x)       # a virtual twin batch (placeholder + (X, bias)): backward re-attaches the tag
-        # the unit below's (z, save) leave the dict here and become saved tensors of this node: every backward through the graph
-        # (retain_graph) finds them, and they are freed with the graph's other saved tensors -- the dict lives as long as the caller
-        # holds the loss tensor, i.e. into the next step, and must not keep a whole set of pre-activations alive
-        below = (link_in.pop("z"), link_in.pop("save")) if (training and link_in is not None and "z" in link_in) else (None, None)
-        ctx.save_for_backward(x, z, save_all, None if norm is None else norm[0], None if norm is None else norm[1], *below)
+        below = link_in.take_below() if (training and link_in is not None) else (None, None)
+        ctx.save_for_backward(x, z, save_all, *saved, *below)
         ctx.training = training
         ctx.packed = packed
         ctx.wshape = tuple(weight.shape)
         _record_versions(ctx, weight, gamma, beta)  # (also for ops.grad_slot_if_free in backward)
         ctx.link_out = ctx.link_in = None
         if training and link_out is not None:
-            link_out.clear()
-            link_out.update(z=z, save=save_all)
-            if defer:
-                link_out["deferred"] = True
-                link_out["slots"] = act_slots
+            link_out.publish(z, save_all, deferred, slots)
             ctx.link_out = link_out
         if below[0] is not None:
             ctx.link_in = link_in
         if pooled is not None and link_out is not None:
-            link_out["pooled"] = pooled
-        return a
+            link_out.pooled = pooled
 
     @staticmethod
     def _forward_pre(ctx, x, weight, gamma, beta, running_mean, running_var, training, momentum, eps, packed, groups, link_out,
-                     link_in, p16, aux=None):
-        """Pre-split storage (Settings.presplit).  p16 in: "x" = the pre-split form of x (then the convolution, its input gradient
-        and weight gradient run on pre-split operands, ops.pre_layer_ok) or None; "want": write the output activation pre-split
-        ("out": its destination, e.g. the skip groups of a concat buffer; else allocated); "keep_fp32": write the fp32 activation too
-        (it has fp32 readers); with a pooling request in link_out (UNet.forward: {"p16": the pooled tensor is wanted pre-split}).
-        p16 out: "a" = the pre-split output.  The graph carries placeholders where no fp32 tensor exists."""
-        want_pool = link_out.pop("want_pool", None) if link_out is not None else None
-        if link_out is not None:
-            link_out.pop("defer", None)
-        xP = p16.get("x")
-        x_slots = p16.get("x_slots") if xP is not None else None
+                     link_in, io):
+        """Pre-split storage (Settings.presplit): see UnitIO; a pooling request in link_out says whether the pooled tensor is wanted
+        pre-split.  The graph carries placeholders where no fp32 tensor exists."""
+        want_pool, _ = link_out.take_requests() if link_out is not None else (None, False)
+        xP = io.xP
+        x_slots = io.x_slots if xP is not None else None
         if xP is not None:
             z, cm = ops.conv3x3_pre_bn_partials(xP, packed, x_slots)
         else:       # (an fp32 x: the magnitude slots its producer left on it, as in forward)
-            x_amax = aux.get("x_amax") if aux is not None else None
+            x_amax = io.x_amax
             z, cm = ops.conv3x3_fwd_bn_partials(x, packed, amax=x_amax) if training else (ops.conv3x3_auto(x, packed, 0, amax=x_amax), None)
         G = groups if (training and groups > 1) else 1
         Bz, C, Hz, Wz = z.shape
         Bg = Bz // G
         save_all = torch.empty((G, 4, C), dtype=torch.float32, device=z.device)
-        want = bool(p16.get("want"))
-        keep = bool(p16.get("keep_fp32")) or not want or ops.PRESPLIT_KEEP_FP32
+        want = bool(io.want)
+        keep = bool(io.keep_fp32) or not want or ops.PRESPLIT_KEEP_FP32
         aP = None
         if want:
-            aP = p16.get("out")
+            aP = io.out
             if aP is None:
                 aP = ops.p16_empty(Bz, C, Hz, Wz, z.device)
         # the network's last unit (round 5): its activation has ONE reader, the head, which forms relu(bn(z)) on load from z and the
         # coefficients -- no activation tensor, no BatchNorm + ReLU pass (a placeholder goes through the graph)
-        head = p16.get("head_link")
+        head = io.head_link
         defer_head = bool(head is not None and training and G == 2 and not want and want_pool is None and z.dtype == torch.float32
                           and ops.HEAD_NORM and not ops.PRESPLIT_KEEP_FP32)
         a = torch.empty(z.shape, dtype=torch.float32, device=z.device) if (keep and not defer_head) else ops.fp32_placeholder(z.shape, z.device)      # (z may be stored as bf16)
@@ -207,10 +202,10 @@ class ConvBNReLUFn(torch.autograd.Function):
         a_amax = ops.new_amax(z.device) if (not want and parts2) else None
         pooled = None
         if want_pool is not None and Hz % 2 == 0 and Wz % 2 == 0:
-            if want_pool.get("p16"):
-                pooled = (None, None, ops.p16_empty(Bz, C, Hz // 2, Wz // 2, z.device))
+            if want_pool.p16:
+                pooled = Pooled(yP=ops.p16_empty(Bz, C, Hz // 2, Wz // 2, z.device), pre=True)
             else:
-                pooled = (torch.empty((Bz, C, Hz // 2, Wz // 2), dtype=torch.float32, device=z.device), None, None)
+                pooled = Pooled(y=torch.empty((Bz, C, Hz // 2, Wz // 2), dtype=torch.float32, device=z.device), pre=True)
         # the statistics groups of a twin batch (consecutive batch slices) go through every pass in ONE launch: the kernels pick a
         # group's coefficients from save_all [G][4][C] by image index
         if training and cm is not None:
@@ -225,43 +220,25 @@ class ConvBNReLUFn(torch.autograd.Function):
                     ops.bn_eval_coeffs(gamma, beta, running_mean, running_var, eps, save=save_all[g])
         gi = Bg if G > 1 else 0
         if defer_head:
-            head["z"], head["save"] = z, save_all
             # (the head's backward may then keep dH = g L unwritten and hand this unit the reduce records instead: _backward_pre takes
             # that hand-off only on its pre-split branch)
-            head["bwd_fuse"] = xP is not None
+            head.z, head.save, head.bwd_fuse = z, save_all, xP is not None
             a_amax = None
         elif pooled is not None:
-            if not ops.bn_relu_apply_pool_split(z, save_all, aP, a if keep else None, pooled[2], pooled[0], slots=act_slots, group_images=gi):
+            if not ops.bn_relu_apply_pool_split(z, save_all, aP, a if keep else None, pooled.yP, pooled.y, slots=act_slots, group_images=gi):
                 raise RuntimeError("onet_amd: pre-split BatchNorm + pooling pass refused a shape ops.pre_layer_ok accepted")
         elif aP is not None:
             ops.bn_relu_apply_split(z, save_all, aP, a=a if keep else None, slots=act_slots, group_images=gi)
         else:
             ops.bn_relu_apply(z, save_all, out=a, amax=a_amax, group_images=gi)
-        p16["a"], p16["a_slots"], p16["a_amax"] = aP, act_slots, a_amax
+        io.aP, io.a_slots, io.a_amax = aP, act_slots, a_amax
         ctx.x_slots = x_slots
         # (first convolution of a decoder block: see UpConvTCatFn -- the up-sampled half of dx leaves pre-split.  The request is kept on
-        # this node, not taken from the dict in backward: every backward through a retained graph makes the same hand-off)
-        ctx.up_link = p16.get("up_link")
-        ctx.up_want = None if ctx.up_link is None else ctx.up_link.get("want")
-        ctx.twin = ops.twin_src_of(x)       # a virtual twin batch (placeholder + (X, bias)): backward re-attaches the tag
+        # this node, not read from the link in backward: every backward through a retained graph makes the same hand-off)
+        ctx.up_link = io.up_link
+        ctx.up_want = None if ctx.up_link is None else ctx.up_link.want
         ctx.head_link = head if defer_head else None      # (every backward of the head publishes in it anew: kept on this node)
-        # the unit below's (z, save): saved tensors of this node (see ConvBNReLUFn.forward)
-        below = (link_in.pop("z"), link_in.pop("save")) if (training and link_in is not None and "z" in link_in) else (None, None)
-        ctx.save_for_backward(x, z, save_all, xP, *below)
-        ctx.pre = True
-        ctx.training = training
-        ctx.packed = packed
-        ctx.wshape = tuple(weight.shape)
-        _record_versions(ctx, weight, gamma, beta)
-        ctx.link_out = ctx.link_in = None
-        if training and link_out is not None:
-            link_out.clear()
-            link_out.update(z=z, save=save_all)
-            ctx.link_out = link_out
-        if below[0] is not None:
-            ctx.link_in = link_in
-        if pooled is not None and link_out is not None:
-            link_out["pooled"] = pooled
+        ConvBNReLUFn._finish_forward(ctx, True, x, weight, gamma, beta, training, packed, z, save_all, (xP,), link_out, link_in, pooled)
         return a
 
     @staticmethod
@@ -274,17 +251,9 @@ class ConvBNReLUFn(torch.autograd.Function):
 
     @staticmethod
     def _take_head_handoff(link, da):
-        """What the fused head backward (HeadSoftmaxTwinFn.backward) left for the network's last unit: (rec4, da_amax, (g, L)) or None.
-        The unit's da = g L then exists nowhere, so `da` must be the placeholder the head returned for it -- under the identity check
-        of the other hand-offs; anything else (the activation got a second consumer, whose gradient autograd added) is refused: there
-        is no tensor to fall back on."""
-        if link is None or "gl" not in link:
-            return None
-        rda, rec4, da_amax, gl = link.pop("da"), link.pop("rec4"), link.pop("da_amax", None), link.pop("gl")
-        if not ops.is_placeholder(da) or rda.data_ptr() != da.data_ptr() or rda.shape != da.shape or rda.stride() != da.stride():
-            raise RuntimeError("onet_amd: the head kept the gradient of the last activation unwritten, but autograd handed its unit "
-                               "another tensor (a second consumer of that activation?)")
-        return rec4, da_amax, gl
+        """What the fused head backward (HeadSoftmaxTwinFn.backward) left in the HeadLink for the network's last unit, or None: the
+        unit's da = g L then exists nowhere, so `da` must be the placeholder the head returned for it (a strict take)."""
+        return None if link is None else link.grad.take(da, strict=True)
 
     @staticmethod
     def _backward_pre(ctx, da):
@@ -294,20 +263,13 @@ class ConvBNReLUFn(torch.autograd.Function):
         _check_versions(ctx, (True, True, False))    # (as torch: conv2d saves the weight, batch_norm gamma, neither beta)
         pw, pg, pb = ctx.params
         aff = (ops.grad_slot_if_free(pg) if need_g else None, ops.grad_slot_if_free(pb) if need_b else None)
-        rec4, da_amax = None, None
-        lk = ctx.link_out
-        if lk is not None and "rec4" in lk:
-            rda, rec4, da_amax = lk.pop("da"), lk.pop("rec4", None), lk.pop("da_amax", None)
-            lk.pop("rec", None)
-            if rda.data_ptr() != da.data_ptr() or rda.shape != da.shape or rda.stride() != da.stride():
-                rec4 = da_amax = None
-        # the network's last unit behind the fused head backward: da = g L was never written (`da` is its placeholder); the records
-        # and max |da| came with (g, L), from which the apply pass forms it
-        da_gl = None
-        hand = ConvBNReLUFn._take_head_handoff(getattr(ctx, "head_link", None), da)
-        if hand is not None:
-            rec4, da_amax, da_gl = hand
-        nones = (None,) * 12
+        # the reduce records of THIS layer (and max |da|), if the consumer above wrote them while producing exactly this `da`.  The
+        # network's last unit behind the fused head backward: da = g L was never written (`da` is its placeholder); the records and
+        # max |da| came with (g, L), from which the apply pass forms it
+        hand = None if ctx.link_out is None else ctx.link_out.grad.take(da)
+        hand = ConvBNReLUFn._take_head_handoff(ctx.head_link, da) or hand
+        rec4, da_amax, da_gl = (None, None, None) if hand is None else (hand.rec4, hand.da_amax, hand.gl)
+        nones = (None,) * 11
         if xP is None:
             # fp32 input (the stem): dz in fp32 for the fp32-input kernels; no input gradient path on pre-split operands
             if need_w and not need_x and x.shape[1] <= 4 and ops.STEM_WGRAD_BN and (not ops.is_placeholder(x) or ops.twin_src_of(x) is not None):
@@ -328,15 +290,13 @@ class ConvBNReLUFn(torch.autograd.Function):
         dx = None
         if need_x and z_below is not None and save_below is not None and ctx.training:
             # the unit below's BatchNorm-backward reduce rides in this launch's epilogue (its da IS this dx): the records (and max |da|)
-            # go back through the shared dict, where that unit's backward looks for them
+            # go back through the shared link, where that unit's backward looks for them
             fused = ops.conv3x3_split_dgrad_pre_bnreduce(dzP, dpack, ctx.wshape[1], z_below, save_below, slots=dz_slots,
                                                          always=dz_slots is not None, want_amax=ops.p16_parts() == 2)
             if fused is not None:
                 dx, rec_below, am_below = fused
-                ctx.link_in["da"], ctx.link_in["rec4"] = dx, rec_below
-                if am_below is not None:
-                    ctx.link_in["da_amax"] = am_below
-        up = getattr(ctx, "up_link", None)
+                ctx.link_in.grad.publish(dx, rec4=rec_below, da_amax=am_below)
+        up = ctx.up_link
         if need_x and dx is None and up is not None and ctx.up_want and (dz_slots is not None or dzP.shape[3] == 1):
             # the input of this convolution is a concat buffer whose up-sampled half came out of a ConvTranspose2d: that half of dx is
             # read only by the ConvTranspose2d backward GEMMs, and leaves this launch in THEIR operand form (fp16 hi | mid slots scaled by
@@ -344,7 +304,7 @@ class ConvBNReLUFn(torch.autograd.Function):
             C2, Ct = ctx.up_want
             bound = ops.conv3x3_dgrad_bound(pw, dz_slots, C2) if dzP.shape[3] == 2 else None      # (plain bf16 parts are not scaled)
             dx, dyP = ops.conv3x3_split_dgrad_pre_slots(dzP, dpack, ctx.wshape[1], C2, bound, slots=dz_slots, always=dz_slots is not None)
-            up["dyP"], up["dy_slots"], up["da"] = dyP, bound, dx
+            up.publish(dyP, bound, dx)
         if need_x and dx is None:
             dx = ops.conv3x3_split_pre(dzP, dpack, ctx.wshape[1], slots=dz_slots, always=dz_slots is not None)
         return (dx, dw, (dgamma if need_g else None), (dbeta if need_b else None)) + nones
@@ -360,13 +320,9 @@ class ConvBNReLUFn(torch.autograd.Function):
         pw, pg, pb = ctx.params
         aff = (ops.grad_slot_if_free(pg) if need_g else None, ops.grad_slot_if_free(pb) if need_b else None)
         G = save_all.shape[0]
-        # the reduce records of THIS layer, if the unit above wrote them while producing exactly this `da`
-        rec = rec4 = None
-        lk = ctx.link_out
-        if lk is not None and ("rec" in lk or "rec4" in lk):
-            rda, rec, rec4 = lk.pop("da"), lk.pop("rec", None), lk.pop("rec4", None)
-            if rda.data_ptr() != da.data_ptr() or rda.shape != da.shape or rda.stride() != da.stride():
-                rec = rec4 = None                   # autograd handed over something else (another consumer, a hook)
+        # the reduce records of THIS layer, if the consumer above wrote them while producing exactly this `da`
+        hand = None if ctx.link_out is None else ctx.link_out.grad.take(da)
+        rec, rec4 = (None, None) if hand is None else (hand.rec, hand.rec4)
         Bz, Cz, Hz, Wz = z.shape
         # fp16-split gradient kernels (Settings.grad_f16): the BatchNorm backward records max |dz| on its way out, and the input- and
         # weight-gradient kernels that consume dz scale it by a power of two chosen from that before splitting it into fp16 parts
@@ -401,10 +357,10 @@ class ConvBNReLUFn(torch.autograd.Function):
                 fused = ops.conv3x3_dgrad_bnreduce(dz, ctx.packed, z_below, save_below)
             if fused is not None:
                 dx, r = fused
-                lk["da"], lk["rec"] = dx, r
+                lk.grad.publish(dx, rec=r)
             else:
                 dx = ops.conv3x3_auto(dz, ctx.packed, 1, amax=dz_amax)
-        return (dx, dw, (dgamma if need_g else None), (dbeta if need_b else None)) + (None,) * 12
+        return (dx, dw, (dgamma if need_g else None), (dbeta if need_b else None)) + (None,) * 11
 
 
 @_carries_settings
@@ -475,28 +431,26 @@ class SkipPoolFn(torch.autograd.Function):
     """x -> (x, maxpool2(x)[, x]) for an encoder output that feeds both the next Down (OV:67) and an Up's skip concat
     (OV:100) -- and, for the first one, also leaves the U-Net as its first output (OV:152): backward sums the two or
     three gradients inside the pooling-backward kernel (one pass instead of pool backward + autograd's full-tensor
-    adds).  `link`: the dict the producing Conv-BN-ReLU unit published its (z, save) in; the sum written here IS that
+    adds).  `link`: the UnitLink the producing Conv-BN-ReLU unit published its (z, save) in; the sum written here IS that
     unit's activation gradient, so its BatchNorm-backward reduce records are taken in the same kernel and left in the
-    dict for the unit's backward."""
+    link for the unit's backward."""
 
     @staticmethod
-    def forward(ctx, x, returned=False, link=None, carry=None):
-        """carry: a dict that takes the pooled tensor's pre-split form back to the caller ("yP"), where its producer wrote one."""
+    def forward(ctx, x, returned=False, link=None):
         ops.require_gpu(x)
-        pooled = link.pop("pooled", None) if link is not None else None
-        if pooled is not None and len(pooled) == 3:
-            # pre-split storage: the producing pass wrote the pooled tensor pre-split (pooled[2]) or in fp32 (pooled[0])
+        pooled = link.take_pooled() if link is not None else None
+        if pooled is not None and pooled.pre:
+            # pre-split storage: the producing pass wrote the pooled tensor pre-split (pooled.yP: the caller has read it from the link
+            # and tags the placeholder with it) or in fp32 (pooled.y)
             shp = (x.shape[0], x.shape[1], x.shape[2] // 2, x.shape[3] // 2)
-            y = pooled[0] if pooled[0] is not None else ops.fp32_placeholder(shp, x.device)
-            if carry is not None:
-                carry["yP"] = pooled[2]
+            y = pooled.y if pooled.y is not None else ops.fp32_placeholder(shp, x.device)
             ctx.pre = True
-        elif pooled is not None and pooled[0] is not None and tuple(pooled[0].shape) == (x.shape[0], x.shape[1], x.shape[2] // 2, x.shape[3] // 2):
-            y = pooled[0]                   # the producing BatchNorm + ReLU pass already wrote the pooled tensor (onet_bn_relu_apply_pool)
+        elif pooled is not None and pooled.y is not None and tuple(pooled.y.shape) == (x.shape[0], x.shape[1], x.shape[2] // 2, x.shape[3] // 2):
+            y = pooled.y                    # the producing BatchNorm + ReLU pass already wrote the pooled tensor (onet_bn_relu_apply_pool)
         else:
             y = ops.maxpool2_fwd(x)
-        # the producing unit's (z, save): saved tensors of this node (see ConvBNReLUFn.forward)
-        below = (link.pop("z"), link.pop("save")) if (link is not None and "z" in link) else (None, None)
+        # the producing unit's (z, save): saved tensors of this node (UnitLink.take_below)
+        below = link.take_below() if link is not None else (None, None)
         ctx.save_for_backward(x, *below)
         ctx.link = link if below[0] is not None else None
         return (x.view_as(x), y, x.view_as(x)) if returned else (x.view_as(x), y)
@@ -506,17 +460,15 @@ class SkipPoolFn(torch.autograd.Function):
         x, z, save = ctx.saved_tensors
         if g_pool is None:
             gs = [g for g in (g_skip, g_ret) if g is not None]
-            return (sum(gs[1:], gs[0]) if gs else None), None, None, None
+            return (sum(gs[1:], gs[0]) if gs else None), None, None
         lk = ctx.link
         if lk is not None:
             am = ops.new_amax(g_pool.device) if (getattr(ctx, "pre", False) and ops.p16_parts() == 2) else None
             dx, part2 = ops.maxpool2_bwd(x, g_pool, add=g_skip, add2=g_ret, bn=(z, save), dx_amax=am)
             if part2 is not None:
-                lk["da"], lk["rec4"] = dx, part2
-                if am is not None:
-                    lk["da_amax"] = am
-            return dx, None, None, None
-        return ops.maxpool2_bwd(x, g_pool, add=g_skip, add2=g_ret), None, None, None
+                lk.grad.publish(dx, rec4=part2, da_amax=am)
+            return dx, None, None
+        return ops.maxpool2_bwd(x, g_pool, add=g_skip, add2=g_ret), None, None
 
 
 def _pad_offsets(x1_hw, x2_hw):
@@ -537,8 +489,8 @@ class UpConvTCatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x1, x2, weight, bias, packed, cat_holder=None, p16=None):
-        """p16 (pre-split storage): {"catP": the pre-split concat buffer, skip groups written by the encoder}: the up-sampled groups
-        are written here and NO fp32 concat exists (a placeholder goes through the graph)."""
+        """p16 (pre-split storage): a ConcatIO; the up-sampled groups of its concat buffer are written here and NO fp32 concat exists
+        (a placeholder goes through the graph)."""
         ops.require_gpu(x1, x2, weight, bias)
         wp_fused, wp_dgrad = packed               # (ops.PackedT hands out lazy handles: a classic fp32 pack is made only if it is used)
         B, Cin, h, w = x1.shape
@@ -546,34 +498,34 @@ class UpConvTCatFn(torch.autograd.Function):
         C2, Ho, Wo = x2.shape[1], x2.shape[2], x2.shape[3]
         pt, pl = _pad_offsets((h, w), (Ho, Wo))
         if p16 is not None:
-            catP = p16["catP"]
+            catP = p16.catP
             assert (Ho, Wo) == (2 * h, 2 * w) and catP.shape[1] * 8 == C2 + Ct and C2 % 8 == 0
             # round 5: x1 pre-split by its producer and the weights in slot form -- both GEMM operands are LDS-DMA copies
-            x1P = p16.get("x1P")
+            x1P = p16.x1P
             done = False
             if x1P is not None and hasattr(packed, "slots") and (pt, pl) == (0, 0):
-                done = ops.convT2x2_fwd_slots(x1P, packed.slots(x1P.shape[3]), bias, catP[:, C2 // 8:], Ct, x_slots=p16.get("x1_slots"),
-                                              slots=p16.get("up_slots"))
+                done = ops.convT2x2_fwd_slots(x1P, packed.slots(x1P.shape[3]), bias, catP[:, C2 // 8:], Ct, x_slots=p16.x1_slots,
+                                              slots=p16.up_slots)
             if not done and ops.is_placeholder(x1):
                 raise RuntimeError("onet_amd: ConvTranspose2d input kept only pre-split reached a shape the slot-operand GEMM does not take")
             # the GEMM's epilogue writes whole pre-split slots; shapes outside its fast path: fp32 + one conversion pass
-            if not done and not ops.convT2x2_fwd_p(x1, ops.pack_of(wp_fused), bias, catP[:, C2 // 8:], Ct, pt, pl, slots=p16.get("up_slots")):
+            if not done and not ops.convT2x2_fwd_p(x1, ops.pack_of(wp_fused), bias, catP[:, C2 // 8:], Ct, pt, pl, slots=p16.up_slots):
                 # (e.g. an 8 x 8 input map: h w % 128 != 0.)  The conversion pass applies the guard scale of the same slots the
                 # fused epilogue would have used, so the consumer's rescale stays right
                 up = torch.empty((B, Ct, Ho, Wo), dtype=torch.float32, device=x1.device)
                 ops.convT2x2_fwd(x1, ops.pack_of(wp_fused), bias, up, Ct, pt, pl)
-                ops.split_pack_act(up, out=catP[:, C2 // 8:], slots=p16.get("up_slots"))
+                ops.split_pack_act(up, out=catP[:, C2 // 8:], slots=p16.up_slots)
             ctx.save_for_backward(x1)
             ctx.wp_dgrad = wp_dgrad
             ctx.meta = (C2, Ct, h, w, pt, pl, tuple(weight.shape), bias is not None)
             _record_versions(ctx, weight, bias)
             # round 5: the backward GEMMs on slot operands too -- the consumer of the concat buffer (the decoder block's first convolution)
-            # is told, through the shared dict, to hand the up-sampled half of its input gradient over pre-split
-            lk = p16.get("up_link")
+            # is told, through the shared UpLink, to hand the up-sampled half of its input gradient over pre-split
+            lk = p16.up_link
             ctx.up_link = None
             if lk is not None and done:
-                lk["want"] = (C2, Ct)
-                ctx.up_link, ctx.slot_ops = lk, (x1P, p16.get("x1_slots"), packed)
+                lk.want = (C2, Ct)
+                ctx.up_link, ctx.slot_ops = lk, (x1P, p16.x1_slots, packed)
             elif ops.is_placeholder(x1):
                 raise RuntimeError("onet_amd: ConvTranspose2d input kept only pre-split, but the slot-operand backward is not set up")
             return ops.fp32_placeholder((B, C2 + Ct, Ho, Wo), x1.device)
@@ -605,10 +557,11 @@ class UpConvTCatFn(torch.autograd.Function):
         dx1 = dw = db = None
         lk = getattr(ctx, "up_link", None)
         if lk is not None:
-            # (the per-backward payload only: the request itself, lk["want"], stays for a further backward through a retained graph)
-            dyP, dy_slots, rda = lk.pop("dyP", None), lk.pop("dy_slots", None), lk.pop("da", None)
-            if dyP is not None and rda is not None and rda.data_ptr() == dcat.data_ptr() and rda.shape == dcat.shape:
+            # (the per-backward payload only: the request itself, UpLink.want, stays for a further backward through a retained graph)
+            hand = lk.take(dcat)
+            if hand is not None:
                 # the up-sampled half of dcat exists only pre-split (written by the 3x3 input gradient that produced dcat)
+                dyP, dy_slots = hand
                 x1P, x1_slots, packed = ctx.slot_ops
                 want_db = need_b and has_bias
                 if need_x1:
@@ -743,17 +696,17 @@ class HeadSoftmaxTwinFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, L, H, head_link=None):
-        """head_link (round 5): {"z", "save"} published by the network's last Conv-BatchNorm-ReLU unit, which then wrote NO activation
-        (H is a placeholder): the head normalises and rectifies z on load -- the same bits -- in forward and backward."""
+        """head_link (round 5): the HeadLink in which the network's last Conv-BatchNorm-ReLU unit published (z, save) where it wrote NO
+        activation (H is a placeholder): the head normalises and rectifies z on load -- the same bits -- in forward and backward."""
         B = L.shape[0] // 2
         ctx.h_save = None
         ctx.unit_link = None
-        if head_link is not None and "z" in head_link:
-            z, save = head_link.pop("z"), head_link.pop("save")
+        z, save, bwd_fuse = head_link.take_forward() if head_link is not None else (None, None, False)
+        if z is not None:
             assert z.shape == H.shape and z.dtype == torch.float32 and save.shape[0] == 2
             ctx.h_save = save
             # the unit can take dH = g L unwritten (its placeholder H has this one reader, so its gradient arrives there as returned here)
-            if head_link.pop("bwd_fuse", False) and ops.is_placeholder(H):
+            if bwd_fuse and ops.is_placeholder(H):
                 ctx.unit_link = head_link
             H = z
         elif ops.is_placeholder(H):
@@ -774,8 +727,7 @@ class HeadSoftmaxTwinFn(torch.autograd.Function):
             g = ops.head_grad_map(dVt, dVd, dS, S)
             dL, rec4, da_amax = ops.head_bwd_reduce(g, (gsLt, gsLd), L, H, ctx.h_save, want_amax=ops.p16_parts() == 2)
             dH = ops.fp32_placeholder(H.shape, H.device)
-            lk.clear()
-            lk.update(da=dH, rec4=rec4, da_amax=da_amax, gl=(g, L))
+            lk.grad.publish(dH, rec4=rec4, da_amax=da_amax, gl=(g, L))
             return dL, dH, None
         nrm = None if ctx.h_save is None else (ctx.h_save[0], ctx.h_save[1])
         dL, dH = ops.head_softmax_bwd(dVt, dVd, dS, S, L[:B], H[:B], L[B:], H[B:], twin=True, gsums=(gsLt, gsLd), h_norm=nrm)

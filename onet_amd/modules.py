@@ -13,12 +13,14 @@ called.  There is no CPU fallback: a CPU tensor raises."""
 from __future__ import annotations
 
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
 
 from . import functional as Fn
 from . import ops
+from .handoff import BlockOut, ConcatIO, HeadLink, PoolRequest, UnitIO, UnitLink, UpLink
 
 
 class _Packable:
@@ -124,7 +126,7 @@ class DoubleConv(nn.Module):
         return bool(ops.presplit() and s[1].training and s[4].training and s[1].running_mean is not None)
 
     @staticmethod
-    def _unit(x, conv, bn, out=None, groups=1, link_out=None, link_in=None, p16=None):
+    def _unit(x, conv, bn, out=None, groups=1, link_out=None, link_in=None, io=None):
         training = bn.training or (bn.running_mean is None)
         if x.dim() != 4:
             raise ValueError(f"expected 4D input (got {x.dim()}D input)")
@@ -137,22 +139,21 @@ class DoubleConv(nn.Module):
         if training and bn.track_running_stats:
             ops.count_batches(bn.num_batches_tracked, groups)
         # magnitude slots (ops.tag_amax): what x's producer recorded of it goes in, what this unit records of its output comes out
-        aux = {"x_amax": ops.amax_of(x)}
+        if io is None:
+            io = UnitIO()
+        io.x_amax = ops.amax_of(x)
         a = Fn.ConvBNReLUFn.apply(x, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                  training, bn.momentum, bn.eps, conv.packed(), out, groups, link_out, link_in, aux, p16)
-        if p16 is not None:
-            ops.tag_p16(a, p16.get("a"), p16.get("a_slots"))      # pre-split storage: the output's pre-split form (+ its scale slots) rides on it
-            if p16.get("a_amax") is not None:
-                return ops.tag_amax(a, p16["a_amax"])
-        return ops.tag_amax(a, aux.get("a_amax"))
+                                  training, bn.momentum, bn.eps, conv.packed(), out, groups, link_out, link_in, io)
+        ops.tag_p16(a, io.aP, io.a_slots)           # pre-split storage: the output's pre-split form (+ its scale slots) rides on it
+        return ops.tag_amax(a, io.a_amax)
 
     def forward(self, x, out=None, groups=1, pool_link=None, p16_out=None, up_link=None, head_link=None):
         """`out`: optional plane-contiguous [B, Cout, H, W] destination view (the skip half of a concat buffer);
-        `groups`: the batch holds that many independent BatchNorm batches (twin pass); `pool_link`: dict the second
-        unit publishes its (z, save) in for the SkipPoolFn that consumes the block's output; `p16_out` (pre-split storage): {"out": pre-split destination of the
-        block's output (the skip groups of a pre-split concat buffer), "keep_fp32": the fp32 tensor is needed too}."""
+        `groups`: the batch holds that many independent BatchNorm batches (twin pass); `pool_link`: the UnitLink the second
+        unit publishes its (z, save) in for the SkipPoolFn that consumes the block's output; `p16_out` (pre-split storage): a BlockOut
+        (`out`: e.g. the skip groups of a pre-split concat buffer)."""
         s = self.double_conv
-        link = {}       # unit 1 -> unit 2: lets unit 2's dgrad launch take unit 1's BatchNorm-backward reduce pass with it
+        link = UnitLink()   # unit 1 -> unit 2: lets unit 2's dgrad launch take unit 1's BatchNorm-backward reduce pass with it
         if x.dim() == 4 and x.is_cuda and self.pre_capable():
             # pre-split storage: a tensor is written pre-split exactly where ops.pre_layer_ok says its consuming convolution runs
             # all three of its kernels on pre-split operands (the producer of x decided with the same function)
@@ -162,17 +163,17 @@ class DoubleConv(nn.Module):
             if xP is not None or pre2 or p16_out is not None:
                 if xP is None and ops.is_placeholder(x) and ops.twin_src_of(x) is None:
                     raise RuntimeError("onet_amd: a tensor kept only pre-split reached a DoubleConv without its pre-split form")
-                p1 = {"x": xP, "x_slots": ops.p16_slots(x), "want": pre2, "up_link": up_link}
-                a1 = self._unit(x, s[0], s[1], None, groups, link_out=link, p16=p1)
-                p2 = {"x": p1.get("a"), "x_slots": p1.get("a_slots"), "want": p16_out is not None, "head_link": head_link,
-                      "out": None if p16_out is None else p16_out.get("out"),
-                      "keep_fp32": True if p16_out is None else bool(p16_out.get("keep_fp32"))}
-                return self._unit(a1, s[3], s[4], None, groups, link_out=pool_link, link_in=link, p16=p2)
+                p1 = UnitIO(xP=xP, x_slots=ops.p16_slots(x), want=pre2, up_link=up_link)
+                a1 = self._unit(x, s[0], s[1], None, groups, link_out=link, io=p1)
+                p2 = UnitIO(xP=p1.aP, x_slots=p1.a_slots, want=p16_out is not None, head_link=head_link,
+                            out=None if p16_out is None else p16_out.out,
+                            keep_fp32=True if p16_out is None else bool(p16_out.keep_fp32))
+                return self._unit(a1, s[3], s[4], None, groups, link_out=pool_link, link_in=link, io=p2)
         # fp32 model, split-bf16 kernels: unit 2's convolution (forward and weight gradient) applies unit 1's BatchNorm + ReLU
         # on load -- unit 1 writes no activation (functional.ConvBNReLUFn; bit-identical to the materialised form)
         if (x.dim() == 4 and x.is_cuda and s[1].training and s[4].training and s[1].running_mean is not None
                 and ops.norm_on_load_ok(x.shape[0], s[3].in_channels, s[3].out_channels, x.shape[2], x.shape[3], groups)):
-            link["defer"] = True
+            link.defer = True
         a1 = self._unit(x, s[0], s[1], None, groups, link_out=link)
         return self._unit(a1, s[3], s[4], None if out is None else (out,), groups, link_out=pool_link, link_in=link)
 
@@ -253,13 +254,12 @@ class Up(nn.Module):
             x1_slots = ops.p16_slots(x1) if x1P is not None else None
             s_skip, x1_amax = ops.p16_slots(x2), (x1_slots if x1P is not None else ops.amax_of(x1))
             s_up = ops.convT2x2_out_bound(self.up.weight, self.up.bias, x1_amax) if (x1_amax is not None and catP.shape[3] == 2) else None
-            p16 = {"catP": catP, "up_slots": s_up, "x1P": x1P, "x1_slots": x1_slots}
-            # the backward GEMMs on slot operands (round 5): this Up's ConvTranspose2d and the first convolution of its DoubleConv share a
-            # dict through which the up-sampled half of the concat gradient travels pre-split
+            # the backward GEMMs on slot operands (round 5): this Up's ConvTranspose2d and the first convolution of its DoubleConv share an
+            # UpLink through which the up-sampled half of the concat gradient travels pre-split
             B, Cin, h, w = x1.shape
-            up_link = {} if (x1P is not None and self.training and self.conv.pre_capable() and
-                             ops.convt_bwd_slots_ok(B, Cin, self.up.out_channels, x2.shape[1], h, w)) else None
-            p16["up_link"] = up_link
+            up_link = UpLink() if (x1P is not None and self.training and self.conv.pre_capable() and
+                                   ops.convt_bwd_slots_ok(B, Cin, self.up.out_channels, x2.shape[1], h, w)) else None
+            p16 = ConcatIO(catP, s_up, x1P, x1_slots, up_link)
             x = Fn.UpConvTCatFn.apply(x1, x2, self.up.weight, self.up.bias, self.up.packed(), None, p16)
             ops.tag_p16(x, catP, (s_skip, s_up, x2.shape[1]) if (s_skip is not None or s_up is not None) else None)
             return self.conv(x, groups=groups, p16_out=p16_out, up_link=up_link, head_link=head_link)
@@ -268,6 +268,22 @@ class Up(nn.Module):
         else:
             x = Fn.UpBilinearCatFn.apply(x1, x2)
         return self.conv(x, groups=groups, p16_out=p16_out)
+
+
+class _Level(NamedTuple):
+    """UNet._level_storage, encoder level k (inc, down1 .. down3).  The blocks around its output, the skip tensor: enc writes it, nxt
+    (the next Down's block) reads it max-pooled, up concatenates it for its block dec, and src is the block below, which feeds up's
+    ConvTranspose2d.  Its storage: cat, the fp32 concat buffer, or catP, the pre-split one (one of them, or neither); pool_p: the
+    pooled tensor feeds a pre-split convolution; upP: the BlockOut of src (its output is written pre-split), or None."""
+    enc: DoubleConv
+    nxt: DoubleConv
+    dec: DoubleConv
+    up: Up
+    src: DoubleConv
+    cat: object
+    catP: object
+    pool_p: bool
+    upP: BlockOut | None
 
 
 class UNet(nn.Module):
@@ -300,16 +316,13 @@ class UNet(nn.Module):
                 nn.init.kaiming_normal_(m.weight, mode=mode, nonlinearity="relu")
                 if m.bias is not None:
                     m.bias.data.zero_()
-            elif isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d)):
+            elif isinstance(m, nn.BatchNorm2d):
                 m.weight.data.fill_(1)
-                m.bias.data.zero_()
-            elif isinstance(m, nn.Linear):
-                m.weight.data.normal_(0, 0.01)
                 m.bias.data.zero_()
 
     def forward(self, x, groups=1, head_link=None):
-        """head_link (Onet.forward, twin batch): a dict through which the LAST unit hands its pre-activation and coefficients to the head
-        instead of writing its activation (the second returned tensor is then a placeholder: Onet's head is its only reader)."""
+        """head_link (Onet.forward, twin batch): the HeadLink through which the LAST unit hands its pre-activation and coefficients to the
+        head instead of writing its activation (the second returned tensor is then a placeholder: Onet's head is its only reader)."""
         # the 18 num_batches_tracked counters of a pass take their increments in one multi-tensor launch when the pass is through
         if head_link is None and groups == 1 and not self.training and ops.fused_eval():
             from . import inference
@@ -320,103 +333,94 @@ class UNet(nn.Module):
         with ops.counting_batches():
             return self._forward(x, groups, None if plain else head_link, plain)
 
-    def _forward(self, x, groups=1, head_link=None, plain=False):
-        """plain: a hook watches a block (_hooked): every block returns a real fp32 tensor and its consumers read only that."""
-        # ConvTranspose path: the four skip tensors are produced directly inside the first half of their concat
-        # buffers (allocated here, before the encoder runs), the decoder fills the second half
-        cats = [None] * 4
-        if not self.bilinear and x.dim() == 4 and x.is_cuda:
-            B, h, w = x.shape[0], x.shape[2], x.shape[3]
-            for k, enc in enumerate((self.inc, self.down1.maxpool_conv[1], self.down2.maxpool_conv[1],
-                                     self.down3.maxpool_conv[1])):
+    def _level_storage(self, x, plain):
+        """-> one _Level per encoder level k: the blocks around that level's skip tensor and how it, its pooled copy and the input of
+        its Up's ConvTranspose2d are stored in this pass."""
+        encs = (self.inc, self.down1.maxpool_conv[1], self.down2.maxpool_conv[1], self.down3.maxpool_conv[1])
+        nxts = encs[1:] + (self.down4.maxpool_conv[1],)
+        srcs = (self.up3.conv, self.up2.conv, self.up1.conv, self.down4.maxpool_conv[1])
+        on = not self.bilinear and x.dim() == 4 and x.is_cuda
+        pre = on and ops.presplit() and self.training and not plain
+        levels = []
+        for k, (enc, nxt, up, src) in enumerate(zip(encs, nxts, (self.up4, self.up3, self.up2, self.up1), srcs)):
+            cat = catP = upP = None
+            pool_p = False
+            if on:
+                B, h, w = x.shape[0], x.shape[2] >> k, x.shape[3] >> k
                 C = enc.double_conv[3].out_channels
-                if h > 0 and w > 0:
-                    cats[k] = torch.empty((B, 2 * C, h, w), dtype=torch.float32, device=x.device)
-                h, w = h // 2, w // 2
-
-        # pre-split storage: where the decoder's first convolution runs on pre-split operands (ops.pre_layer_ok), the concat buffer
-        # exists ONLY pre-split: the encoder's BatchNorm pass writes the skip groups, the Up block the up-sampled ones
-        catsP = [None] * 4
-        pool_p = [False] * 4                                # the pooled tensor of encoder level k feeds a pre-split convolution
-        if not self.bilinear and x.dim() == 4 and x.is_cuda and ops.presplit() and self.training and not plain:
-            B, h, w = x.shape[0], x.shape[2], x.shape[3]
-            for k, enc in enumerate((self.inc, self.down1.maxpool_conv[1], self.down2.maxpool_conv[1], self.down3.maxpool_conv[1])):
-                C = enc.double_conv[3].out_channels
-                dec = (self.up4, self.up3, self.up2, self.up1)[k].conv.double_conv[0]
-                nxt = (self.down1, self.down2, self.down3, self.down4)[k].maxpool_conv[1].double_conv[0]
-                dec_blk = (self.up4, self.up3, self.up2, self.up1)[k].conv
-                nxt_blk = (self.down1, self.down2, self.down3, self.down4)[k].maxpool_conv[1]
+            if pre:
+                # pre-split storage: where the decoder's first convolution runs on pre-split operands (ops.pre_layer_ok), the concat
+                # buffer exists ONLY pre-split: the encoder's BatchNorm pass writes the skip groups, the Up block the up-sampled ones
                 # (producer AND consumer must take their pre-split branches: DoubleConv.pre_capable -- a partially frozen network keeps
                 # fp32 tensors at the levels concerned, as it did before pre-split storage)
-                if h % 16 == 0 and w % 16 == 0 and dec.in_channels == 2 * C and ops.pre_layer_ok(B, dec.in_channels, dec.out_channels, h, w) \
-                        and enc.pre_capable() and dec_blk.pre_capable():
-                    catsP[k] = ops.p16_empty(B, 2 * C, h, w, x.device)
-                    cats[k] = None
-                pool_p[k] = h % 2 == 0 and w % 2 == 0 and ops.pre_layer_ok(B, nxt.in_channels, nxt.out_channels, h // 2, w // 2) \
-                    and nxt_blk.pre_capable()
-                h, w = h // 2, w // 2
-        # round 5: the input of a ConvTranspose2d whose output goes into a pre-split concat buffer is written pre-split by the block below
-        # (down4, up1 .. up3) where the slot-operand GEMM takes the shape; its fp32 tensor stays for the weight gradient
-        upP = [None] * 4                                    # [k]: p16_out of the block that feeds level k's Up
-        if any(c is not None for c in catsP):
-            B, h, w = x.shape[0], x.shape[2], x.shape[3]
-            for k in range(4):
-                up = (self.up4, self.up3, self.up2, self.up1)[k]
-                src = (self.up3.conv, self.up2.conv, self.up1.conv, self.down4.maxpool_conv[1])[k]
-                hk, wk = h >> (k + 1), w >> (k + 1)         # the map that level k's ConvTranspose2d reads
-                if catsP[k] is not None and isinstance(up.up, ConvT2x2) and src.pre_capable() and \
-                        ops.convt_slots_ok(B, up.up.in_channels, up.up.out_channels, hk, wk):
-                    # (the fp32 tensor stays only where the weight gradient still reads it: Up.forward decides with the same function)
-                    bwd = up.training and up.conv.pre_capable() and \
-                        ops.convt_bwd_slots_ok(B, up.up.in_channels, up.up.out_channels, up.up.out_channels, hk, wk)
-                    upP[k] = {"keep_fp32": not bwd}
+                c_dec, c_nxt = up.conv.double_conv[0], nxt.double_conv[0]
+                if h % 16 == 0 and w % 16 == 0 and c_dec.in_channels == 2 * C and ops.pre_layer_ok(B, c_dec.in_channels, c_dec.out_channels, h, w) \
+                        and enc.pre_capable() and up.conv.pre_capable():
+                    catP = ops.p16_empty(B, 2 * C, h, w, x.device)
+                pool_p = h % 2 == 0 and w % 2 == 0 and ops.pre_layer_ok(B, c_nxt.in_channels, c_nxt.out_channels, h // 2, w // 2) \
+                    and nxt.pre_capable()
+            if on and catP is None and h > 0 and w > 0:
+                # ConvTranspose path: the skip tensor is produced directly inside the first half of its concat buffer (allocated here,
+                # before the encoder runs), the decoder fills the second half
+                cat = torch.empty((B, 2 * C, h, w), dtype=torch.float32, device=x.device)
+            # round 5: the input of a ConvTranspose2d whose output goes into a pre-split concat buffer is written pre-split by the block
+            # below (down4, up1 .. up3) where the slot-operand GEMM takes the shape (h / 2 x w / 2: the map that ConvTranspose2d reads)
+            if catP is not None and isinstance(up.up, ConvT2x2) and src.pre_capable() and \
+                    ops.convt_slots_ok(B, up.up.in_channels, up.up.out_channels, h >> 1, w >> 1):
+                # (the fp32 tensor stays only where the weight gradient still reads it: Up.forward decides with the same function)
+                bwd = up.training and up.conv.pre_capable() and \
+                    ops.convt_bwd_slots_ok(B, up.up.in_channels, up.up.out_channels, up.up.out_channels, h >> 1, w >> 1)
+                upP = BlockOut(keep_fp32=not bwd)
+            levels.append(_Level(enc, nxt, up.conv, up, src, cat, catP, pool_p, upP))
+        return levels
 
-        def skip(k, C):
-            return None if cats[k] is None else cats[k][:, :C]
+    def _forward(self, x, groups=1, head_link=None, plain=False):
+        """plain: a hook watches a block (_hooked): every block returns a real fp32 tensor and its consumers read only that."""
+        lv = self._level_storage(x, plain)
 
-        def skipP(k, C, keep_fp32=False):
-            return None if catsP[k] is None else {"out": catsP[k][:, :C // 8], "keep_fp32": keep_fp32}
+        def skip(k):
+            return None if lv[k].cat is None else lv[k].cat[:, :lv[k].enc.double_conv[3].out_channels]
+
+        def skipP(k, keep_fp32=False):
+            return None if lv[k].catP is None else BlockOut(lv[k].catP[:, :lv[k].enc.double_conv[3].out_channels // 8], keep_fp32)
 
         g = groups
 
-        def fork(t, returned=False, link=None, nxt=None):
+        def fork(t, returned=False, link=None):
             # skip tensors feed the next Down's pooling AND an Up's concat (x1 also leaves as the first output): one
             # node, so that their gradients are summed inside the pooling-backward kernel
             if t.is_cuda:
                 am = ops.amax_of(t)
-                carry = {} if ops.presplit() else None        # (carries the pooled tensor's pre-split form back: "yP")
-                outs = Fn.SkipPoolFn.apply(t, returned, link, carry)
-                if carry is not None:
-                    ops.tag_p16(outs[1], carry.get("yP"), ops.p16_slots(t))  # the pooled tensor's pre-split form (max-pooling keeps the bound)
+                # (the pooled tensor's pre-split form, where its producer wrote one: read before SkipPoolFn takes the record)
+                yP = None if (link is None or link.pooled is None) else link.pooled.yP
+                outs = Fn.SkipPoolFn.apply(t, returned, link)
+                if ops.presplit():
+                    ops.tag_p16(outs[1], yP, ops.p16_slots(t))                # the pooled tensor's pre-split form (max-pooling keeps the bound)
                     ops.tag_p16(outs[0], ops.p16_of(t), ops.p16_slots(t))     # the skip view keeps the tensor's pre-split form
                 ops.tag_amax(outs[1], am)                    # max-pooling keeps the maximum: the same slots bound the pooled tensor
                 return outs
             return (t, None, t) if returned else (t, None)
 
         # pl[i]: the producing block's second unit -> the SkipPoolFn of its output (BatchNorm-backward reduce records)
-        pl = [None] * 4 if plain else [{} for _ in range(4)]
-        c0 = self.inc.double_conv[3].out_channels
-        c1 = self.down1.maxpool_conv[1].double_conv[3].out_channels
-        c2 = self.down2.maxpool_conv[1].double_conv[3].out_channels
-        c3 = self.down3.maxpool_conv[1].double_conv[3].out_channels
+        pl = [None] * 4 if plain else [UnitLink() for _ in range(4)]
         if x.dim() == 4 and x.is_cuda and ops.FUSE_POOL and not plain:
             # the four encoder outputs are max-pooled next: their BatchNorm + ReLU pass writes the pooled tensor too
             for i in range(4):
-                pl[i]["want_pool"] = {"p16": pool_p[i]}
+                pl[i].want_pool = PoolRequest(lv[i].pool_p)
         # (pre-split storage: x1 leaves the U-Net and feeds the head, so it keeps its fp32 tensor beside the pre-split skip groups)
-        x1 = self.inc(x, out=skip(0, c0), groups=g, pool_link=pl[0], p16_out=skipP(0, c0, True))
-        x1, p1, x1_out = fork(x1, True, pl[0], self.down1)
-        x2 = self.down1(x1, out=skip(1, c1), groups=g, pooled=p1, pool_link=pl[1], p16_out=skipP(1, c1))
-        x2, p2 = fork(x2, False, pl[1], self.down2)
-        x3 = self.down2(x2, out=skip(2, c2), groups=g, pooled=p2, pool_link=pl[2], p16_out=skipP(2, c2))
-        x3, p3 = fork(x3, False, pl[2], self.down3)
-        x4 = self.down3(x3, out=skip(3, c3), groups=g, pooled=p3, pool_link=pl[3], p16_out=skipP(3, c3))
-        x4, p4 = fork(x4, False, pl[3], self.down4)
-        x5 = self.down4(x4, groups=g, pooled=p4, p16_out=upP[3])
-        y4 = self.up1(x5, x4, cat=cats[3], groups=g, catP=catsP[3], p16_out=upP[2])
-        y3 = self.up2(y4, x3, cat=cats[2], groups=g, catP=catsP[2], p16_out=upP[1])
-        y2 = self.up3(y3, x2, cat=cats[1], groups=g, catP=catsP[1], p16_out=upP[0])
-        y1 = self.up4(y2, x1, cat=cats[0], groups=g, catP=catsP[0], head_link=head_link)
+        x1 = self.inc(x, out=skip(0), groups=g, pool_link=pl[0], p16_out=skipP(0, True))
+        x1, p1, x1_out = fork(x1, True, pl[0])
+        x2 = self.down1(x1, out=skip(1), groups=g, pooled=p1, pool_link=pl[1], p16_out=skipP(1))
+        x2, p2 = fork(x2, False, pl[1])
+        x3 = self.down2(x2, out=skip(2), groups=g, pooled=p2, pool_link=pl[2], p16_out=skipP(2))
+        x3, p3 = fork(x3, False, pl[2])
+        x4 = self.down3(x3, out=skip(3), groups=g, pooled=p3, pool_link=pl[3], p16_out=skipP(3))
+        x4, p4 = fork(x4, False, pl[3])
+        x5 = self.down4(x4, groups=g, pooled=p4, p16_out=lv[3].upP)
+        y4 = self.up1(x5, x4, cat=lv[3].cat, groups=g, catP=lv[3].catP, p16_out=lv[2].upP)
+        y3 = self.up2(y4, x3, cat=lv[2].cat, groups=g, catP=lv[2].catP, p16_out=lv[1].upP)
+        y2 = self.up3(y3, x2, cat=lv[1].cat, groups=g, catP=lv[1].catP, p16_out=lv[0].upP)
+        y1 = self.up4(y2, x1, cat=lv[0].cat, groups=g, catP=lv[0].catP, head_link=head_link)
         return x1_out, y1
 
 
@@ -469,7 +473,7 @@ class Onet(nn.Module):
             # split-K reduction instead of two plus autograd's add.
             # (a hooked U-Net gets the twin batch as a real tensor: a pre-hook of its first block would otherwise see a placeholder)
             XX = Fn.TwinInputFn.apply(X, float(self.bias), not _hooked(self.topu))
-            hl = {} if (ops.HEAD_NORM and self.training) else None     # (the last activation is formed by the head from z: no tensor)
+            hl = HeadLink() if (ops.HEAD_NORM and self.training) else None     # (the last activation is formed by the head from z: no tensor)
             L, H = self.topu(XX, groups=2, head_link=hl)
             Vt, Vd, S, sLt, sLd = Fn.HeadSoftmaxTwinFn.apply(L, H, hl)
             Lt, Ld = Fn.TwinSplitFn.apply(L)

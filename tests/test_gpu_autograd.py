@@ -3,7 +3,7 @@ retained graph, torch.autograd.grad (alone, then .backward(); with FlatAdam atta
 leave outputs without a gradient, parameters edited in place between forward and backward, an eval forward in between, gradient
 accumulation through FlatAdam's flat buffer, create_graph.
 
-The layers hand state to each other outside autograd (functional.py: the link dicts of DoubleConv, the pooling and the head, the
+The layers hand state to each other outside autograd (handoff.py: the link records of DoubleConv, the pooling and the head, the
 decoder's up_link; placeholders for tensors that exist only pre-split; lazily built ConvTranspose2d input-gradient packs; gradients
 written straight into FlatAdam's buffer).  Every test first checks, by counting the launches, that the hand-offs it targets really
 run at its shape, then holds the gradients to the fp64 oracle under the HIP run's own ReLU / pooling decisions

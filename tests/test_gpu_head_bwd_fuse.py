@@ -212,15 +212,23 @@ def test_unit_refuses_a_gradient_that_is_not_the_heads_placeholder(dev):
     raises -- it never reads a placeholder and never silently drops the hand-off; the hand-off is taken once."""
     from onet_amd import ops
     from onet_amd import functional as Fn
+    from onet_amd.handoff import HeadLink
     shape = (2, 8, 4, 4)
     ph = ops.fp32_placeholder(shape, dev)
-    link = {"da": ph, "rec4": "records", "da_amax": None, "gl": ("g", "L")}
-    assert Fn.ConvBNReLUFn._take_head_handoff(dict(link), ops.fp32_placeholder(shape, dev)) == ("records", None, ("g", "L"))
+    take = Fn.ConvBNReLUFn._take_head_handoff
+
+    def link():
+        lk = HeadLink()
+        lk.grad.publish(ph, rec4="records", da_amax=None, gl=("g", "L"))
+        return lk
+
+    got = take(link(), ops.fp32_placeholder(shape, dev))
+    assert (got.rec4, got.da_amax, got.gl) == ("records", None, ("g", "L"))
     with pytest.raises(RuntimeError, match="another tensor"):
-        Fn.ConvBNReLUFn._take_head_handoff(dict(link), torch.ones(shape, device=dev))
+        take(link(), torch.ones(shape, device=dev))
     with pytest.raises(RuntimeError, match="another tensor"):
-        Fn.ConvBNReLUFn._take_head_handoff(dict(link), ops.fp32_placeholder((2, 8, 4, 8), dev))
-    taken = dict(link)
-    Fn.ConvBNReLUFn._take_head_handoff(taken, ph)
-    assert "gl" not in taken and Fn.ConvBNReLUFn._take_head_handoff(taken, ph) is None
-    assert Fn.ConvBNReLUFn._take_head_handoff(None, ph) is None
+        take(link(), ops.fp32_placeholder((2, 8, 4, 8), dev))
+    taken = link()
+    take(taken, ph)
+    assert taken.grad.gl is None and take(taken, ph) is None
+    assert take(None, ph) is None
