@@ -2,7 +2,7 @@
 include/onet_hip_ragged.h / include/onet_hip_ragged_split.h for the one-part / fp16 two-part eval plan on ragged maps,
 include/onet_hip_anymap.h for the one-part plan's levels on maps of any size, include/onet_hip_pairs.h for its bottom level on
 image-pair tiles, include/onet_hip_upmap.h for its ConvTranspose2d edges on maps of any size, include/onet_hip_split_pairs.h for the
-fp16 two-part plan's bottom level on image-pair tiles).
+fp16 two-part plan's bottom level on image-pair tiles, include/onet_hip_verify.h for the SNR-gain report and the cascade).
 
 The prototypes are PARSED from the header, so the Python side cannot drift from
 the ABI.  There is no CPU fallback: if the library cannot be loaded (or built),
@@ -32,6 +32,8 @@ UPMAP_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_upmap.h"
 SPLIT_PAIRS_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_split_pairs.h")
 # ... and of the Adam step with its hyper-parameters in double (1 - beta rounded once, as torch.optim.Adam forms it)
 OPTIM_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_optim.h")
+# ... and of the performance report's device side: get_psnr's moments and the two-stage cascade's second input
+VERIFY_HEADER = os.path.join(os.path.dirname(HERE), "include", "onet_hip_verify.h")
 LIBPATH = os.environ.get("ONET_HIP_LIB") or os.path.join(HERE, "libonet_hip.so")
 
 _CT = {
@@ -90,7 +92,7 @@ def load(build_if_missing: bool = True):
         _build.build()
     lib = ctypes.CDLL(LIBPATH)
     _protos = {}
-    for header in (HEADER, EVAL_HEADER, RAGGED_HEADER, RAGGED_SPLIT_HEADER, ANYMAP_HEADER, PAIRS_HEADER, UPMAP_HEADER, SPLIT_PAIRS_HEADER, OPTIM_HEADER):
+    for header in (HEADER, EVAL_HEADER, RAGGED_HEADER, RAGGED_SPLIT_HEADER, ANYMAP_HEADER, PAIRS_HEADER, UPMAP_HEADER, SPLIT_PAIRS_HEADER, OPTIM_HEADER, VERIFY_HEADER):
         protos = parse_header(header)
         for name, (restype, argtypes, _) in protos.items():
             try:

@@ -16,7 +16,7 @@ def _stale():
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".hpp"))] + \
-        [os.path.join(HERE, "..", "include", h) for h in ("onet_hip.h", "onet_hip_eval.h", "onet_hip_ragged.h", "onet_hip_ragged_split.h", "onet_hip_anymap.h", "onet_hip_pairs.h", "onet_hip_upmap.h", "onet_hip_split_pairs.h", "onet_hip_optim.h")]
+        [os.path.join(HERE, "..", "include", h) for h in ("onet_hip.h", "onet_hip_eval.h", "onet_hip_ragged.h", "onet_hip_ragged_split.h", "onet_hip_anymap.h", "onet_hip_pairs.h", "onet_hip_upmap.h", "onet_hip_split_pairs.h", "onet_hip_optim.h", "onet_hip_verify.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

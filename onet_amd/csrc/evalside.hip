@@ -7,14 +7,25 @@
 // HBM-bound streaming reductions: one block per plane / image, wave-shuffle + LDS combine.
 //   * the validation step (include/onet_hip_eval.h): counts_kernel, the confusion counts of a whole batch in one launch spread
 //     over (chunks of an image, image), straight from the head's Vt, Vd or from a label map, ground truth read in its own dtype
+//   * the performance report's device side (include/onet_hip_verify.h): per-frame min / max of Vt, Vd and the fp64 sums and maxima
+//     get_psnr (UT:457-476) is made of, per image, by a fixed partition and a fixed-order merge (no floating-point atomics); the
+//     two-stage cascade's second input, the batch's flip decision read from its confusion counts by every block
 #include <algorithm>
 #include "common.hpp"
 #include "../../include/onet_hip_eval.h"
+#include "../../include/onet_hip_verify.h"
 
 using namespace onet;
 
-__global__ __launch_bounds__(256) void normalise_per_frame_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                                  int HW, float spacing) {
+// tensor_normal_per_frame's n(v) = (v - min) / (max - min + np.spacing(1)), evaluated in fp32 like torch does: the ONE expression of
+// normalise_per_frame_kernel, moments_kernel and cascade_input_kernel, so that the three give the same bits
+struct FrameScale {
+    float lo, den;
+    __device__ __forceinline__ FrameScale(float lo_, float hi_) : lo(lo_), den((hi_ - lo_) + 2.220446049250313e-16f) {}
+    __device__ __forceinline__ float operator()(float v) const { return (v - lo) / den; }
+};
+
+__global__ __launch_bounds__(256) void normalise_per_frame_kernel(const float* __restrict__ x, float* __restrict__ y, int HW) {
     __shared__ float smin[4], smax[4];
     const float* src = x + (int64_t)blockIdx.x * HW;
     float* dst = y + (int64_t)blockIdx.x * HW;
@@ -36,8 +47,8 @@ __global__ __launch_bounds__(256) void normalise_per_frame_kernel(const float* _
     __syncthreads();
     lo = fminf(fminf(smin[0], smin[1]), fminf(smin[2], smin[3]));
     hi = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
-    const float den = (hi - lo) + spacing;      // (max - min + np.spacing(1)) evaluated in fp32 like torch does
-    for (int i = threadIdx.x; i < HW; i += 256) dst[i] = (src[i] - lo) / den;
+    const FrameScale n(lo, hi);
+    for (int i = threadIdx.x; i < HW; i += 256) dst[i] = n(src[i]);
 }
 
 // counts[b] = (TP, FP, FN, TN) with positive class 1
@@ -210,12 +221,311 @@ static int launch_label_counts(const void* pred, int64_t pred_bs, const void* gt
     return launch_counts_gt(LabelMap<PredT>{static_cast<const PredT*>(pred), pred_bs}, gt, gt_dtype, gt_bs, counts, B, HW, vec, st);
 }
 
+// ---- the performance report's device side (include/onet_hip_verify.h): per-frame min / max, get_psnr's sums and maxima, the
+// cascade's second-stage input.  Fixed partition: block g of an image's G = frame_parts(HW) blocks takes the COUNTS_CHUNK-pixel
+// chunks g, g + G, ...; partial results go to the workspace, one wave merges them in lane order: no floating-point atomics, the
+// same bits in every run.
+constexpr int FRAME_PARTS = 64;       // at most one wave's lanes of partial results per image
+constexpr int MOMENTS = 9;            // per image: (sum v^2 on the target, sum v^2 off it, max v on it) of X, n(Vt), n(Vd)
+
+static inline int frame_parts(int HW) { return std::min(cdiv(HW, COUNTS_CHUNK), FRAME_PARTS); }
+
+// (min, max) pairs of NP maps over a wave
+template <int NP>
+__device__ __forceinline__ void wave_minmax(float (&m)[2 * NP]) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            m[2 * k] = fminf(m[2 * k], __shfl_xor(m[2 * k], o, 64));
+            m[2 * k + 1] = fmaxf(m[2 * k + 1], __shfl_xor(m[2 * k + 1], o, 64));
+        }
+    }
+}
+
+// ... and over a 256-thread block: the result in every thread (red: 4 * 2 NP floats)
+template <int NP>
+__device__ __forceinline__ void block_minmax_256(float (&m)[2 * NP], float* red) {
+    wave_minmax<NP>(m);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 2 * NP; ++k) red[(threadIdx.x >> 6) * 2 * NP + k] = m[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        m[2 * k] = fminf(fminf(red[2 * k], red[2 * NP + 2 * k]), fminf(red[4 * NP + 2 * k], red[6 * NP + 2 * k]));
+        m[2 * k + 1] = fmaxf(fmaxf(red[2 * k + 1], red[2 * NP + 2 * k + 1]), fmaxf(red[4 * NP + 2 * k + 1], red[6 * NP + 2 * k + 1]));
+    }
+}
+
+// grid (G, image): part[b][g][4] = (min Vt, max Vt, min Vd, max Vd) of block g's chunks
+template <bool VEC>
+__global__ __launch_bounds__(256) void frame_minmax_kernel(const float* __restrict__ Vt, const float* __restrict__ Vd,
+                                                           float* __restrict__ part, int HW) {
+    __shared__ float red[4 * 4];
+    const int b = blockIdx.y;
+    const float *vt = Vt + (int64_t)b * HW, *vd = Vd + (int64_t)b * HW;
+    float m[4] = {INFINITY, -INFINITY, INFINITY, -INFINITY};
+    for (int64_t base = (int64_t)blockIdx.x * COUNTS_CHUNK; base < HW; base += (int64_t)gridDim.x * COUNTS_CHUNK) {
+        if (VEC) {
+            const int64_t i = base + threadIdx.x * 4;
+            if (i < HW) {       // (HW % 4 == 0: the four are inside together)
+                const Pack<float, 4> t = load_pack<float, 4>(vt + i), d = load_pack<float, 4>(vd + i);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    m[0] = fminf(m[0], t.v[k]);
+                    m[1] = fmaxf(m[1], t.v[k]);
+                    m[2] = fminf(m[2], d.v[k]);
+                    m[3] = fmaxf(m[3], d.v[k]);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = base + k * 256 + threadIdx.x;
+                if (i < HW) {
+                    const float t = vt[i], d = vd[i];
+                    m[0] = fminf(m[0], t);
+                    m[1] = fmaxf(m[1], t);
+                    m[2] = fminf(m[2], d);
+                    m[3] = fmaxf(m[3], d);
+                }
+            }
+        }
+    }
+    block_minmax_256<2>(m, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) part[((int64_t)b * gridDim.x + blockIdx.x) * 4 + k] = m[k];
+    }
+}
+
+// one pixel's share of a block's partial moments: s[2 k], s[2 k + 1] the sums of source k on / off the target, mx[k] its maximum on it
+__device__ __forceinline__ void moments_add(double (&s)[6], float (&mx)[3], int t, float x, float a, float d) {
+    const float v[3] = {x, a, d};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double sq = (double)v[k] * (double)v[k];
+        s[2 * k] += t ? sq : 0.0;
+        s[2 * k + 1] += t ? 0.0 : sq;
+        mx[k] = t ? fmaxf(mx[k], v[k]) : mx[k];
+    }
+}
+
+// grid (G, image), G frame_minmax_kernel's: every block merges the image's G min / max partials (block 0 stores them to minmax[b]),
+// then part[b][g][9] = the moments of its chunks
+template <typename GtT, bool VEC>
+__global__ __launch_bounds__(256) void moments_kernel(const float* __restrict__ X, int64_t x_bs, const float* __restrict__ Vt,
+                                                      const float* __restrict__ Vd, const LabelMap<GtT> gt,
+                                                      const float* __restrict__ mm_part, float* __restrict__ minmax,
+                                                      double* __restrict__ part, int HW) {
+    __shared__ float smm[4];
+    __shared__ double red[4 * 6];
+    __shared__ float redx[4 * 3];
+    const int b = blockIdx.y, G = gridDim.x;
+    if (threadIdx.x < 64) {
+        float m[4] = {INFINITY, -INFINITY, INFINITY, -INFINITY};
+        if ((int)threadIdx.x < G) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) m[k] = mm_part[((int64_t)b * G + threadIdx.x) * 4 + k];
+        }
+        wave_minmax<2>(m);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                smm[k] = m[k];
+                if (blockIdx.x == 0) minmax[(int64_t)b * 4 + k] = m[k];
+            }
+        }
+    }
+    __syncthreads();
+    const FrameScale nt(smm[0], smm[1]), nd(smm[2], smm[3]);
+    const float *x = X ? X + (int64_t)b * x_bs : nullptr, *vt = Vt + (int64_t)b * HW, *vd = Vd + (int64_t)b * HW;
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    float mx[3] = {0.f, 0.f, 0.f};
+    for (int64_t base = (int64_t)blockIdx.x * COUNTS_CHUNK; base < HW; base += (int64_t)gridDim.x * COUNTS_CHUNK) {
+        if (VEC) {
+            const int64_t i = base + threadIdx.x * 4;
+            if (i < HW) {
+                int t[4];
+                gt.template labels<4>(b, i, HW, t);
+                const Pack<float, 4> pt = load_pack<float, 4>(vt + i), pd = load_pack<float, 4>(vd + i);
+                Pack<float, 4> px = {{0.f, 0.f, 0.f, 0.f}};
+                if (x) px = load_pack<float, 4>(x + i);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) moments_add(s, mx, t[k], px.v[k], nt(pt.v[k]), nd(pd.v[k]));
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = base + k * 256 + threadIdx.x;
+                if (i < HW) {
+                    int t[1];
+                    gt.template labels<1>(b, i, HW, t);
+                    moments_add(s, mx, t[0], x ? x[i] : 0.f, nt(vt[i]), nd(vd[i]));
+                }
+            }
+        }
+    }
+    block_sum_256<double, 6>(s, red);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o, 64));
+        if ((threadIdx.x & 63) == 0) redx[(threadIdx.x >> 6) * 3 + k] = mx[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double* dst = part + ((int64_t)b * G + blockIdx.x) * MOMENTS;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            dst[3 * k] = s[2 * k];
+            dst[3 * k + 1] = s[2 * k + 1];
+            dst[3 * k + 2] = (double)fmaxf(fmaxf(redx[k], redx[3 + k]), fmaxf(redx[6 + k], redx[9 + k]));
+        }
+    }
+}
+
+// grid (image), one wave: lane g holds block g's partial row (zeros past G), merged by wave_sum's fixed tree
+__global__ __launch_bounds__(64) void moments_merge_kernel(const double* __restrict__ part, double* __restrict__ moments, int G) {
+    const int b = blockIdx.x;
+    double v[MOMENTS];
+#pragma unroll
+    for (int k = 0; k < MOMENTS; ++k) v[k] = (int)threadIdx.x < G ? part[((int64_t)b * G + threadIdx.x) * MOMENTS + k] : 0.0;
+#pragma unroll
+    for (int k = 0; k < MOMENTS; ++k) {
+        if (k % 3 == 2) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v[k] = fmax(v[k], __shfl_xor(v[k], o, 64));
+        } else {
+            v[k] = wave_sum(v[k]);
+        }
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < MOMENTS; ++k) moments[(int64_t)b * MOMENTS + k] = v[k];
+    }
+}
+
+// grid (blocks of an image, image); minmax == NULL: ONE block per image (the entry point's grid), which finds the selected frame's
+// min / max itself.  Every block sums the batch's counts: flip = right < wrong, integers.
+template <bool VEC>
+__global__ __launch_bounds__(256) void cascade_input_kernel(const float* __restrict__ Vt, const float* __restrict__ Vd,
+                                                            const float* __restrict__ minmax, const int64_t* __restrict__ counts,
+                                                            float* __restrict__ X2, int B, int HW) {
+    __shared__ long long redc[4 * 2];
+    __shared__ float red[4 * 2];
+    __shared__ int sflip;
+    const int b = blockIdx.y;
+    long long c[2] = {0, 0};      // (right, wrong) = (TP + TN, FP + FN) over the batch
+    for (int i = threadIdx.x; i < B; i += 256) {
+        c[0] += counts[(int64_t)i * 4 + 0] + counts[(int64_t)i * 4 + 3];
+        c[1] += counts[(int64_t)i * 4 + 1] + counts[(int64_t)i * 4 + 2];
+    }
+    block_sum_256<long long, 2>(c, redc);
+    if (threadIdx.x == 0) sflip = c[0] < c[1];
+    __syncthreads();
+    const bool flip = sflip != 0;
+    const float* src = (flip ? Vt : Vd) + (int64_t)b * HW;
+    float* dst = X2 + (int64_t)b * HW;
+    float m[2] = {INFINITY, -INFINITY};
+    if (minmax) {
+        m[0] = minmax[(int64_t)b * 4 + (flip ? 0 : 2)];
+        m[1] = minmax[(int64_t)b * 4 + (flip ? 1 : 3)];
+    } else {
+        for (int i = threadIdx.x; i < HW; i += 256) {
+            const float v = src[i];
+            m[0] = fminf(m[0], v);
+            m[1] = fmaxf(m[1], v);
+        }
+        block_minmax_256<1>(m, red);
+    }
+    const FrameScale n(m[0], m[1]);
+    for (int64_t base = (int64_t)blockIdx.x * COUNTS_CHUNK; base < HW; base += (int64_t)gridDim.x * COUNTS_CHUNK) {
+        if (VEC) {
+            const int64_t i = base + threadIdx.x * 4;
+            if (i < HW) {
+                Pack<float, 4> v = load_pack<float, 4>(src + i);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v.v[k] = n(v.v[k]);
+                store_pack<float, 4>(dst + i, v);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = base + k * 256 + threadIdx.x;
+                if (i < HW) dst[i] = n(src[i]);
+            }
+        }
+    }
+}
+
+template <typename GtT>
+static int launch_moments(const float* X, int64_t x_bs, const float* Vt, const float* Vd, const void* gt, int64_t gt_bs,
+                          const float* mm_part, float* minmax, double* part, int B, int HW, bool vec, hipStream_t st) {
+    const dim3 grid((unsigned)frame_parts(HW), (unsigned)B);
+    const LabelMap<GtT> g{static_cast<const GtT*>(gt), gt_bs};
+    if (vec)
+        hipLaunchKernelGGL((moments_kernel<GtT, true>), grid, dim3(256), 0, st, X, x_bs, Vt, Vd, g, mm_part, minmax, part, HW);
+    else
+        hipLaunchKernelGGL((moments_kernel<GtT, false>), grid, dim3(256), 0, st, X, x_bs, Vt, Vd, g, mm_part, minmax, part, HW);
+    return check_launch("moments_kernel");
+}
+
 extern "C" {
+
+int onet_snr_moments(const float* X, int64_t x_bs, const float* Vt, const float* Vd, const void* gt, int gt_dtype, int64_t gt_bs,
+                     double* moments, float* minmax, int B, int HW, void* ws, int64_t ws_bytes, void* stream) {
+    ONET_REQUIRE(Vt && Vd && gt && moments && minmax && ws, "snr_moments: null pointer");
+    ONET_REQUIRE(B > 0 && B <= 65535 && HW > 0, "snr_moments: bad shape");
+    ONET_REQUIRE(gt_dtype >= 0 && gt_dtype <= 3, "snr_moments: unknown dtype code %d", gt_dtype);
+    ONET_REQUIRE(gt_bs >= HW && (!X || x_bs >= HW), "snr_moments: batch stride %lld / %lld below HW = %d", (long long)gt_bs,
+                 (long long)x_bs, HW);
+    const int64_t need = (int64_t)B * FRAME_PARTS * (MOMENTS * 8 + 4 * 4);
+    ONET_REQUIRE((uintptr_t)ws % 8 == 0 && ws_bytes >= need, "snr_moments: workspace of %lld bytes (8-byte aligned) needed, %lld given",
+                 (long long)need, (long long)ws_bytes);
+    const hipStream_t st = as_stream(stream);
+    const int G = frame_parts(HW);
+    double* part = static_cast<double*>(ws);                                                            // [B][G][9]
+    float* mm_part = reinterpret_cast<float*>(static_cast<char*>(ws) + (int64_t)B * FRAME_PARTS * MOMENTS * 8);   // [B][G][4]
+    const bool vec_v = HW % 4 == 0 && wide_ok(Vt, HW, 4) && wide_ok(Vd, HW, 4);
+    const bool vec = vec_v && wide_ok(X, x_bs, 4) && wide_ok(gt, gt_bs, LABEL_BYTES[gt_dtype]);
+    const dim3 grid((unsigned)G, (unsigned)B);
+    if (vec_v)
+        hipLaunchKernelGGL((frame_minmax_kernel<true>), grid, dim3(256), 0, st, Vt, Vd, mm_part, HW);
+    else
+        hipLaunchKernelGGL((frame_minmax_kernel<false>), grid, dim3(256), 0, st, Vt, Vd, mm_part, HW);
+    int rc = check_launch("frame_minmax_kernel");
+    if (rc != 0) return rc;
+    switch (gt_dtype) {
+        case 0: rc = launch_moments<uint8_t>(X, x_bs, Vt, Vd, gt, gt_bs, mm_part, minmax, part, B, HW, vec, st); break;
+        case 1: rc = launch_moments<int32_t>(X, x_bs, Vt, Vd, gt, gt_bs, mm_part, minmax, part, B, HW, vec, st); break;
+        case 2: rc = launch_moments<int64_t>(X, x_bs, Vt, Vd, gt, gt_bs, mm_part, minmax, part, B, HW, vec, st); break;
+        default: rc = launch_moments<float>(X, x_bs, Vt, Vd, gt, gt_bs, mm_part, minmax, part, B, HW, vec, st); break;
+    }
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(moments_merge_kernel, dim3(B), dim3(64), 0, st, part, moments, G);
+    return check_launch("moments_merge_kernel");
+}
+
+int onet_cascade_input(const float* Vt, const float* Vd, const float* minmax, const int64_t* counts, float* X2, int B, int HW,
+                       void* stream) {
+    ONET_REQUIRE(Vt && Vd && counts && X2, "cascade_input: null pointer");
+    ONET_REQUIRE(B > 0 && B <= 65535 && HW > 0, "cascade_input: bad shape");
+    const bool vec = HW % 4 == 0 && wide_ok(Vt, HW, 4) && wide_ok(Vd, HW, 4) && wide_ok(X2, HW, 4);
+    // (without minmax a block scans its whole frame first: one block per image)
+    const dim3 grid(minmax ? (unsigned)frame_parts(HW) : 1u, (unsigned)B);
+    if (vec)
+        hipLaunchKernelGGL((cascade_input_kernel<true>), grid, dim3(256), 0, as_stream(stream), Vt, Vd, minmax, counts, X2, B, HW);
+    else
+        hipLaunchKernelGGL((cascade_input_kernel<false>), grid, dim3(256), 0, as_stream(stream), Vt, Vd, minmax, counts, X2, B, HW);
+    return check_launch("cascade_input_kernel");
+}
 
 int onet_normalise_per_frame(const float* x, float* y, int planes, int HW, void* stream) {
     ONET_REQUIRE(x && y && planes > 0 && HW > 0, "normalise_per_frame: bad args");
-    hipLaunchKernelGGL(normalise_per_frame_kernel, dim3(planes), dim3(256), 0, as_stream(stream), x, y, HW,
-                       2.220446049250313e-16f);
+    hipLaunchKernelGGL(normalise_per_frame_kernel, dim3(planes), dim3(256), 0, as_stream(stream), x, y, HW);
     return check_launch("normalise_per_frame_kernel");
 }
 

@@ -816,3 +816,79 @@ def validate(onet, X, gt, into=None, want_labels=False, want_S=False, want_loss=
             S = S_fwd if S is None else S
             loss = _loss_value(Lt, S[:, :1], Ld, S[:, 1:]) if want_loss else None
         return Validation(counts[row:row + B], labels, S if want_S else None, Vt, Vd, loss)
+
+
+# ----------------------------------------------------------------------------- the performance report: SNR gain, two-stage cascade
+class EvalSnr:
+    """get_psnr's moments of a validation epoch, kept on the device beside an EvalCounts: an fp64 [capacity, 9] tensor whose rows
+    verify_step(..., snr=self) writes, one per image (ops.snr_moments' layout), and the host-side list of the batch sizes so far.
+    rows() is the epoch's one device-to-host copy; metrics.snr_report(rows, count rows, batch_sizes) does the rest on the host."""
+
+    def __init__(self, capacity, device):
+        self.moments = torch.zeros((int(capacity), 9), dtype=torch.float64, device=device)
+        self.batch_sizes = []
+
+    def __len__(self):
+        return sum(self.batch_sizes)
+
+    def reset(self):
+        self.moments.zero_()
+        self.batch_sizes = []
+
+    def reserve(self, B):
+        """-> the first of the B rows the next batch writes"""
+        row = len(self)
+        if row + B > self.moments.shape[0]:
+            raise ValueError(f"onet_amd: EvalSnr of {self.moments.shape[0]} images cannot take {B} more after {row}")
+        self.batch_sizes.append(int(B))
+        return row
+
+    def rows(self):
+        """float64 [images so far, 9] on the host"""
+        return self.moments[:len(self)].cpu()
+
+
+Verification = namedtuple("Verification", "counts moments labels Vt Vd")
+
+
+def verify_step(onet, X, gt, into=None, snr=None, want_labels=False):
+    """One step of BOTH loops of the reference's performance report (verify_onet_simclutter, TS:420-454) on one forward:
+    validate(onet, X, gt, into, want_labels) -- test_simclutter's part: the same forward, the same ops.score_counts launch, its counts
+    and labels -- then ops.snr_moments on that forward's Vt, Vd: measure_snr_on_fg's part (TS:46-95), the sums and maxima get_psnr
+    takes of X, n(Vt) and n(Vd), per image, into rows of `snr` (an EvalSnr) or, without one, of a fresh [B, 9] tensor.  Which of
+    n(Vt) / n(Vd) is the foreground follows from the batch's counts: metrics.snr_report decides on the host, once per epoch.  `X`
+    must be [B, 1, H, W] (get_psnr asserts img.shape == label.shape); `into` and `snr` must stand at the same row.  No host
+    synchronisation: everything returned is a device tensor.
+    -> Verification(counts [B, 4], moments = the fp64 [B, 9] view of this batch's rows, labels | None, Vt, Vd)"""
+    if X.dim() != 4 or X.shape[1] != 1:
+        raise ValueError(f"onet_amd: verify_step takes a one-channel [B, 1, H, W] input (get_psnr compares it with the label map), got {tuple(X.shape)}")
+    if into is not None and snr is not None and len(into) != len(snr):
+        raise ValueError(f"onet_amd: verify_step: the EvalCounts stands at row {len(into)}, the EvalSnr at row {len(snr)}")
+    B = X.shape[0]
+    if snr is not None and len(snr) + B > snr.moments.shape[0]:       # (before validate reserves its rows)
+        raise ValueError(f"onet_amd: EvalSnr of {snr.moments.shape[0]} images cannot take {B} more after {len(snr)}")
+    v = validate(onet, X, gt, into=into, want_labels=want_labels)
+    with torch.no_grad():
+        if snr is None:
+            moments, row = torch.empty((B, 9), dtype=torch.float64, device=v.Vt.device), 0
+        else:
+            moments, row = snr.moments, snr.reserve(B)
+        ops.snr_moments(X, v.Vt, v.Vd, gt, moments, row=row)
+    return Verification(v.counts, moments[row:row + B], v.labels, v.Vt, v.Vd)
+
+
+def cascade_input(Vt, Vd, counts):
+    """The second stage's input of the two-stage cascade (TS:327-332), X2 [B, 1, H, W] = tensor_normal_per_frame of Vt where the hard
+    re-assignment flips the batch's labels and of Vd where it keeps them, the decision read on the device from `counts` (the [B, 4]
+    rows validate returned for this batch): no torch.equal, no host round trip in the middle of the batch."""
+    with torch.no_grad():
+        return ops.cascade_input(Vt, Vd, counts)
+
+
+def verify_cascade(onet, onet2nd, X, gt, into=None, into2=None):
+    """One batch of test_2nd_stage_simclutter (TS:312-345): validate(onet, X, gt, into), cascade_input of its Vt, Vd and counts,
+    validate(onet2nd, X2, gt, into2) -- each model under its own settings, nothing synchronises.  metrics.cascade_metrics turns the
+    two EvalCounts into the report.  -> (Validation of the first stage, Validation of the second)"""
+    v1 = validate(onet, X, gt, into=into)
+    v2 = validate(onet2nd, cascade_input(v1.Vt, v1.Vd, v1.counts), gt, into=into2)
+    return v1, v2

@@ -229,3 +229,53 @@ def evaluate(onet, X, labels):
         c = confusion_counts(pred, labels)
     return {"acc": _acc(c), "miou": _miou(c), "target_iou": _target_iou(c), "dr": _detection_rate(c),
             "far": _false_alarm_rate(c)}
+
+
+# ----------------------------------------------------------------------------- the performance report: SNR gain, two-stage cascade
+def _get_psnr(sum_t, sum_bg, peak, n_t, numel):
+    """get_psnr's statements after its sums (UT:466-476) in float64, in its order; a batch without target pixels gives what it gives
+    (0 / 0 -> nan, log10(0) -> -inf), not an exception.  -> (psnr, snr)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n_t = np.float64(n_t)
+        target_power = np.float64(sum_t) / n_t
+        erc = np.float64(sum_bg) / (np.float64(numel) - n_t)
+        psnr = 10 * np.log10(np.float64(peak) ** 2 / erc)
+        snr = 10 * np.log10(target_power / erc)
+    return float(psnr), float(snr)
+
+
+def snr_report(moment_rows, count_rows, batch_sizes):
+    """measure_snr_on_fg's result (TS:46-95) from an epoch's per-image rows alone: `moment_rows` [n, 9] (EvalSnr.rows(): per image
+    (sum v^2 on the target, sum v^2 off it, max v on it) of X, n(Vt), n(Vd)), `count_rows` [n, 4] (EvalCounts.rows()), `batch_sizes`
+    the images of each batch in order.  Per batch get_psnr's formulas (UT:457-476) on the batch totals, float64: peak = the largest of
+    the images' maxima, target pixels = TP + FN, all pixels = the four counts' sum; the foreground is n(Vt) where the hard
+    re-assignment flips the batch (acc < acc of the flipped counts, compared as integers: both are the counts over one float64
+    numel) and n(Vd) where it keeps it (TS:80-83).  -> {"input_psnr", "input_snr", "fg_psnr", "fg_snr": the means over batches
+    (TS:91-94), "per_batch": [{"flipped", "input_psnr", "input_snr", "fg_psnr", "fg_snr"}]}"""
+    mom = np.asarray(moment_rows, dtype=np.float64).reshape(-1, 9)
+    cnt = np.asarray(count_rows, dtype=np.int64).reshape(-1, 4)
+    if sum(batch_sizes) != mom.shape[0] or mom.shape[0] != cnt.shape[0]:
+        raise ValueError(f"snr_report: {mom.shape[0]} moment rows and {cnt.shape[0]} count rows for batches of {list(batch_sizes)}")
+    per_batch, r0 = [], 0
+    for n in batch_sizes:
+        m, c = mom[r0:r0 + n], cnt[r0:r0 + n]
+        r0 += n
+        tp, fp, fn, tn = (int(v) for v in c.sum(axis=0))
+        flip = (tp + tn) < (fp + fn)
+        vals = {}
+        for name, s in (("input", 0), ("fg", 1 if flip else 2)):
+            vals[name] = _get_psnr(m[:, 3 * s].sum(), m[:, 3 * s + 1].sum(), m[:, 3 * s + 2].max(), tp + fn, tp + fp + fn + tn)
+        per_batch.append({"flipped": flip, "input_psnr": vals["input"][0], "input_snr": vals["input"][1],
+                          "fg_psnr": vals["fg"][0], "fg_snr": vals["fg"][1]})
+    out = {k: float(np.array([b[k] for b in per_batch], dtype=np.float64).mean()) for k in ("input_psnr", "input_snr", "fg_psnr", "fg_snr")}
+    out["per_batch"] = per_batch
+    return out
+
+
+def cascade_metrics(rows1, rows2, batch_sizes):
+    """test_2nd_stage_simclutter's numbers (TS:296-390) from the two stages' per-image confusion counts (the EvalCounts.rows() that
+    verify_cascade filled): each stage through epoch_metrics(..., "simclutter").  -> {"stage1": (acc, miou, dr, far, tiou), "stage2":
+    (...), "reference_return": (acc2, miou2, dr2, far2, tiou1) -- what TS:390 returns, the FIRST stage's tiou included as there}"""
+    s1 = epoch_metrics(rows1, batch_sizes, "simclutter")
+    s2 = epoch_metrics(rows2, batch_sizes, "simclutter")
+    return {"stage1": s1, "stage2": s2, "reference_return": s2[:4] + s1[4:]}

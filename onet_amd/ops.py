@@ -2803,6 +2803,75 @@ def label_counts(pred, gt, counts, row=0):
     return counts
 
 
+# per image and block of onet_snr_moments' fixed partition (include/onet_hip_verify.h): 9 doubles and 4 floats, at most 64 blocks
+_SNR_WS_PER_IMAGE = 64 * (9 * 8 + 4 * 4)
+
+
+def _scores_pair(Vt, Vd, what):
+    require_gpu(Vt, Vd)
+    if Vt.shape != Vd.shape or Vt.dim() != 4 or Vt.shape[1] != 1 or Vt.dtype != F32 or Vd.dtype != F32:
+        raise ValueError(f"{what}: Vt and Vd must be fp32 [B, 1, H, W] tensors of one shape")
+    return Vt.contiguous(), Vd.contiguous()
+
+
+def _minmax_rows(minmax, B, device, what):
+    if minmax is None:
+        return torch.empty((B, 4), dtype=F32, device=device)
+    if minmax.dtype != F32 or tuple(minmax.shape) != (B, 4) or not minmax.is_cuda or not minmax.is_contiguous():
+        raise ValueError(f"{what}: minmax must be a contiguous fp32 [{B}, 4] tensor on the GPU")
+    return minmax
+
+
+def snr_moments(X, Vt, Vd, gt, moments, row=0, minmax=None):
+    """What get_psnr (UT:457-476) is made of, per image, in one call: rows [row, row + B) of `moments` (fp64 [n, 9]) are WRITTEN with
+    (sum v^2 on the target, sum v^2 off it, max(0, max v on it)) of X as it is, of n(Vt) and of n(Vd) -- n = tensor_normal_per_frame's
+    expression in fp32, each square and every sum in fp64, a fixed summation order (the same bits in every run) -- and `minmax` (fp32
+    [B, 4], allocated where None) with (min Vt, max Vt, min Vd, max Vd).  Vt, Vd fp32 [B, 1, H, W]; X fp32 of the same shape (a batch
+    slice of a wider tensor is read where it lies) or None: its three values are written as 0; gt as score_counts takes it.
+    -> minmax"""
+    Vt, Vd = _scores_pair(Vt, Vd, "snr_moments")
+    B, _, H, W = Vt.shape
+    x_bs = H * W
+    if X is not None:
+        require_gpu(X)
+        if X.shape != Vt.shape or X.dtype != F32:
+            raise ValueError(f"snr_moments: X must be an fp32 tensor of Vt's shape {tuple(Vt.shape)}, got {tuple(X.shape)}")
+        if not X[0].is_contiguous() or (B > 1 and X.stride(0) < H * W):
+            X = X.contiguous()
+        x_bs = X.stride(0) if B > 1 else H * W
+    gt, code, gbs = _label_map(gt, B, H * W, "snr_moments")
+    if moments.dtype != torch.float64 or moments.dim() != 2 or moments.shape[1] != 9 or not moments.is_cuda or not moments.is_contiguous():
+        raise ValueError("snr_moments: moments must be a contiguous float64 [n, 9] tensor on the GPU")
+    if row < 0 or row + B > moments.shape[0]:
+        raise ValueError(f"snr_moments: rows [{row}, {row + B}) outside a moments tensor of {moments.shape[0]} rows")
+    minmax = _minmax_rows(minmax, B, Vt.device, "snr_moments")
+    ws = workspace(B * _SNR_WS_PER_IMAGE, Vt.device)
+    _lib.call("onet_snr_moments", _p(X), x_bs, _p(Vt), _p(Vd), _p(gt), code, gbs, moments.data_ptr() + 72 * row, _p(minmax), B, H * W,
+              _p(ws), ws.numel() * 4, _stream(),
+              nbytes=B * H * W * (4.0 * (4 + (X is not None)) + gt.element_size()))
+    return minmax
+
+
+def cascade_input(Vt, Vd, counts, minmax=None, out=None):
+    """The two-stage cascade's second input (TS:327-332) without the host round trip: X2 = n(Vt) where the hard re-assignment flips
+    this batch's labels, n(Vd) where it keeps them -- the decision is read on the device from `counts`, the batch's B int64
+    (TP, FP, FN, TN) rows as score_counts left them: flip = (sum TP + sum TN) < (sum FP + sum FN).  minmax: snr_moments' [B, 4], or
+    None: the kernel finds the selected frames' min / max itself.  -> X2 fp32 [B, 1, H, W] (`out` where given)"""
+    Vt, Vd = _scores_pair(Vt, Vd, "cascade_input")
+    B, _, H, W = Vt.shape
+    if counts.dtype != torch.int64 or tuple(counts.shape) != (B, 4) or not counts.is_cuda or not counts.is_contiguous():
+        raise ValueError(f"cascade_input: counts must be the batch's contiguous int64 [{B}, 4] rows on the GPU")
+    if minmax is not None:
+        minmax = _minmax_rows(minmax, B, Vt.device, "cascade_input")
+    if out is None:
+        out = torch.empty_like(Vt)
+    elif out.shape != Vt.shape or out.dtype != F32 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError(f"cascade_input: out must be a contiguous fp32 tensor of Vt's shape {tuple(Vt.shape)} on the GPU")
+    _lib.call("onet_cascade_input", _p(Vt), _p(Vd), _p(minmax), _p(counts), _p(out), B, H * W, _stream(),
+              nbytes=B * H * W * (8.0 if minmax is not None else 12.0))
+    return out
+
+
 # ----------------------------------------------------------------------------- optimizer
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
     """one torch.optim.Adam step over flat buffers; the hyper-parameters go down as doubles (include/onet_hip_optim.h)"""
